@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/s of the vectorised env step (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--workload terrain|flat|trimesh|abb] [--envs 4096]
+    python bench.py --gpus N --steps K --warmup W [--workload terrain|flat|trimesh|abb] [--envs 4096] [--full] [--dump-outputs DIR]
 
 One "step" = one ShifuVecEnv.step over all envs of this rank with random actions
 `2*rand-1` (the reference's run_mode='random' driver, shifu/runner/policy_runner.py:33-41).
@@ -12,8 +12,11 @@ IK, 6 sub-steps of 20 ms with box contacts, refresh, termination, rewards, re-sp
 inside shf_abb_step.  For N>1 an RCCL all-gather of the (sum,count) episode statistics every 24
 steps is the only cross-rank traffic: envs shard with no data-path collective ("weak" scaling).
 
-Rank 0 prints ONE JSON line.  `roofline.achieved` = B_alg x envs / mean duration of the fused
-kernel, measured with HIP events on the launch stream inside the timed region; `roofline.secondary`
+Rank 0 prints ONE JSON line: `value` (env-steps/s over the K timed vec-steps) and `ms_per_step`.  A plain run does only
+that (set up, warm up, time, print); --dump-outputs DIR also writes the arrays of the last timed vec-step as DIR/<name>.npy.
+--full adds the figures that take passes of their own, after the timed region (the dump is taken before them):
+`roofline.achieved` = B_alg x envs / mean duration of the fused kernel, measured with HIP events on the launch stream
+over a second pass of K launches; `roofline.secondary`
 prices the same launch against the fp32 vector peak with the algorithm's counted flops and states
 the occupancy; `cpu_baseline` times the CPU oracle (a port, not the reference: Isaac Gym is not
 installable) on a bounded sample of the same workload on this box's host cores.
@@ -219,6 +222,33 @@ def committed_profile(kernel_key: str):
         return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, per_env: dict, shared: dict, n: int, seed: int = 0) -> None:
+    """Write what the timed vec-step hands its caller as <path>/<name>.npy: integer / bool tensors as float64 / float32
+    (exact), per-env tensors (leading dimension n, or n x something) with the env as the first axis.  Past DUMP_LIMIT_BYTES
+    in all, a fixed seeded sample of envs is written for every per-env array, and its env ids as env_index.npy."""
+    def host(t):
+        a = t.detach().cpu().numpy()
+        return a.astype(np.float64 if a.dtype in (np.int64, np.int32, np.float64) else np.float32)
+    env_arrays = {}
+    for k, t in per_env.items():
+        a = host(t)
+        env_arrays[k] = a if a.shape[0] == n else a.reshape((n, a.shape[0] // n) + a.shape[1:])
+    shared = {k: host(t) for k, t in shared.items()}
+    per_env_bytes = sum(a.nbytes for a in env_arrays.values())
+    budget = DUMP_LIMIT_BYTES - sum(a.nbytes for a in shared.values()) - 8 * n
+    if per_env_bytes > budget:
+        keep = max(1, int(n * budget / per_env_bytes))
+        idx = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        env_arrays = {k: a[idx] for k, a in env_arrays.items()}
+        shared["env_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in list(env_arrays.items()) + list(shared.items()):
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -266,6 +296,13 @@ def main():
     ap.add_argument("--decimation", type=int, default=4, help="(experiments only) control.decimation")
     ap.add_argument("--no-extra-substep", action="store_true", help="(experiments only) drop the Q1 sub-step")
     ap.add_argument("--log-interval", type=int, default=24, help="all-gather period (num_steps_per_env)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: the kernel-only pass (roofline), the candidate-count pass, "
+                         "dropped constraints, the `other_solver` leg and the CPU baseline (off by default: a plain run sets up, "
+                         "warms up, times --steps vec-steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed vec-step computed on rank 0 (obs, rew, reset, time_out, "
+                         "episode_length, dof_state, root_state, body_state, episode_stats) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -406,15 +443,16 @@ def main():
 
     torch.cuda.synchronize()
     # constraints / contacts beyond the per-env limits (SHF_T_DROPPED: counted by the kernels, never cleared here): the count
-    # before the timed region, read again after it -- one D2H on each side, outside the clock
-    dropped_t = env.sim.tensors.get(_abi.T_DROPPED)
+    # before the timed region, read again after it -- one D2H on each side, outside the clock (--full)
+    dropped_t = env.sim.tensors.get(_abi.T_DROPPED) if args.full else None
     dropped0 = int(dropped_t.sum().item()) if dropped_t is not None else None
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
+    slot = None
     t0 = time.perf_counter()
     for i in range(args.steps):
-        vec_step(i)
+        slot = vec_step(i)
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
@@ -422,30 +460,40 @@ def main():
     elapsed = time.perf_counter() - t0
     dropped1 = int(dropped_t.sum().item()) if dropped_t is not None else None
     envs_dropping = int((dropped_t > 0).sum().item()) if dropped_t is not None else None
+    if args.dump_outputs and rank == 0 and slot is not None:
+        # the buffers still hold the last timed vec-step: nothing has launched since
+        S = env.sim.tensors
+        dump_outputs(args.dump_outputs,
+                     {"obs": env.obs_buf, "rew": env.rew_buf, "reset": env.reset_buf, "time_out": env.time_out_buf,
+                      "episode_length": env.episode_length_buf, "dof_state": S[_abi.T_DOF_STATE],
+                      "root_state": S[_abi.T_ROOT_STATE], "body_state": S[_abi.T_BODY_STATE]},
+                     {"episode_stats": env.task.tensors[stats_t][slot]}, N)
 
-    # duration of the fused kernel alone: HIP events on the launch stream around each of K eager launches
-    events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-    if args.actions == "kernel":
-        # the vec-step IS the kernel launch: one pair of events around K back-to-back launches (an event pair around every
-        # launch adds ~2 us of event processing to each and reads higher than rocprofv3's per-kernel duration)
-        events[0][0].record()
-        for i in range(args.steps):
-            eager_step()
-        events[0][1].record()
-        torch.cuda.synchronize()
-        kern_ms = events[0][0].elapsed_time(events[0][1]) / args.steps
-    else:
-        for i in range(args.steps):
-            eager_step(events[i])
-        torch.cuda.synchronize()
-        kern_ms = sum(a.elapsed_time(b) for a, b in events) / args.steps
+    kern_ms = None
+    if args.full:
+        # duration of the fused kernel alone: HIP events on the launch stream around each of K eager launches
+        events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        if args.actions == "kernel":
+            # the vec-step IS the kernel launch: one pair of events around K back-to-back launches (an event pair around every
+            # launch adds ~2 us of event processing to each and reads higher than rocprofv3's per-kernel duration)
+            events[0][0].record()
+            for i in range(args.steps):
+                eager_step()
+            events[0][1].record()
+            torch.cuda.synchronize()
+            kern_ms = events[0][0].elapsed_time(events[0][1]) / args.steps
+        else:
+            for i in range(args.steps):
+                eager_step(events[i])
+            torch.cuda.synchronize()
+            kern_ms = sum(a.elapsed_time(b) for a, b in events) / args.steps
 
     # candidate constraints per env and sub-step BEFORE the max_contacts cap (SHF_T_CONTACT_HIST), from a third, untimed pass of
     # up to 100 steps with the histogram bound (binding it costs the kernel one read-modify-write per env and sub-step: kept out of
-    # the timed region and of the kernel_ms pass)
+    # the timed region and of the kernel_ms pass; --full)
     cand_hist = None
     hard = args.solver in ("pgs", "tgs")
-    if hard and graph is None:
+    if args.full and hard and graph is None:
         ht = env.sim.bind_contact_hist(True)
         for i in range(min(args.steps, 100)):
             eager_step()
@@ -471,9 +519,8 @@ def main():
     finite = bool(torch.isfinite(env.obs_buf).all().item())
     resets = int(env.task.tensors[count_t].sum().item())
 
-    if rank == 0:
-        total_envs = N * world
-        value = total_envs * args.steps / elapsed
+    roofline = None
+    if rank == 0 and args.full:
         b_alg = B_ALG[args.workload]
         achieved = b_alg * N / (kern_ms * 1e-3) / 1e9
         prof = committed_profile(f"{kernel}_{args.workload}_g{group}" + ("_" + mapping if mapping != "body" else "") + ("_" + args.solver if args.solver in ("pgs", "tgs") else "") + ("_link" if (abb and args.link_contacts) else "")) if (N == 4096 and not args.self_collision) else None
@@ -513,6 +560,24 @@ def main():
                                                           "2.30 / 1.93 clk per SIMD at 2 / 4 waves; peak priced at 2 clk (MI355X_MICROARCH.md) and 2.4 GHz",
                                            "note": "the launch is bound by the dependent chain of each wave (LDS hand-offs, "
                                                    "IEEE div/sqrt sequences), not by chip-wide issue slots: see single_wave_issue_frac"}
+        roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS,
+                    "peak_achievable": HBM_ACHIEVABLE_GBS, "frac_of_achievable": achieved / HBM_ACHIEVABLE_GBS,
+                    "traffic": None if not prof else prof.get("traffic_bytes"),
+                    "traffic_source": None if not prof else prof.get("source"),
+                    # the loaded kernel's machine-code hash (shifu_amd/build.py: kernel_code_hashes) against the one the replayed
+                    # counters were collected from: true = the counters describe another build of this kernel (re-profile)
+                    "kernel_symbol": entry, "kernel_code_sha": None if vg is None else vg.get("code_sha"),
+                    "counters_kernel_sha": None if not prof else prof.get("kernel_code_sha"),
+                    "counters_stale": None if not prof else (prof.get("kernel_code_sha") is None or vg is None or prof.get("kernel_code_sha") != vg.get("code_sha")),
+                    "kernel": (("k_a1_chain_" + args.solver + ("16" if int(env.sim_params.max_contacts) > 8 else "")) if (kernel == "k_a1_step" and args.solver in ("pgs", "tgs")) else "k_a1_chain" if (kernel == "k_a1_step" and mapping == "chain") else "k_abb_step_ws" if (kernel == "k_abb_step" and mapping == "split") else "k_abb_step_pgs_wide" if (abb and "pgs_wide" in env.task.kernel_symbol()) else kernel), "kernel_ms": kern_ms, "alg_bytes_per_env_step": b_alg,
+                    "note": "latency/ALU-bound by design: a few KB of compulsory traffic per env-step (DESIGN.md 5)" +
+                            ("; alg_bytes counts the env's own tensors (state in, state / body_state / contact / Jacobian / obs out): link contacts "
+                             "add work on the LDS-resident model and scene, not tensors, so B_alg is the rod-only scene's" if (abb and args.link_contacts) else ""),
+                    "secondary": secondary}
+    if rank == 0:
+        total_envs = N * world
+        value = total_envs * args.steps / elapsed
         out = {
             "metric": ("env-steps/sec (whole node), ABB push-box 6-dof arm + free cube, 4096 envs/GPU" if abb else
                        "env-steps/sec (whole node), A1 12-dof 4096 envs/GPU"), "value": value, "unit": "env-steps/s",
@@ -550,30 +615,16 @@ def main():
                        "candidates_per_substep_hist": None if cand_hist is None else [round(float(x), 5) for x in cand_hist / max(cand_hist.sum(), 1.0)],
                        "candidates_per_substep_mean": None if cand_hist is None else float((cand_hist * np.arange(len(cand_hist))).sum() / max(cand_hist.sum(), 1.0)),
                        "substeps_above_cap_frac": None if cand_hist is None else float(cand_hist[((int(env.sim_params.max_contacts) or 8) + 1):].sum() / max(cand_hist.sum(), 1.0)),
-                       "gathers_in_timed_region": gathers["timed"], "gathers_in_warmup": gathers["warmup"]},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "peak_achievable": HBM_ACHIEVABLE_GBS, "frac_of_achievable": achieved / HBM_ACHIEVABLE_GBS,
-                         "traffic": None if not prof else prof.get("traffic_bytes"),
-                         "traffic_source": None if not prof else prof.get("source"),
-                         # the loaded kernel's machine-code hash (shifu_amd/build.py: kernel_code_hashes) against the one the replayed
-                         # counters were collected from: true = the counters describe another build of this kernel (re-profile)
-                         "kernel_symbol": entry, "kernel_code_sha": None if vg is None else vg.get("code_sha"),
-                         "counters_kernel_sha": None if not prof else prof.get("kernel_code_sha"),
-                         "counters_stale": None if not prof else (prof.get("kernel_code_sha") is None or vg is None or prof.get("kernel_code_sha") != vg.get("code_sha")),
-                         "kernel": (("k_a1_chain_" + args.solver + ("16" if int(env.sim_params.max_contacts) > 8 else "")) if (kernel == "k_a1_step" and args.solver in ("pgs", "tgs")) else "k_a1_chain" if (kernel == "k_a1_step" and mapping == "chain") else "k_abb_step_ws" if (kernel == "k_abb_step" and mapping == "split") else "k_abb_step_pgs_wide" if (abb and "pgs_wide" in env.task.kernel_symbol()) else kernel), "kernel_ms": kern_ms, "alg_bytes_per_env_step": b_alg,
-                         "note": "latency/ALU-bound by design: a few KB of compulsory traffic per env-step (DESIGN.md 5)" +
-                                 ("; alg_bytes counts the env's own tensors (state in, state / body_state / contact / Jacobian / obs out): link contacts "
-                                  "add work on the LDS-resident model and scene, not tensors, so B_alg is the rod-only scene's" if (abb and args.link_contacts) else ""),
-                         "secondary": secondary},
+                       "gathers_in_timed_region": gathers["timed"], "gathers_in_warmup": gathers["warmup"], "full": bool(args.full)},
+            "roofline": roofline,
         }
-        if kern_ms > out["ms_per_step"]:
+        if args.full and kern_ms > out["ms_per_step"]:
             # a kernel cannot take longer than the step that contains it: the two are different passes of K launches (the
             # timed region by the host clock, then a second pass bracketed by HIP events) and differ by run-to-run noise
             out["roofline"]["kernel_ms_note"] = ("kernel_ms (HIP events, second pass of K launches) reads above ms_per_step (host clock, "
                                                  "timed pass): pass-to-pass noise, not a longer kernel; roofline.achieved uses kernel_ms, "
                                                  "the more conservative of the two")
-        if world == 1 and not solver_given and not args.no_other_solver and args.actions == "kernel" and graph is None:
+        if args.full and world == 1 and not solver_given and not args.no_other_solver and args.actions == "kernel" and graph is None:
             # the driver runs the default command only: the opt-in compliant law of rounds 1-4 on the same workload, same K and
             # W, same clock, so that one line carries both (a fresh env; the main measurement above is already taken)
             other = "compliant" if args.solver in ("pgs", "tgs") else "pgs"
@@ -597,7 +648,7 @@ def main():
                                    "obs_finite": bool(torch.isfinite(env2.obs_buf).all().item()),
                                    "note": "the same workload under the solver that is not the default, timed the same way (host clock, K steps after W "
                                            "warm-up steps); compliant = the spring-damper law of rounds 1-4 (opt-in: --solver compliant)"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             scene_kw = {"link_contacts": bool(args.link_contacts), "link_shapes": args.link_shapes} if abb else {}
             cb = out["cpu_baseline"] = cpu_baseline(args.workload, solver_kw={"solver": args.solver, "pos_iters": args.pos_iters, "vel_iters": args.vel_iters, **({} if args.max_contacts is None else {"max_contacts": args.max_contacts})}, **scene_kw)     # the only leg that touches oracle/
             f_alg = cb["flops_per_env_step"]

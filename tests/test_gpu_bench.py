@@ -89,7 +89,7 @@ def test_a_failing_rank_fails_the_job():
 
 def test_bench_one_rank_over_rccl():
     """The same code path on RCCL (backend nccl) with a single rank: what every rank of the driver's 8-GPU run executes."""
-    out = _run_bench(["--gpus", "1", "--steps", "30", "--warmup", "5", "--no-cpu-baseline"],
+    out = _run_bench(["--gpus", "1", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--full"],
                      {"SHIFU_AMD_FORCE_DIST": "1", "RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1",
                       "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(_free_port())}, "1rank_rccl")
     assert out["n_gpus"] == 1 and out["config"]["total_envs"] == 4096

@@ -1,7 +1,7 @@
 set -u
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 OUT=gpurun_out/final; mkdir -p $OUT
-B="--steps 500 --warmup 50"
+B="--steps 500 --warmup 50 --full"
 bash tools/profile.sh r06_abb_tgs --workload abb > /dev/null 2>&1
 bash tools/profile.sh r06_abb_pgs --workload abb --solver pgs > /dev/null 2>&1
 find gpurun_out -name "*kernel_trace.csv" -size +4M -delete

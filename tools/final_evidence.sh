@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd "$REPO"
 PARTS=${*:-tests bench sweep hooks phase prof soak}
 has() { [[ " $PARTS " == *" $1 "* ]]; }
-B="--steps 500 --warmup 50"
+B="--steps 500 --warmup 50 --full"     # the bench lines carry roofline, cpu_baseline and other_solver
 if has tests; then
   python -m pytest tests -m gpu -q 2>&1 | tail -3 > "$OUT/pytest_gpu.txt"
   python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.txt" 2>&1
@@ -28,7 +28,7 @@ if has bench; then
   python bench.py --max-contacts 16 $B --no-cpu-baseline --no-other-solver > "$OUT/bench_terrain_k16.json" 2>/dev/null
   python bench.py --workload abb --solver tgs --mapping body $B --no-cpu-baseline --no-other-solver > "$OUT/bench_abb_body.json" 2>/dev/null
   python bench.py --workload abb --link-shapes hull $B --no-cpu-baseline --no-other-solver > "$OUT/bench_abb_hull.json" 2>/dev/null
-  python bench.py --steps 20 --warmup 5 > "$OUT/bench_terrain_driver_shape.json" 2>/dev/null
+  python bench.py --steps 20 --warmup 5 --full > "$OUT/bench_terrain_driver_shape.json" 2>/dev/null
   python bench.py --workload trimesh --self-collision $B --no-cpu-baseline --no-other-solver > "$OUT/bench_trimesh_selfcollision.json" 2>/dev/null
   python bench.py --workload abb --no-link-contacts $B --no-cpu-baseline > "$OUT/bench_abb_rod_only.json" 2>/dev/null
   # ... and the compliant law of rounds 1-4 (opt-in) on the same

@@ -29,7 +29,7 @@ def main(src, dst, key=None, kern="k_a1_step"):
     rows = list(csv.DictReader(open(os.path.join(src, "stats", "a1_kernel_stats.csv"))))
     out = ["# rocprofv3 summary: " + os.path.basename(src), "",
            "Command: `tools/profile.sh` (rocprofv3 --kernel-trace --stats, then separate --pmc passes) around",
-           "`python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline ...`; 4096 envs, 1x MI355X.", ""]
+           "`python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --full ...`; 4096 envs, 1x MI355X.", ""]
     bj = os.path.join(src, "bench_stats.json")
     kernel_sha = kernel_symbol = None
     if os.path.exists(bj):

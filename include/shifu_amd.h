@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SHF_ABI_VERSION 15
+#define SHF_ABI_VERSION 16
 
 #define SHF_MAX_BODIES 32 /* reported rigid bodies per articulation        */
 #define SHF_MAX_DOFS 32
@@ -783,6 +783,76 @@ int shf_ik_dls(const float* j_ee, int64_t j_env_stride, const float* dof_pos, in
  * sums[k] += terms[k]; HOST arrays of num_keys <= 16 device pointers to (num_envs) fp32 tensors. */
 int shf_reward_accumulate(const float* const* terms, float* const* sums, int32_t num_keys, int64_t num_envs, float* rew,
                           void* stream);
+
+/* ---- camera sensors: one ray per pixel against the analytic collision shapes (ABI v16; csrc/shf_render.hip) --------
+ * A render scene is kept apart from ShfModel (which the step kernels stage in LDS): every collision shape of the
+ * articulation and the box actors in the frame of the body whose body_state row moves it, and the terrain.  Conventions
+ * (DESIGN.md "Camera sensors"): a camera looks along its local +x with +z up; pixel (row r, col c), row 0 at the top,
+ * casts dir = fwd + right x t + up y t H/W with t = tan(hfov / 2), x = 2 (c + 1/2) / W - 1, y = 1 - 2 (r + 1/2) / H, so the
+ * ray parameter is the view-space depth.  A pixel shows the nearest surface ENTERED at a depth in [near, far] (surfaces
+ * entered before `near` are not drawn, like a back-face-culled rasteriser).  Color = body color x (AMBIENT + DIFFUSE
+ * max(0, n . LIGHT)), rounded to u8, alpha 255; nothing hit: depth +inf (-inf when ShfCamera.depth_negative), segmentation
+ * 0, the background color.  The constants below are mirrored in shifu_amd/render.py. */
+#define SHF_RENDER_MAX_SHAPES 64        /* one wave64 lane per shape in the per-wave cull                          */
+#define SHF_RENDER_MAX_POLYS 16
+#define SHF_RENDER_POLY_MAX_FACES 40    /* = SHF_HULL_MAX_FACES                                                   */
+#define SHF_RENDER_BOX 0                /* param = half extents                                                   */
+#define SHF_RENDER_SPHERE 1             /* param[0] = radius                                                      */
+#define SHF_RENDER_CAPSULE 2            /* param[0] = radius, param[1] = half length of the segment along local z */
+#define SHF_RENDER_POLY 3               /* convex polytope ShfRenderScene.poly[ShfRenderShape.poly]               */
+#define SHF_RENDER_AMBIENT 0.35f
+#define SHF_RENDER_DIFFUSE 0.65f
+#define SHF_RENDER_LIGHT_X 0.40824829f  /* unit vector towards the light: (1, 1, 2) / sqrt(6)                      */
+#define SHF_RENDER_LIGHT_Y 0.40824829f
+#define SHF_RENDER_LIGHT_Z 0.81649658f
+#define SHF_RENDER_BG_R 140             /* background RGB (u8)                                                    */
+#define SHF_RENDER_BG_G 170
+#define SHF_RENDER_BG_B 200
+
+typedef struct ShfRenderShape {
+  int32_t body;       /* body_state row within the env (0 .. num_bodies - 1)                                       */
+  int32_t kind;       /* SHF_RENDER_*                                                                              */
+  int32_t poly;       /* SHF_RENDER_POLY: index into ShfRenderScene.poly, else -1                                  */
+  int32_t pad;
+  float pos[3];       /* shape origin in the body frame                                                            */
+  float radius;       /* bounding sphere about pos (the per-wave frustum cull)                                     */
+  float rot[9];       /* shape axes in the body frame, row-major                                                   */
+  float param[3];
+} ShfRenderShape;
+
+typedef struct ShfRenderPoly {
+  int32_t nf, pad[3];
+  float plane[SHF_RENDER_POLY_MAX_FACES][4];  /* n . x <= w in the shape frame, unit outward n                    */
+} ShfRenderPoly;
+
+typedef struct ShfRenderScene {
+  int32_t nshapes, npolys;
+  int32_t num_bodies;   /* body_state rows per env (articulation bodies, then box actors)                          */
+  int32_t ground;       /* 1: the terrain passed to shf_render_cameras is drawn (segmentation 0), 0: no terrain     */
+  float ground_color[3];
+  float hf_zmin, hf_zmax; /* height field: lowest / highest sample x vscale (the bounding box the walk is clipped to) */
+  float pad[3];
+  ShfRenderShape shape[SHF_RENDER_MAX_SHAPES];
+  ShfRenderPoly poly[SHF_RENDER_MAX_POLYS];
+} ShfRenderScene;
+
+typedef struct ShfCamera {
+  int32_t width, height;
+  float horizontal_fov;  /* degrees, (0, 180)                                                                      */
+  float near_plane, far_plane;
+  int32_t depth_negative;  /* 1: depth written negated (Isaac Gym's IMAGE_DEPTH), -inf where nothing is hit           */
+} ShfCamera;
+
+/* Renders one camera per env for num_envs envs with one ShfCamera.  scene_dev: an ShfRenderScene in device memory;
+ * terrain / height_samples_dev: as bound to the sim (rows == 0: the plane z = 0; warped trimeshes are refused);
+ * body_state (num_envs * num_bodies, 13); cam_pose (num_envs, 7) pos + quat xyzw, in the body_state frame; seg_ids
+ * (num_envs, num_bodies) int32; colors (num_envs, num_bodies, 3) in [0, 1].  Outputs, each optional (NULL skips it):
+ * depth (num_envs, H, W) f32, seg (num_envs, H, W) int32, rgba (num_envs, H, W, 4) u8.  No atomics, no host sync:
+ * stream-ordered and capturable; a pixel depends only on its own env's inputs. */
+int shf_render_cameras(const ShfRenderScene* scene_dev, const ShfTerrain* terrain, const int16_t* height_samples_dev,
+                       const ShfCamera* camera, int32_t num_envs, const float* body_state, const float* cam_pose,
+                       const int32_t* seg_ids, const float* colors, float* depth_or_null, int32_t* seg_or_null,
+                       uint8_t* rgba_or_null, void* stream);
 
 #ifdef __cplusplus
 }

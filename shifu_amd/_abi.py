@@ -1,7 +1,7 @@
 """ctypes mirrors of the PODs in include/shifu_amd.h (keep in lock-step)."""
 import ctypes as C
 
-SHF_ABI_VERSION = 15
+SHF_ABI_VERSION = 16
 MAP_BODY, MAP_CHAIN, MAP_CHAIN_SPLIT = 0, 1, 2   # shf_sim_set_mapping
 MAX_BODIES = 32
 MAX_DOFS = 32
@@ -84,6 +84,34 @@ class ShfSimParams(C.Structure):
 class ShfTerrain(C.Structure):
     _fields_ = [("rows", i32), ("cols", i32), ("hscale", f32), ("vscale", f32), ("border", f32),
                 ("friction", f32), ("warped", i32), ("nz_min", f32)]
+
+
+# camera sensors (ABI v16; csrc/shf_render.hip)
+RENDER_MAX_SHAPES, RENDER_MAX_POLYS, RENDER_POLY_MAX_FACES = 64, 16, 40
+RENDER_BOX, RENDER_SPHERE, RENDER_CAPSULE, RENDER_POLY = 0, 1, 2, 3
+RENDER_AMBIENT, RENDER_DIFFUSE = 0.35, 0.65
+RENDER_LIGHT = (0.40824829, 0.40824829, 0.81649658)
+RENDER_BG = (140, 170, 200)
+
+
+class ShfRenderShape(C.Structure):
+    _fields_ = [("body", i32), ("kind", i32), ("poly", i32), ("pad", i32), ("pos", f32 * 3), ("radius", f32),
+                ("rot", f32 * 9), ("param", f32 * 3)]
+
+
+class ShfRenderPoly(C.Structure):
+    _fields_ = [("nf", i32), ("pad", i32 * 3), ("plane", (f32 * 4) * RENDER_POLY_MAX_FACES)]
+
+
+class ShfRenderScene(C.Structure):
+    _fields_ = [("nshapes", i32), ("npolys", i32), ("num_bodies", i32), ("ground", i32), ("ground_color", f32 * 3),
+                ("hf_zmin", f32), ("hf_zmax", f32), ("pad", f32 * 3),
+                ("shape", ShfRenderShape * RENDER_MAX_SHAPES), ("poly", ShfRenderPoly * RENDER_MAX_POLYS)]
+
+
+class ShfCamera(C.Structure):
+    _fields_ = [("width", i32), ("height", i32), ("horizontal_fov", f32), ("near_plane", f32), ("far_plane", f32),
+                ("depth_negative", i32)]
 
 
 class ShfA1TaskParams(C.Structure):

@@ -84,6 +84,8 @@ _SIGS = {
     "shf_gae": ([vp, vp, vp, vp, i32, i64, C.c_float, C.c_float, vp, vp], i32),
     "shf_ppo_loss_workspace": ([i64, i32, C.POINTER(i64)], i32),
     "shf_ppo_loss": ([vp] * 10 + [i64, i32, C.c_float, C.c_float, C.c_float, i32] + [vp] * 6, i32),
+    # camera sensors (csrc/shf_render.hip)
+    "shf_render_cameras": ([vp, C.POINTER(_abi.ShfTerrain), vp, C.POINTER(_abi.ShfCamera), i32] + [vp] * 7 + [vp], i32),
 }
 EXPORTS = sorted(list(_SIGS) + ["shf_last_error", "shf_mlp_last_error"])
 

@@ -1,5 +1,5 @@
-"""Sensor configs (reference shifu/configs/sensor_config.py).  Kept so user configs
-import; rasterised cameras themselves are out of scope on this backend."""
+"""Sensor configs (reference shifu/configs/sensor_config.py).  Camera sensors are rendered by a ray caster against the
+collision geometry (shifu_amd/units/sensors.py, shifu_amd/render.py)."""
 from shifu_amd.isaacgym import gymapi
 
 from .base_config import BaseConfig

@@ -1,0 +1,392 @@
+// shf_render.hip -- camera sensors (ABI v16): one ray per pixel against the analytic collision shapes of each env, the
+// ground plane or the height field.  No rasteriser: boxes, spheres, capsules and convex polytopes are intersected in
+// closed form, the height field by a 2-D DDA walk over its cells (two triangles each, split as the collision code splits
+// them: along (i+1, j)-(i, j+1)).  Conventions and constants: include/shifu_amd.h (ShfRenderScene); the checker is
+// tests/render_ref.py, an independent float64 brute-force caster.
+//
+// Layout: one 256-thread workgroup per (env, 16 x 16 pixel tile), a wave per 16 x 4 pixel strip.  The env's shape
+// world poses are built once per workgroup into LDS (one thread per shape); each wave then culls the shapes' bounding
+// spheres against the cone of its strip's rays (one lane per shape, a ballot), so the loop over candidate shapes is
+// wave-uniform and its LDS reads are broadcasts.  Stores are one dword per lane per image, 64 consecutive bytes per row.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "../../include/shifu_amd.h"
+
+int shf_set_error(const std::string& msg);   // shf_api.hip
+
+#define RT_TILE 16
+#define RT_THREADS 256
+#define RT_SW 20   // floats per shape in LDS: c[3] R[9] param[3] radius col[3] pad
+
+namespace {
+
+__device__ __forceinline__ float dot3(const float* a, const float* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+
+// row-major rotation of the unit quaternion (x, y, z, w)
+__device__ __forceinline__ void quat_mat(const float* q, float* R) {
+  const float x = q[0], y = q[1], z = q[2], w = q[3];
+  R[0] = 1.0f - 2.0f * (y * y + z * z); R[1] = 2.0f * (x * y - z * w);        R[2] = 2.0f * (x * z + y * w);
+  R[3] = 2.0f * (x * y + z * w);        R[4] = 1.0f - 2.0f * (x * x + z * z); R[5] = 2.0f * (y * z - x * w);
+  R[6] = 2.0f * (x * z - y * w);        R[7] = 2.0f * (y * z + x * w);        R[8] = 1.0f - 2.0f * (x * x + y * y);
+}
+
+// entry parameter of a sphere of radius r at the origin (INFINITY: missed); *n the outward unit normal there
+__device__ __forceinline__ float hit_sphere(const float* o, const float* d, float r, float* n) {
+  const float a = dot3(d, d), b = dot3(o, d), c = dot3(o, o) - r * r;
+  const float disc = b * b - a * c;
+  if (disc < 0.0f) return INFINITY;
+  const float s = (-b - sqrtf(disc)) / a;
+  const float ir = 1.0f / r;
+  for (int k = 0; k < 3; k++) n[k] = (o[k] + s * d[k]) * ir;
+  return s;
+}
+
+__device__ __forceinline__ float hit_box(const float* o, const float* d, const float* h, float* n) {
+  float sin_ = -INFINITY, sout = INFINITY;
+  int ax = 0;
+  for (int k = 0; k < 3; k++) {
+    const float inv = 1.0f / d[k];
+    const float t1 = (-h[k] - o[k]) * inv, t2 = (h[k] - o[k]) * inv;
+    const float tn = fminf(t1, t2), tf = fmaxf(t1, t2);
+    if (tn > sin_) { sin_ = tn; ax = k; }
+    sout = fminf(sout, tf);
+  }
+  if (!(sin_ <= sout)) return INFINITY;
+  for (int k = 0; k < 3; k++) n[k] = 0.0f;
+  n[ax] = d[ax] > 0.0f ? -1.0f : 1.0f;
+  return sin_;
+}
+
+// capsule along local z: the segment [-hl, hl], radius r -- the first entry into the cylinder or either end sphere
+__device__ __forceinline__ float hit_capsule(const float* o, const float* d, float r, float hl, float* n) {
+  float best = INFINITY;
+  const float a = d[0] * d[0] + d[1] * d[1];
+  if (a > 0.0f) {
+    const float b = o[0] * d[0] + o[1] * d[1], c = o[0] * o[0] + o[1] * o[1] - r * r;
+    const float disc = b * b - a * c;
+    if (disc >= 0.0f) {
+      const float s = (-b - sqrtf(disc)) / a;
+      const float z = o[2] + s * d[2];
+      if (fabsf(z) <= hl) {
+        best = s;
+        n[0] = (o[0] + s * d[0]) / r; n[1] = (o[1] + s * d[1]) / r; n[2] = 0.0f;
+      }
+    }
+  }
+  for (int e = 0; e < 2; e++) {
+    const float oc[3] = {o[0], o[1], o[2] - (e ? hl : -hl)};
+    float ns[3];
+    const float s = hit_sphere(oc, d, r, ns);
+    if (s < best) { best = s; n[0] = ns[0]; n[1] = ns[1]; n[2] = ns[2]; }
+  }
+  return best;
+}
+
+__device__ __forceinline__ float hit_poly(const ShfRenderPoly* __restrict__ P, const float* o, const float* d, float* n) {
+  float sin_ = -INFINITY, sout = INFINITY;
+  int face = -1;
+  const int nf = min(P->nf, SHF_RENDER_POLY_MAX_FACES);
+  for (int f = 0; f < nf; f++) {
+    const float pn[3] = {P->plane[f][0], P->plane[f][1], P->plane[f][2]};
+    const float dn = dot3(pn, d), num = P->plane[f][3] - dot3(pn, o);
+    if (dn < 0.0f) {
+      const float s = num / dn;
+      if (s > sin_) { sin_ = s; face = f; }
+    } else if (dn > 0.0f) {
+      sout = fminf(sout, num / dn);
+    } else if (num < 0.0f) {
+      return INFINITY;
+    }
+  }
+  if (face < 0 || !(sin_ <= sout)) return INFINITY;
+  n[0] = P->plane[face][0]; n[1] = P->plane[face][1]; n[2] = P->plane[face][2];
+  return sin_;
+}
+
+// the plane of the height-field triangle v0 v1 v2 (world coordinates) when the ray meets its front face (upward normal):
+// *s_out its parameter, n the unit normal; whether the hit lies inside the triangle is tested by the caller in cell units
+__device__ __forceinline__ bool hf_triangle(const float* o, const float* d, const float* v0, const float* v1, const float* v2,
+                                            float* s_out, float* n) {
+  const float e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
+  const float c[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+  const float dn = dot3(c, d);
+  if (!(dn < 0.0f)) return false;
+  const float w[3] = {v0[0] - o[0], v0[1] - o[1], v0[2] - o[2]};
+  *s_out = dot3(w, c) / dn;
+  const float il = 1.0f / sqrtf(dot3(c, c));
+  n[0] = c[0] * il; n[1] = c[1] * il; n[2] = c[2] * il;
+  return true;
+}
+
+// nearest front-facing height-field surface with s in [near, s_max]; the walk covers [near, s_max] clipped to the field's
+// bounding box, cell by cell in ray order (the first cell with a hit holds the nearest one: a front face is entered at most
+// once per cell, the two triangles being a graph over it)
+__device__ float hit_heightfield(const ShfTerrain& T, const int16_t* __restrict__ H, float zmin, float zmax, const float* o,
+                                 const float* d, float s_min, float s_max, float* n) {
+  const int rows = T.rows, cols = T.cols;
+  const float hs = T.hscale, vs = T.vscale, bd = T.border;
+  const float lo[3] = {-bd, -bd, zmin}, hi[3] = {(float)(rows - 1) * hs - bd, (float)(cols - 1) * hs - bd, zmax};
+  float s0 = s_min, s1 = s_max;
+  for (int k = 0; k < 3; k++) {
+    if (d[k] == 0.0f) {
+      if (o[k] < lo[k] || o[k] > hi[k]) return INFINITY;
+      continue;
+    }
+    const float inv = 1.0f / d[k];
+    const float t1 = (lo[k] - o[k]) * inv, t2 = (hi[k] - o[k]) * inv;
+    s0 = fmaxf(s0, fminf(t1, t2));
+    s1 = fminf(s1, fmaxf(t1, t2));
+  }
+  if (!(s0 <= s1)) return INFINITY;
+  const float ih = 1.0f / hs;
+  const float fx = (o[0] + s0 * d[0] + bd) * ih, fy = (o[1] + s0 * d[1] + bd) * ih;
+  int i = (int)fminf(fmaxf(floorf(fx), 0.0f), (float)(rows - 2));
+  int j = (int)fminf(fmaxf(floorf(fy), 0.0f), (float)(cols - 2));
+  const int si = d[0] > 0.0f ? 1 : -1, sj = d[1] > 0.0f ? 1 : -1;
+  const float tdx = d[0] != 0.0f ? hs / fabsf(d[0]) : INFINITY, tdy = d[1] != 0.0f ? hs / fabsf(d[1]) : INFINITY;
+  float sx = d[0] != 0.0f ? ((float)(i + (si > 0 ? 1 : 0)) * hs - bd - o[0]) / d[0] : INFINITY;
+  float sy = d[1] != 0.0f ? ((float)(j + (sj > 0 ? 1 : 0)) * hs - bd - o[1]) / d[1] : INFINITY;
+  const float eps = 1e-5f;
+  for (int it = 0; it < rows + cols; it++) {
+    const int16_t* r0 = H + (size_t)i * cols + j;
+    const int16_t* r1 = r0 + cols;
+    const float x0 = (float)i * hs - bd, y0 = (float)j * hs - bd, x1 = x0 + hs, y1 = y0 + hs;
+    const float v00[3] = {x0, y0, (float)r0[0] * vs}, v10[3] = {x1, y0, (float)r1[0] * vs};
+    const float v01[3] = {x0, y1, (float)r0[1] * vs}, v11[3] = {x1, y1, (float)r1[1] * vs};
+    float best = INFINITY, s, nn[3];
+    // lower triangle (u + v <= 1) and upper one (u + v >= 1), (u, v) the hit's position in the cell
+    if (hf_triangle(o, d, v00, v10, v01, &s, nn) && s >= s_min && s <= s_max) {
+      const float u = (o[0] + s * d[0] - x0) * ih, v = (o[1] + s * d[1] - y0) * ih;
+      if (u >= -eps && v >= -eps && u + v <= 1.0f + eps && s < best) { best = s; n[0] = nn[0]; n[1] = nn[1]; n[2] = nn[2]; }
+    }
+    if (hf_triangle(o, d, v11, v01, v10, &s, nn) && s >= s_min && s <= s_max) {
+      const float u = (o[0] + s * d[0] - x0) * ih, v = (o[1] + s * d[1] - y0) * ih;
+      if (u <= 1.0f + eps && v <= 1.0f + eps && u + v >= 1.0f - eps && s < best) { best = s; n[0] = nn[0]; n[1] = nn[1]; n[2] = nn[2]; }
+    }
+    if (best < INFINITY) return best;
+    if (fminf(sx, sy) > s1) break;
+    if (sx < sy) {
+      i += si; sx += tdx;
+      if (i < 0 || i > rows - 2) break;
+    } else {
+      j += sj; sy += tdy;
+      if (j < 0 || j > cols - 2) break;
+    }
+  }
+  return INFINITY;
+}
+
+__device__ __forceinline__ uint32_t shade_u8(float c, float lam) {
+  const float v = fminf(fmaxf(c * lam, 0.0f), 1.0f);
+  return (uint32_t)floorf(v * 255.0f + 0.5f);
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(RT_THREADS) k_render_cameras(const ShfRenderScene* __restrict__ scene, ShfTerrain T,
+                                                             const int16_t* __restrict__ hsamp, ShfCamera cam, int tiles_x,
+                                                             int tiles, const float* __restrict__ body_state,
+                                                             const float* __restrict__ cam_pose, const int32_t* __restrict__ seg_ids,
+                                                             const float* __restrict__ colors, float* __restrict__ depth,
+                                                             int32_t* __restrict__ seg_out, uint32_t* __restrict__ rgba) {
+  __shared__ float S[SHF_RENDER_MAX_SHAPES * RT_SW];
+  __shared__ int SI[SHF_RENDER_MAX_SHAPES * 3];   // kind, poly, segmentation id
+  const int env = blockIdx.x / tiles, tile = blockIdx.x - env * tiles;
+  const int tx = tile % tiles_x, ty = tile / tiles_x;
+  const int lid = threadIdx.x, wave = lid >> 6, lane = lid & 63;
+  const int W = cam.width, Hh = cam.height;
+  // (the scene is device data: its counts are clamped to the LDS tables here, not trusted)
+  const int ns = min(max(scene->nshapes, 0), SHF_RENDER_MAX_SHAPES), B = max(scene->num_bodies, 1);
+
+  // camera basis: fwd = local +x, up = local +z, right = -(local +y)
+  const float* cp = cam_pose + (size_t)env * 7;
+  float Rc[9];
+  {
+    const float q[4] = {cp[3], cp[4], cp[5], cp[6]};
+    quat_mat(q, Rc);
+  }
+  const float o[3] = {cp[0], cp[1], cp[2]};
+  const float fwd[3] = {Rc[0], Rc[3], Rc[6]}, right[3] = {-Rc[1], -Rc[4], -Rc[7]}, up[3] = {Rc[2], Rc[5], Rc[8]};
+  const float t = tanf(0.5f * cam.horizontal_fov * 0.017453292519943295f);
+  const float ty_scale = t * (float)Hh / (float)W;
+
+  if (lid < ns) {
+    const ShfRenderShape& sh = scene->shape[lid];
+    const size_t row = (size_t)env * B + min(max(sh.body, 0), B - 1);
+    const float* bsr = body_state + row * 13;
+    float Rb[9];
+    {
+      const float q[4] = {bsr[3], bsr[4], bsr[5], bsr[6]};
+      quat_mat(q, Rb);
+    }
+    float* s = S + lid * RT_SW;
+    for (int r = 0; r < 3; r++) {
+      s[r] = bsr[r] + Rb[3 * r] * sh.pos[0] + Rb[3 * r + 1] * sh.pos[1] + Rb[3 * r + 2] * sh.pos[2];
+      for (int c = 0; c < 3; c++)
+        s[3 + 3 * r + c] = Rb[3 * r] * sh.rot[c] + Rb[3 * r + 1] * sh.rot[3 + c] + Rb[3 * r + 2] * sh.rot[6 + c];
+      s[12 + r] = sh.param[r];
+      s[16 + r] = colors[row * 3 + r];
+    }
+    s[15] = sh.radius;
+    SI[lid * 3] = sh.kind;
+    SI[lid * 3 + 1] = sh.poly;
+    SI[lid * 3 + 2] = seg_ids[row];
+  }
+  __syncthreads();
+
+  // this wave's strip: columns [c0, c0 + 16), rows [r0, r0 + 4)
+  const int c0 = tx * RT_TILE, r0 = ty * RT_TILE + wave * 4;
+  const int col = c0 + (lane & 15), rowp = r0 + (lane >> 4);
+  const float iW = 1.0f / (float)W, iH = 1.0f / (float)Hh;
+
+  // per-wave cull: the cone around the strip's central ray that holds its four corner rays, against each shape's
+  // bounding sphere and the [near, far] depth range (lane k tests shape k)
+  uint64_t cand;
+  {
+    const float xa = 2.0f * (float)c0 * iW - 1.0f, xb = 2.0f * (float)(c0 + RT_TILE) * iW - 1.0f;
+    const float ya = 1.0f - 2.0f * (float)r0 * iH, yb = 1.0f - 2.0f * (float)(r0 + 4) * iH;
+    float ax[3];
+    for (int k = 0; k < 3; k++) ax[k] = fwd[k] + right[k] * (0.5f * (xa + xb) * t) + up[k] * (0.5f * (ya + yb) * ty_scale);
+    const float ian = 1.0f / sqrtf(dot3(ax, ax));
+    for (int k = 0; k < 3; k++) ax[k] *= ian;
+    float cmin = 1.0f;
+    for (int e = 0; e < 4; e++) {
+      const float xx = (e & 1) ? xb : xa, yy = (e & 2) ? yb : ya;
+      float dd[3];
+      for (int k = 0; k < 3; k++) dd[k] = fwd[k] + right[k] * (xx * t) + up[k] * (yy * ty_scale);
+      cmin = fminf(cmin, dot3(dd, ax) / sqrtf(dot3(dd, dd)));
+    }
+    const float half = acosf(fminf(fmaxf(cmin, -1.0f), 1.0f));
+    bool hit = false;
+    if (lane < ns) {
+      const float* s = S + lane * RT_SW;
+      const float v[3] = {s[0] - o[0], s[1] - o[1], s[2] - o[2]};
+      const float r = s[15], dist2 = dot3(v, v), dv = dot3(v, fwd);
+      if (dv - r <= cam.far_plane && dv + r >= cam.near_plane) {
+        if (dist2 <= r * r) {
+          hit = true;
+        } else {
+          const float dist = sqrtf(dist2);
+          const float ang = acosf(fminf(fmaxf(dot3(v, ax) / dist, -1.0f), 1.0f));
+          hit = ang <= half + asinf(fminf(r / dist, 1.0f)) + 1e-3f;
+        }
+      }
+    }
+    cand = __ballot(hit);
+  }
+
+  const float px = 2.0f * ((float)col + 0.5f) * iW - 1.0f, py = 1.0f - 2.0f * ((float)rowp + 0.5f) * iH;
+  float d[3];
+  for (int k = 0; k < 3; k++) d[k] = fwd[k] + right[k] * (px * t) + up[k] * (py * ty_scale);
+  const float nearp = cam.near_plane, farp = cam.far_plane;
+
+  float best = INFINITY, nw[3] = {0.0f, 0.0f, 1.0f};
+  int best_i = -1;
+  while (cand) {
+    const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(cand));
+    cand &= cand - 1;
+    const float* s = S + i * RT_SW;
+    const float rel[3] = {o[0] - s[0], o[1] - s[1], o[2] - s[2]};
+    float ol[3], dl[3];
+    for (int k = 0; k < 3; k++) {     // into the shape frame: R^T (.)
+      ol[k] = s[3 + k] * rel[0] + s[6 + k] * rel[1] + s[9 + k] * rel[2];
+      dl[k] = s[3 + k] * d[0] + s[6 + k] * d[1] + s[9 + k] * d[2];
+    }
+    const int kind = SI[i * 3];
+    float nl[3] = {0.0f, 0.0f, 1.0f}, sh;
+    if (kind == SHF_RENDER_BOX) {
+      const float h[3] = {s[12], s[13], s[14]};
+      sh = hit_box(ol, dl, h, nl);
+    } else if (kind == SHF_RENDER_SPHERE) {
+      sh = hit_sphere(ol, dl, s[12], nl);
+    } else if (kind == SHF_RENDER_CAPSULE) {
+      sh = hit_capsule(ol, dl, s[12], s[13], nl);
+    } else {
+      const int p = __builtin_amdgcn_readfirstlane(min(max(SI[i * 3 + 1], 0), SHF_RENDER_MAX_POLYS - 1));
+      sh = hit_poly(&scene->poly[p], ol, dl, nl);
+    }
+    if (sh >= nearp && sh <= farp && sh < best) {
+      best = sh;
+      best_i = i;
+      for (int k = 0; k < 3; k++) nw[k] = s[3 + 3 * k] * nl[0] + s[4 + 3 * k] * nl[1] + s[5 + 3 * k] * nl[2];
+    }
+  }
+
+  int sid = 0;
+  float base[3] = {0.0f, 0.0f, 0.0f};
+  bool ground_hit = false;
+  if (scene->ground) {
+    const float lim = fminf(best, farp);
+    float nn[3], sg = INFINITY;
+    if (T.rows == 0) {
+      if (d[2] < 0.0f) {
+        const float s = -o[2] / d[2];
+        if (s >= nearp && s <= lim) { sg = s; nn[0] = 0.0f; nn[1] = 0.0f; nn[2] = 1.0f; }
+      }
+    } else {
+      sg = hit_heightfield(T, hsamp, scene->hf_zmin, scene->hf_zmax, o, d, nearp, lim, nn);
+    }
+    if (sg < best) {
+      best = sg;
+      ground_hit = true;
+      nw[0] = nn[0]; nw[1] = nn[1]; nw[2] = nn[2];
+      base[0] = scene->ground_color[0]; base[1] = scene->ground_color[1]; base[2] = scene->ground_color[2];
+    }
+  }
+  if (!ground_hit && best_i >= 0) {
+    const float* s = S + best_i * RT_SW;
+    base[0] = s[16]; base[1] = s[17]; base[2] = s[18];
+    sid = SI[best_i * 3 + 2];
+  }
+
+  if (col >= W || rowp >= Hh) return;
+  const size_t px_i = ((size_t)env * Hh + rowp) * W + col;
+  const bool any = best < INFINITY;
+  if (depth) {
+    const float dv = any ? best : INFINITY;
+    depth[px_i] = cam.depth_negative ? -dv : dv;
+  }
+  if (seg_out) seg_out[px_i] = sid;
+  if (rgba) {
+    uint32_t pix;
+    if (any) {
+      const float il = 1.0f / sqrtf(dot3(nw, nw));
+      const float nl = (nw[0] * SHF_RENDER_LIGHT_X + nw[1] * SHF_RENDER_LIGHT_Y + nw[2] * SHF_RENDER_LIGHT_Z) * il;
+      const float lam = SHF_RENDER_AMBIENT + SHF_RENDER_DIFFUSE * fmaxf(nl, 0.0f);
+      pix = shade_u8(base[0], lam) | (shade_u8(base[1], lam) << 8) | (shade_u8(base[2], lam) << 16) | (255u << 24);
+    } else {
+      pix = (uint32_t)SHF_RENDER_BG_R | ((uint32_t)SHF_RENDER_BG_G << 8) | ((uint32_t)SHF_RENDER_BG_B << 16) | (255u << 24);
+    }
+    rgba[px_i] = pix;
+  }
+}
+
+extern "C" int shf_render_cameras(const ShfRenderScene* scene_dev, const ShfTerrain* terrain, const int16_t* height_samples_dev,
+                                  const ShfCamera* camera, int32_t num_envs, const float* body_state, const float* cam_pose,
+                                  const int32_t* seg_ids, const float* colors, float* depth_or_null, int32_t* seg_or_null,
+                                  uint8_t* rgba_or_null, void* stream) {
+  if (!scene_dev || !terrain || !camera) return shf_set_error("shf_render_cameras: null scene, terrain or camera");
+  const ShfCamera c = *camera;
+  if (c.width <= 0 || c.height <= 0 || c.width > 16384 || c.height > 16384)
+    return shf_set_error("shf_render_cameras: width and height must be in 1..16384");
+  if (!(c.horizontal_fov > 0.0f && c.horizontal_fov < 180.0f))
+    return shf_set_error("shf_render_cameras: horizontal_fov must be in (0, 180) degrees");
+  if (!(c.near_plane > 0.0f && c.far_plane > c.near_plane))
+    return shf_set_error("shf_render_cameras: need 0 < near_plane < far_plane");
+  if (terrain->warped) return shf_set_error("shf_render_cameras: a warped trimesh terrain cannot be rendered (height fields and planes only)");
+  if (terrain->rows != 0 && (terrain->rows < 2 || terrain->cols < 2 || !height_samples_dev))
+    return shf_set_error("shf_render_cameras: a height field needs at least 2 x 2 samples on the device");
+  if (num_envs < 0) return shf_set_error("shf_render_cameras: num_envs < 0");
+  if (num_envs == 0 || (!depth_or_null && !seg_or_null && !rgba_or_null)) return 0;
+  if (!body_state || !cam_pose || !seg_ids || !colors) return shf_set_error("shf_render_cameras: null input tensor");
+  const int tiles_x = (c.width + RT_TILE - 1) / RT_TILE, tiles = tiles_x * ((c.height + RT_TILE - 1) / RT_TILE);
+  if ((int64_t)tiles * num_envs > 0x7fffffffLL) return shf_set_error("shf_render_cameras: too many envs x tiles for one launch");
+  hipLaunchKernelGGL(k_render_cameras, dim3((unsigned)(tiles * num_envs)), dim3(RT_THREADS), 0, (hipStream_t)stream, scene_dev,
+                     *terrain, height_samples_dev, c, tiles_x, tiles, body_state, cam_pose, seg_ids, colors, depth_or_null,
+                     seg_or_null, reinterpret_cast<uint32_t*>(rgba_or_null));
+  return hipGetLastError() == hipSuccess ? 0 : shf_set_error("shf_render_cameras: launch failed");
+}

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from shifu_amd.isaacgym import gymapi, gymtorch, gymutil
-from shifu_amd.units import Actor, Robot, Unit
+from shifu_amd.units import Actor, CameraSensor, Robot, Unit
 from shifu_amd.utils.terrain import Terrain
 from shifu_amd.utils.torch_utils import free_tensor_attrs
 
@@ -124,8 +124,18 @@ class IsaacGymEnv:
         self._refresh_all()
 
     def refresh_sensors(self):
+        # the reference's order for camera sensors (shifu/gym/isaac_gym.py:159-170): render, then refresh -- here each
+        # camera sensor renders its own camera group (one launch), then fills its buffers for all envs at once
         for sensor in self.sensors:
-            sensor.refresh()
+            if isinstance(sensor, CameraSensor):
+                self.gym.fetch_results(self.sim, True)
+                self.gym.step_graphics(self.sim)
+                sensor.render_images()
+                self.gym.start_access_image_tensors(self.sim)
+                sensor.refresh()
+                self.gym.end_access_image_tensors(self.sim)
+            else:
+                sensor.refresh()
 
     def reset_idx(self, env_ids: Union[list, torch.Tensor], actors=None):
         if len(env_ids) == 0:

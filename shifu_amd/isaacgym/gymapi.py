@@ -5,8 +5,8 @@ This is a naming facade, not a CUDA shim: `acquire_gym()` returns a `Gym` whose 
 methods used by the reference (103 call sites; shifu/gym/isaac_gym.py,
 shifu/units/*.py, examples/*) record the scene while envs are created and, from
 `prepare_sim` on, forward to the C ABI of include/shifu_amd.h through
-shifu_amd.backend.Sim.  Graphics / viewer / camera calls are accepted and ignored
-(no renderer on the MI355X path: SURVEY.md section 2 rows 7, 13).
+shifu_amd.backend.Sim.  Viewer calls are accepted and ignored; camera sensors are rendered by a HIP ray
+caster against the collision shapes (shifu_amd/render.py, DESIGN.md "Camera sensors").
 
 Semantics kept from Isaac Gym:
   * state tensors are sim-owned, pointer-stable, viewed once (`acquire_*`), updated
@@ -36,6 +36,7 @@ FROM_ASSET, COMPUTE_PER_VERTEX, COMPUTE_PER_FACE = 0, 1, 2
 DOMAIN_ENV, DOMAIN_SIM, DOMAIN_ACTOR = 0, 1, 2
 MESH_NONE, MESH_COLLISION, MESH_VISUAL, MESH_VISUAL_AND_COLLISION = 0, 1, 2, 3
 IMAGE_COLOR, IMAGE_DEPTH, IMAGE_SEGMENTATION, IMAGE_OPTICAL_FLOW = 0, 1, 2, 3
+FOLLOW_POSITION, FOLLOW_TRANSFORM = 0, 1
 KEY_ESCAPE, KEY_V = 256, 86
 ENV_SPACE, LOCAL_SPACE, GLOBAL_SPACE = 0, 1, 2
 
@@ -215,6 +216,20 @@ class Env:
     def __init__(self, sim, index):
         self.sim, self.index = sim, index
         self.actors: List[_Actor] = []
+        self.cameras: List["_Camera"] = []
+        self.seg_ids: Dict[tuple, int] = {}        # (actor handle, body index) -> segmentation id
+        self.colors: Dict[tuple, tuple] = {}       # (actor handle, body index) -> RGB in [0, 1]
+
+
+class _Camera:
+    """One create_camera_sensor: its properties and pose (pos, quat xyzw) in the frame of the state tensors, or a body it
+    follows (body row within the env, local pos, local quat)."""
+
+    def __init__(self, props: "CameraProperties"):
+        self.props = copy.deepcopy(props)
+        self.pos = np.zeros(3)
+        self.quat = np.array([0.0, 0.0, 0.0, 1.0])
+        self.attach = None
 
 
 class _TensorHandle:
@@ -235,6 +250,9 @@ class SimHandle:
         self.actors_per_env = 0
         self.num_actors = 0
         self.jacobian = None
+        self.camera_groups: List[dict] = []   # after prepare_sim: one per camera handle (one camera per env each)
+        self.renderer = None
+        self.body_fresh = False               # body_state refreshed since the last simulate (render_all_camera_sensors)
 
 
 class Gym:
@@ -406,8 +424,21 @@ class Gym:
         return True
     def set_actor_dof_properties(self, env, actor_handle, props):
         env.actors[actor_handle].dof_props = props
-    def set_rigid_body_segmentation_id(self, *a, **k): pass
-    def set_rigid_body_color(self, *a, **k): pass
+    def set_rigid_body_segmentation_id(self, env: Env, actor_handle, rigid_body_index, segmentation_id):
+        env.seg_ids[(int(actor_handle), int(rigid_body_index))] = int(segmentation_id)
+        self._camera_table_update(env, actor_handle, rigid_body_index)
+
+    def set_rigid_body_color(self, env: Env, actor_handle, rigid_body_index, mesh_type, color):
+        rgb = (color.x, color.y, color.z) if isinstance(color, Vec3) else tuple(color)
+        env.colors[(int(actor_handle), int(rigid_body_index))] = tuple(float(c) for c in rgb)
+        self._camera_table_update(env, actor_handle, rigid_body_index)
+
+    def get_rigid_body_segmentation_id(self, env: Env, actor_handle, rigid_body_index):
+        return env.seg_ids.get((int(actor_handle), int(rigid_body_index)), 0)
+
+    def get_rigid_body_color(self, env: Env, actor_handle, rigid_body_index, mesh_type=MESH_VISUAL):
+        from ..render import DEFAULT_BODY_COLOR
+        return Vec3(*env.colors.get((int(actor_handle), int(rigid_body_index)), DEFAULT_BODY_COLOR))
 
     # ---- prepare ---------------------------------------------------------------
     def prepare_sim(self, sim: SimHandle):
@@ -522,6 +553,8 @@ class Gym:
             one = np.ones(env0.actors[0].asset.num_bodies, np.float32)
             be.set_body_mass_scale(np.stack([one if env.actors[0].mass_scale is None else env.actors[0].mass_scale for env in sim.envs]))
         sim.backend = be
+        if any(env.cameras for env in sim.envs):
+            self._prepare_cameras(sim)
         return True
 
     # ---- tensors ---------------------------------------------------------------
@@ -535,7 +568,9 @@ class Gym:
 
     def refresh_dof_state_tensor(self, sim): sim.backend.refresh(_abi.REFRESH_DOF)
     def refresh_actor_root_state_tensor(self, sim): sim.backend.refresh(_abi.REFRESH_ROOT)
-    def refresh_rigid_body_state_tensor(self, sim): sim.backend.refresh(_abi.REFRESH_BODY)
+    def refresh_rigid_body_state_tensor(self, sim):
+        sim.backend.refresh(_abi.REFRESH_BODY)
+        sim.body_fresh = True
     def refresh_net_contact_force_tensor(self, sim): sim.backend.refresh(_abi.REFRESH_CONTACT)
     def refresh_jacobian_tensors(self, sim): sim.backend.refresh(_abi.REFRESH_JACOBIAN)
     def refresh_force_sensor_tensor(self, sim): pass
@@ -544,10 +579,13 @@ class Gym:
         """Not an Isaac Gym call: root, rigid-body, dof, Jacobian and net-contact-force tensors refreshed by ONE backend
         call (shifu's refresh_state issues the six refresh_* calls back to back, shifu/gym/isaac_gym.py:145-154)."""
         sim.backend.refresh(_abi.REFRESH_ALL)
+        sim.body_fresh = True
     def refresh_mass_matrix_tensors(self, sim): pass
 
     # ---- stepping --------------------------------------------------------------
-    def simulate(self, sim): sim.backend.step()
+    def simulate(self, sim):
+        sim.body_fresh = False
+        sim.backend.step()
     def fetch_results(self, sim, wait=True): pass
 
     def set_dof_actuation_force_tensor(self, sim, t): sim.backend.set_dof_command(_abi.T_EFFORT, t); return True
@@ -580,7 +618,185 @@ class Gym:
             sim.backend.destroy()
             sim.backend = None
 
-    # ---- graphics: accepted and ignored (no renderer on this path) ----------------
+    # ---- camera sensors (shifu_amd/render.py: one ray per pixel against the collision shapes) ---------------
+    _warned_visual = False
+
+    def create_camera_sensor(self, env: Env, props: CameraProperties):
+        """Registered before prepare_sim; the handle is the camera's index within its env.  Cameras with one handle form a
+        group -- one per env, one set of properties -- rendered by one launch."""
+        sim = env.sim
+        if sim.backend is not None:
+            raise NotImplementedError("create_camera_sensor: cameras must be created before prepare_sim (the render scene is "
+                                      "built there)")
+        self._check_renderable_terrain(sim)
+        if not props.use_collision_geometry and not Gym._warned_visual:
+            Gym._warned_visual = True
+            import warnings
+            warnings.warn("shifu_amd: camera sensors draw the collision geometry (visual meshes are not loaded); "
+                          "CameraProperties.use_collision_geometry = False is treated as True", stacklevel=2)
+        env.cameras.append(_Camera(props))
+        return len(env.cameras) - 1
+
+    @staticmethod
+    def _check_renderable_terrain(sim):
+        t = sim.terrain
+        if t is not None and t[0] == "heightfield" and len(t) > 6 and t[6] is not None:
+            raise NotImplementedError("camera sensors cannot render a warped trimesh terrain (the triangle mesh "
+                                      "convert_heightfield_to_trimesh makes, ShfTerrain.warped): height fields and planes only")
+
+    def set_camera_location(self, camera_handle, env: Env, position, target):
+        from ..render import lookat_quat
+        cam = env.cameras[camera_handle]
+        cam.pos = np.array(tuple(position), float)
+        cam.quat = lookat_quat(cam.pos, tuple(target))
+        cam.attach = None
+        self._camera_pose_update(env, camera_handle)
+
+    def set_camera_transform(self, camera_handle, env: Env, transform: Transform):
+        cam = env.cameras[camera_handle]
+        cam.pos = np.array(tuple(transform.p), float)
+        q = np.array(tuple(transform.r), float)
+        cam.quat = q / np.linalg.norm(q)
+        cam.attach = None
+        self._camera_pose_update(env, camera_handle)
+
+    def attach_camera_to_body(self, camera_handle, env: Env, body_handle, transform: Transform, follow_mode=FOLLOW_TRANSFORM):
+        """body_handle: the body's row within the env's rigid-body states (articulation bodies, then one per box actor);
+        the camera pose is body pose o transform at every render."""
+        if follow_mode != FOLLOW_TRANSFORM:
+            raise NotImplementedError("attach_camera_to_body: FOLLOW_TRANSFORM only")
+        if env.sim.backend is not None:
+            raise NotImplementedError("attach_camera_to_body: before prepare_sim")
+        q = np.array(tuple(transform.r), float)
+        env.cameras[camera_handle].attach = (int(body_handle), np.array(tuple(transform.p), float), q / np.linalg.norm(q))
+
+    def get_camera_view_matrix(self, sim, env: Env, camera_handle):
+        from ..render import view_matrix
+        cam = env.cameras[camera_handle]
+        pos, quat = cam.pos, cam.quat
+        if cam.attach is not None and sim.backend is not None:
+            pose = self._attached_poses(sim, self._group_of(sim, camera_handle))[env.index].cpu().numpy()
+            pos, quat = pose[:3], pose[3:]
+        return view_matrix(pos, quat).astype(np.float32)
+
+    def get_camera_proj_matrix(self, sim, env: Env, camera_handle):
+        from ..render import proj_matrix
+        p = env.cameras[camera_handle].props
+        return proj_matrix(p.width, p.height, p.horizontal_fov, p.near_plane, p.far_plane).astype(np.float32)
+
+    def _prepare_cameras(self, sim):
+        import torch
+        from ..render import DEFAULT_BODY_COLOR, Renderer, build_scene, camera_struct
+        be = sim.backend
+        if be.terrain.warped:
+            raise NotImplementedError("camera sensors cannot render a warped trimesh terrain (ShfTerrain.warped): height "
+                                      "fields and planes only")
+        env0 = sim.envs[0]
+        model = env0.actors[0].asset.model
+        boxes = [a.asset.box_dim for a in env0.actors[1:]]
+        nb = model.blob.nb
+        B = nb + len(boxes)
+        hs = getattr(be, "height_samples", None) if be.terrain.rows > 0 else None
+        scene = build_scene(model.render_shapes, nb, boxes, height_samples=hs, vscale=be.terrain.vscale)
+        sim.renderer = Renderer(scene, be.terrain, be._heights if be.terrain.rows > 0 else None, be.device)
+        n = len(sim.envs)
+        row = lambda a, b: b if a == 0 else nb + a - 1
+        seg = torch.zeros(n, B, dtype=torch.int32)
+        col = torch.tensor(DEFAULT_BODY_COLOR, dtype=torch.float32).repeat(n, B, 1)
+        for e, env in enumerate(sim.envs):
+            for (a, b), v in env.seg_ids.items():
+                seg[e, row(a, b)] = v
+            for (a, b), v in env.colors.items():
+                col[e, row(a, b)] = torch.tensor(v)
+        sim.cam_seg, sim.cam_color = seg.to(be.device), col.to(be.device)
+        ncam = len(env0.cameras)
+        sim.camera_groups = []
+        for k in range(ncam):
+            cams = [env.cameras[k] if k < len(env.cameras) else None for env in sim.envs]
+            key = lambda c: (c.props.width, c.props.height, float(c.props.horizontal_fov), float(c.props.near_plane),
+                             float(c.props.far_plane), c.attach is None)
+            if any(c is None or key(c) != key(cams[0]) for c in cams) or any(len(env.cameras) != ncam for env in sim.envs):
+                raise NotImplementedError("camera sensors: every env needs the same cameras (camera handle k: one per env, "
+                                          "same width, height, fov, near, far, and all attached or none)")
+            p = cams[0].props
+            pose = torch.tensor(np.array([np.concatenate([c.pos, c.quat]) for c in cams]), dtype=torch.float32)
+            g = dict(camera=camera_struct(p.width, p.height, p.horizontal_fov, p.near_plane, p.far_plane, depth_negative=True),
+                     pose=pose.to(be.device), width=p.width, height=p.height,
+                     depth=torch.full((n, p.height, p.width), -float("inf"), dtype=torch.float32, device=be.device),
+                     seg=torch.zeros(n, p.height, p.width, dtype=torch.int32, device=be.device),
+                     rgba=torch.zeros(n, p.height, p.width, 4, dtype=torch.uint8, device=be.device), attach=None)
+            if cams[0].attach is not None:
+                g["attach"] = (torch.tensor([e * B + c.attach[0] for e, c in enumerate(cams)], dtype=torch.long, device=be.device),
+                               torch.tensor(np.array([c.attach[1] for c in cams]), dtype=torch.float32, device=be.device),
+                               torch.tensor(np.array([c.attach[2] for c in cams]), dtype=torch.float32, device=be.device))
+            sim.camera_groups.append(g)
+
+    def _group_of(self, sim, camera_handle):
+        return sim.camera_groups[camera_handle]
+
+    def _attached_poses(self, sim, g):
+        """(N, 7) poses of a group attached to bodies: body pose o local transform, from the body-state tensor."""
+        import torch
+        from .torch_utils import quat_apply, quat_mul
+        rows, lp, lq = g["attach"]
+        bs = sim.backend.tensors[_abi.T_BODY_STATE].index_select(0, rows)
+        return torch.cat([bs[:, :3] + quat_apply(bs[:, 3:7], lp), quat_mul(bs[:, 3:7], lq)], dim=1)
+
+    def _camera_pose_update(self, env: Env, camera_handle):
+        sim = env.sim
+        if sim.backend is None or not sim.camera_groups:
+            return
+        import torch
+        cam = env.cameras[camera_handle]
+        row = np.concatenate([cam.pos, cam.quat]).astype(np.float32)
+        sim.camera_groups[camera_handle]["pose"][env.index].copy_(torch.from_numpy(row))
+
+    def _camera_table_update(self, env: Env, actor_handle, body):
+        sim = env.sim
+        if sim.backend is None or sim.renderer is None:
+            return
+        import torch
+        from ..render import DEFAULT_BODY_COLOR
+        r = int(body) if int(actor_handle) == 0 else sim.robot_asset.num_bodies + int(actor_handle) - 1
+        sim.cam_seg[env.index, r] = env.seg_ids.get((int(actor_handle), int(body)), 0)
+        sim.cam_color[env.index, r] = torch.tensor(env.colors.get((int(actor_handle), int(body)), DEFAULT_BODY_COLOR))
+
+    def render_camera_group(self, sim, camera_handle):
+        """Not an Isaac Gym call: renders one camera group (camera handle k of every env) -- one launch."""
+        if sim.renderer is None:
+            return
+        if not sim.body_fresh:
+            self.refresh_rigid_body_state_tensor(sim)
+        g = sim.camera_groups[camera_handle]
+        pose = g["pose"] if g["attach"] is None else self._attached_poses(sim, g).contiguous()
+        sim.renderer.render(sim.backend.tensors[_abi.T_BODY_STATE], pose, sim.cam_seg, sim.cam_color, g["camera"],
+                            depth=g["depth"], seg_out=g["seg"], rgba=g["rgba"])
+
+    def render_all_camera_sensors(self, sim):
+        """One launch per camera group, on the state of the last simulate (the rigid-body states are refreshed first when
+        they have not been since)."""
+        for k in range(len(sim.camera_groups)):
+            self.render_camera_group(sim, k)
+
+    def get_camera_image_gpu_tensor(self, sim, env: Env, camera_handle, image_type):
+        """Zero-copy view of row env of the group's image: IMAGE_COLOR (H, W, 4) u8 RGBA, IMAGE_DEPTH (H, W) f32 (minus the
+        view-space depth, -inf where nothing is hit), IMAGE_SEGMENTATION (H, W) int32."""
+        if image_type == IMAGE_OPTICAL_FLOW:
+            raise NotImplementedError("IMAGE_OPTICAL_FLOW is not rendered by this backend (depth, segmentation and color are)")
+        if not sim.camera_groups:
+            raise RuntimeError("get_camera_image_gpu_tensor: no camera sensors (create them before prepare_sim)")
+        g = sim.camera_groups[camera_handle]
+        key = {IMAGE_COLOR: "rgba", IMAGE_DEPTH: "depth", IMAGE_SEGMENTATION: "seg"}.get(image_type)
+        if key is None:
+            raise ValueError(f"get_camera_image_gpu_tensor: unknown image type {image_type}")
+        return _TensorHandle(g[key][env.index])
+
+    def camera_group_tensors(self, sim, camera_handle):
+        """Not an Isaac Gym call: the group's (N, H, W[, 4]) images -- dict(rgba=, depth=, seg=) -- for all envs at once."""
+        g = sim.camera_groups[camera_handle]
+        return dict(rgba=g["rgba"], depth=g["depth"], seg=g["seg"])
+
+    # ---- graphics: accepted and ignored (no viewer on this path) ----------------
     def create_viewer(self, *a, **k): return None
     def subscribe_viewer_keyboard_event(self, *a, **k): pass
     def viewer_camera_look_at(self, *a, **k): pass
@@ -591,12 +807,8 @@ class Gym:
     def sync_frame_time(self, sim): pass
     def poll_viewer_events(self, viewer): pass
     def set_light_parameters(self, *a, **k): pass
-    def render_all_camera_sensors(self, sim): pass
     def start_access_image_tensors(self, sim): pass
     def end_access_image_tensors(self, sim): pass
-    def create_camera_sensor(self, *a, **k):
-        raise NotImplementedError("rasterised camera sensors are out of scope on the MI355X path (SURVEY.md row 7)")
-    get_camera_image_gpu_tensor = set_camera_location = set_camera_transform = create_camera_sensor
 
 
 _GYM = None

@@ -99,12 +99,26 @@ class _Joint:
 
 
 @dataclasses.dataclass
+class RenderShape:
+    """One collision shape as camera sensors draw it (shifu_amd/render.py): fixed to reported body `body` at (pos, rot) in
+    that body's frame.  kind "box" (size = full extents), "sphere" (size = [radius]), "capsule" (size = [radius, length]
+    along the shape's z) or "hull" (poly = reduce_hull()'s polytope in the shape frame: what the narrow phase collides)."""
+    body: int
+    kind: str
+    pos: np.ndarray
+    rot: np.ndarray
+    size: np.ndarray
+    poly: Optional[dict] = None
+
+
+@dataclasses.dataclass
 class CompiledModel:
     blob: _abi.ShfModel
     body_names: List[str]
     dof_names: List[str]
     total_mass: float
     hulls: Optional["_abi.ShfHullSet"] = None     # the articulation's convex hulls (blob.nhull of them), for Sim.set_hulls
+    render_shapes: List[RenderShape] = dataclasses.field(default_factory=list)   # every collision shape, for camera sensors
 
     @property
     def rigid_body_dict(self) -> Dict[str, int]:
@@ -618,15 +632,19 @@ def compile_urdf(path: str, *, fix_base_link: bool = False, disable_gravity: boo
     capsules: List[Tuple[int, np.ndarray, np.ndarray, float]] = []
     aboxes: List[Tuple[int, np.ndarray, np.ndarray, np.ndarray]] = []   # (body, centre, rot, half extents) in the body frame
     link_frame: Dict[str, Tuple[int, np.ndarray, np.ndarray]] = {}  # urdf link -> (body, p, R) in body frame
+    render_shapes: List[RenderShape] = []
 
     def absorb(body: int, link: _Link, p: np.ndarray, R: np.ndarray):
         inert[body] = inert[body].merged(link.inertial.transformed(p, R))
         link_frame[link.name] = (body, p.copy(), R.copy())
         for s in link.shapes:
+            # what camera sensors draw: the shape itself, a mesh collider as the polytope the narrow phase collides
+            poly = reduce_hull(s.verts) if s.kind == "hull" else None
+            render_shapes.append(RenderShape(body, s.kind, p + R @ s.pos, R @ s.rot, np.asarray(s.size, float).copy(), poly))
             if s.kind == "hull" and hull_contacts:
                 # the convex narrow phase takes this shape against the box actors (no sample points: they would meet the boxes a
                 # second time as family A; a fixed-base arm has no ground to touch)
-                hull_recs.append((body, reduce_hull(s.verts), p + R @ s.pos, R @ s.rot))
+                hull_recs.append((body, poly, p + R @ s.pos, R @ s.rot))
                 for ca, cb, rad in _shape_capsules(s):
                     capsules.append((body, p + R @ ca, p + R @ cb, rad))
                 continue
@@ -817,6 +835,7 @@ def compile_urdf(path: str, *, fix_base_link: bool = False, disable_gravity: boo
         body, p, R = link_frame[lname]
         q = p + R @ np.asarray(xyz, dtype=float)
         seg = R @ (np.asarray(rec[2], dtype=float) - np.asarray(xyz, dtype=float)) if len(rec) == 4 else np.zeros(3)
+        render_shapes.append(_rounded_render_shape(body, q, seg, float(rad)))
         for part in ((0, 1) if np.any(seg != 0.0) else (0,)):
             recs.append((body, q, seg, rad, part))
     assert len(recs) <= _abi.MAX_SPHERES, f"{len(recs)} rounded-shape records > SHF_MAX_SPHERES"
@@ -905,7 +924,18 @@ def compile_urdf(path: str, *, fix_base_link: bool = False, disable_gravity: boo
         hulls.nhull = m.nhull = len(hull_recs)
         for j, (b, h, hp, hR) in enumerate(sorted(hull_recs, key=lambda t: t[0])):
             hulls.hull[j] = hull_record(h, b, hp, hR)
-    return CompiledModel(m, names, dof_names, float(sum(t.mass for t in merged)), hulls)
+    return CompiledModel(m, names, dof_names, float(sum(t.mass for t in merged)), hulls, render_shapes)
+
+
+def _rounded_render_shape(body: int, a: np.ndarray, seg: np.ndarray, rad: float) -> RenderShape:
+    """extra_spheres record (sphere at a, or capsule from a to a + seg, body frame) as a RenderShape."""
+    L = float(np.linalg.norm(seg))
+    if L == 0.0:
+        return RenderShape(body, "sphere", np.asarray(a, float).copy(), np.eye(3), np.array([rad]))
+    z = seg / L
+    x = np.cross(z, [1.0, 0.0, 0.0] if abs(z[0]) < 0.9 else [0.0, 1.0, 0.0])
+    x /= np.linalg.norm(x)
+    return RenderShape(body, "capsule", a + 0.5 * seg, np.stack([x, np.cross(z, x), z], axis=1), np.array([rad, L]))
 
 
 def asset_path(name: str) -> str:

@@ -1,0 +1,235 @@
+"""Camera sensors: the scene description behind include/shifu_amd.h shf_render_cameras (csrc/shf_render.hip).
+
+A render scene holds every collision shape of the articulation (CompiledModel.render_shapes) and of the box actors in the
+frame of the body that moves it, plus the terrain; the kernel casts one ray per pixel against them.  This module also
+owns the conventions the kernel mirrors (DESIGN.md "Camera sensors"):
+
+  * a camera pose (pos, quat xyzw) looks along its local +x with +z up (Isaac Gym's camera transform);
+  * pixel (row r, col c), row 0 at the top, casts  dir = fwd + right x t + up y t H/W,  t = tan(hfov / 2),
+    x = 2 (c + 1/2) / W - 1,  y = 1 - 2 (r + 1/2) / H  -- so the ray parameter is the view-space depth;
+  * view / projection matrices are row-vector 4 x 4 (p_clip = [p, 1] @ view @ proj, the form of the reference's
+    shifu/utils/camera.py), proj[0, 0] = 1 / t, proj[1, 1] = proj[0, 0] W / H;
+  * color = body color x (AMBIENT + DIFFUSE max(0, n . LIGHT)) rounded to u8, alpha 255; background BACKGROUND.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import _abi
+
+AMBIENT, DIFFUSE = _abi.RENDER_AMBIENT, _abi.RENDER_DIFFUSE
+LIGHT = np.array(_abi.RENDER_LIGHT, dtype=np.float64)
+BACKGROUND = tuple(_abi.RENDER_BG)
+DEFAULT_BODY_COLOR = (0.8, 0.8, 0.8)
+DEFAULT_GROUND_COLOR = (0.5, 0.5, 0.5)
+_KINDS = {"box": _abi.RENDER_BOX, "sphere": _abi.RENDER_SPHERE, "capsule": _abi.RENDER_CAPSULE, "hull": _abi.RENDER_POLY}
+
+
+# -- conventions ------------------------------------------------------------------------------------------------------
+def quat_to_mat(q) -> np.ndarray:
+    x, y, z, w = (float(v) for v in q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def mat_to_quat(R) -> np.ndarray:
+    """Unit quaternion (x, y, z, w) of a rotation matrix."""
+    R = np.asarray(R, float)
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr > 0:
+        s = 2.0 * np.sqrt(tr + 1.0)
+        q = [(R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s, 0.25 * s]
+    elif R[0, 0] > R[1, 1] and R[0, 0] > R[2, 2]:
+        s = 2.0 * np.sqrt(1.0 + R[0, 0] - R[1, 1] - R[2, 2])
+        q = [0.25 * s, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s, (R[2, 1] - R[1, 2]) / s]
+    elif R[1, 1] > R[2, 2]:
+        s = 2.0 * np.sqrt(1.0 + R[1, 1] - R[0, 0] - R[2, 2])
+        q = [(R[0, 1] + R[1, 0]) / s, 0.25 * s, (R[1, 2] + R[2, 1]) / s, (R[0, 2] - R[2, 0]) / s]
+    else:
+        s = 2.0 * np.sqrt(1.0 + R[2, 2] - R[0, 0] - R[1, 1])
+        q = [(R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s, (R[1, 0] - R[0, 1]) / s]
+    q = np.asarray(q)
+    return q / np.linalg.norm(q)
+
+
+def camera_basis(quat):
+    """(fwd, right, up) of a camera pose: local +x, -(local +y), local +z."""
+    R = quat_to_mat(quat)
+    return R[:, 0], -R[:, 1], R[:, 2]
+
+
+def lookat_quat(pos, target) -> np.ndarray:
+    """The camera quaternion of set_camera_location(pos, target): looking from pos at target, world +z up."""
+    f = np.asarray(target, float) - np.asarray(pos, float)
+    n = np.linalg.norm(f)
+    if n == 0.0:
+        raise ValueError("camera position and target coincide")
+    f = f / n
+    r = np.cross(f, [0.0, 0.0, 1.0])
+    if np.linalg.norm(r) < 1e-9:               # looking straight up or down: world +x / -x as the image's up
+        r = np.cross(f, [1.0, 0.0, 0.0]) if f[2] < 0 else np.cross([1.0, 0.0, 0.0], f)
+    r = r / np.linalg.norm(r)
+    u = np.cross(r, f)
+    return mat_to_quat(np.stack([f, -r, u], axis=1))
+
+
+def pixel_rays(quat, width: int, height: int, horizontal_fov: float) -> np.ndarray:
+    """(H, W, 3) ray directions (not unit: their component along fwd is 1) of a camera, row 0 at the top."""
+    fwd, right, up = camera_basis(quat)
+    t = np.tan(0.5 * np.deg2rad(horizontal_fov))
+    x = 2.0 * (np.arange(width) + 0.5) / width - 1.0
+    y = 1.0 - 2.0 * (np.arange(height) + 0.5) / height
+    return (fwd[None, None, :] + right[None, None, :] * (x[None, :, None] * t)
+            + up[None, None, :] * (y[:, None, None] * t * height / width))
+
+
+def view_matrix(pos, quat) -> np.ndarray:
+    """Row-vector world -> view matrix: [p, 1] @ V = (right . (p - o), up . (p - o), -fwd . (p - o), 1)."""
+    fwd, right, up = camera_basis(quat)
+    o = np.asarray(pos, float)
+    V = np.eye(4)
+    V[:3, 0], V[:3, 1], V[:3, 2] = right, up, -fwd
+    V[3, :3] = [-right @ o, -up @ o, fwd @ o]
+    return V
+
+
+def proj_matrix(width: int, height: int, horizontal_fov: float, near: float, far: float) -> np.ndarray:
+    """Row-vector perspective projection: ndc x = x_view / (t (-z_view)), ndc y = y_view W / (t H (-z_view)); the z row maps
+    [near, far] to [-1, 1] (OpenGL)."""
+    t = np.tan(0.5 * np.deg2rad(horizontal_fov))
+    P = np.zeros((4, 4))
+    P[0, 0] = 1.0 / t
+    P[1, 1] = P[0, 0] * width / height
+    P[2, 2] = -(far + near) / (far - near)
+    P[2, 3] = -1.0
+    P[3, 2] = -2.0 * far * near / (far - near)
+    return P
+
+
+def shade(color, normal) -> np.ndarray:
+    """u8 RGB of a surface of `color` ([0, 1]) with unit outward normal `normal` (broadcasts over leading axes)."""
+    lam = AMBIENT + DIFFUSE * np.maximum(np.sum(np.asarray(normal, float) * LIGHT, axis=-1), 0.0)
+    return np.floor(np.clip(np.asarray(color, float) * lam[..., None], 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+
+
+# -- scene --------------------------------------------------------------------------------------------------------------
+def _fill_shape(rec, body: int, kind: str, pos, rot, param, radius: float, poly: int = -1):
+    rec.body, rec.kind, rec.poly = int(body), _KINDS[kind], int(poly)
+    rec.pos[:] = [float(v) for v in pos]
+    rec.rot[:] = [float(v) for v in np.asarray(rot, float).reshape(-1)]
+    p = list(param) + [0.0] * (3 - len(param))
+    rec.param[:] = [float(v) for v in p[:3]]
+    rec.radius = float(radius)
+
+
+def build_scene(render_shapes: Sequence, nb: int, boxes: Sequence = (), ground: bool = True,
+                ground_color=DEFAULT_GROUND_COLOR, height_samples: Optional[np.ndarray] = None,
+                vscale: float = 1.0) -> "_abi.ShfRenderScene":
+    """ShfRenderScene of an articulation's render shapes (model.RenderShape, bodies 0..nb-1) and box actors `boxes` (full
+    extents (x, y, z) each; box k is body row nb + k, in its own frame): nb + len(boxes) body_state rows per env.
+    height_samples / vscale: the height field's bounding box in z."""
+    sc = _abi.ShfRenderScene()
+    n_shapes = len(render_shapes) + len(boxes)
+    if n_shapes > _abi.RENDER_MAX_SHAPES:
+        raise ValueError(f"{n_shapes} shapes > SHF_RENDER_MAX_SHAPES = {_abi.RENDER_MAX_SHAPES}")
+    if any(not 0 <= int(s.body) < nb for s in render_shapes):
+        raise ValueError("render shape on a body outside 0..nb-1")
+    k = npoly = 0
+    for s in render_shapes:
+        rec = sc.shape[k]
+        size = np.asarray(s.size, float)
+        if s.kind == "box":
+            h = 0.5 * size
+            _fill_shape(rec, s.body, "box", s.pos, s.rot, h, np.linalg.norm(h))
+        elif s.kind == "sphere":
+            _fill_shape(rec, s.body, "sphere", s.pos, s.rot, [size[0]], size[0])
+        elif s.kind == "capsule":
+            r, hl = float(size[0]), 0.5 * float(size[1])
+            _fill_shape(rec, s.body, "capsule", s.pos, s.rot, [r, hl], r + hl)
+        elif s.kind == "hull":
+            if npoly >= _abi.RENDER_MAX_POLYS:
+                raise ValueError(f"more than SHF_RENDER_MAX_POLYS = {_abi.RENDER_MAX_POLYS} convex polytopes")
+            v, planes = np.asarray(s.poly["verts"], float), np.asarray(s.poly["planes"], float)
+            if len(planes) > _abi.RENDER_POLY_MAX_FACES:
+                raise ValueError(f"polytope with {len(planes)} faces > SHF_RENDER_POLY_MAX_FACES")
+            c = v.mean(0)                        # re-centred: the bounding sphere is taken about the vertex centroid
+            P = sc.poly[npoly]
+            P.nf = len(planes)
+            for f, pl in enumerate(planes):
+                P.plane[f][:] = [float(pl[0]), float(pl[1]), float(pl[2]), float(pl[3] - pl[:3] @ c)]
+            rot = np.asarray(s.rot, float)
+            _fill_shape(rec, s.body, "hull", np.asarray(s.pos, float) + rot @ c, rot, [], np.linalg.norm(v - c, axis=1).max(), npoly)
+            npoly += 1
+        else:
+            raise ValueError(f"render shape kind {s.kind!r}")
+        k += 1
+    for j, dim in enumerate(boxes):
+        h = 0.5 * np.asarray(dim, float)
+        _fill_shape(sc.shape[k], nb + j, "box", np.zeros(3), np.eye(3), h, np.linalg.norm(h))
+        k += 1
+    sc.nshapes, sc.npolys = k, npoly
+    sc.num_bodies = int(nb) + len(boxes)
+    sc.ground = int(bool(ground))
+    sc.ground_color[:] = [float(v) for v in ground_color]
+    if height_samples is not None and np.asarray(height_samples).size:
+        z = np.asarray(height_samples, np.float64) * float(vscale)
+        sc.hf_zmin, sc.hf_zmax = float(z.min()), float(z.max())
+    return sc
+
+
+def camera_struct(width: int, height: int, horizontal_fov: float, near: float, far: float,
+                  depth_negative: bool = False) -> "_abi.ShfCamera":
+    c = _abi.ShfCamera()
+    c.width, c.height = int(width), int(height)
+    c.horizontal_fov, c.near_plane, c.far_plane = float(horizontal_fov), float(near), float(far)
+    c.depth_negative = int(bool(depth_negative))
+    return c
+
+
+class Renderer:
+    """Device copies of one render scene (+ the terrain) and the launch of shf_render_cameras."""
+
+    def __init__(self, scene: "_abi.ShfRenderScene", terrain: Optional["_abi.ShfTerrain"] = None, heights=None,
+                 device="cuda:0"):
+        import torch
+        from .backend import _struct_to_device
+        self.device = torch.device(device)
+        if terrain is None:
+            terrain = _abi.ShfTerrain()
+            terrain.hscale = terrain.vscale = 1.0
+        if terrain.warped:
+            raise NotImplementedError("camera sensors cannot render a warped trimesh terrain (ShfTerrain.warped); height "
+                                      "fields and the ground plane only")
+        self.scene, self.terrain = scene, terrain
+        self._scene_dev = _struct_to_device(scene, self.device)
+        self._heights = None
+        if terrain.rows > 0:
+            h = heights if isinstance(heights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(heights, np.int16))
+            self._heights = h.to(self.device).contiguous()
+
+    def render(self, body_state, cam_pose, seg, color, camera: "_abi.ShfCamera", depth=None, seg_out=None, rgba=None):
+        """One launch for all envs: body_state (N * num_bodies, 13), cam_pose (N, 7), seg (N, num_bodies) int32, color
+        (N, num_bodies, 3) f32; writes depth (N, H, W) f32, seg_out (N, H, W) int32 and rgba (N, H, W, 4) u8, each optional."""
+        import torch
+        from ._lib import check, lib
+        from .backend import _stream_ptr
+        n = int(cam_pose.shape[0])
+        B, H, W = self.scene.num_bodies, camera.height, camera.width
+        for t, shape, dt in ((body_state, (n * B, 13), torch.float32), (cam_pose, (n, 7), torch.float32),
+                             (seg, (n, B), torch.int32), (color, (n, B, 3), torch.float32),
+                             (depth, (n, H, W), torch.float32), (seg_out, (n, H, W), torch.int32),
+                             (rgba, (n, H, W, 4), torch.uint8)):
+            if t is None:
+                continue
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"render: expected a contiguous {dt} tensor of shape {shape} on {self.device}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(self.device):
+            check(lib().shf_render_cameras(ptr(self._scene_dev), C.byref(self.terrain), ptr(self._heights), C.byref(camera), n,
+                                           ptr(body_state), ptr(cam_pose), ptr(seg), ptr(color), ptr(depth), ptr(seg_out),
+                                           ptr(rgba), _stream_ptr(self.device)))

@@ -1,3 +1,4 @@
 from .units import Unit, Actor, Sensor
 from .object import Object, Box
 from .robot import Robot, ArmRobot, LeggedRobot
+from .sensors import CameraSensor

@@ -1,0 +1,95 @@
+"""Camera-sensor benchmark: the vision stage's camera (reference examples/abb_pushbox_vision/task_config.py:124-145 --
+128 x 128, horizontal FOV 42, near 0.1, far 3, looking from (0.7, 0, 0.7) at (0, 0, 0.1), color + depth + segmentation)
+on the ABB push-box scene through the gym facade and CameraSensor.  Times the render launch alone with device events
+over --renders renders after warm-up, and prints one JSON line.
+
+    python tools/bench_camera.py --envs 1000
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+TARGET_MS = 1.0     # per render at 1000 envs, all three images
+
+
+def make_env(n):
+    import torch
+    from shifu_amd import compat
+    compat.install()
+    from isaacgym import gymapi as ga
+    from shifu.configs import CameraSensorConfig
+    from shifu.units import CameraSensor
+    from examples.abb_pushbox_vision.a_prior_stage import AbbPushBox, AbbRobot, GoalBox, RandPosBox
+    from examples.abb_pushbox_vision.task_config import AbbRobotConfig, GoalBoxConfig, PriorStageEnvConfig, PushBoxConfig, TableConfig
+    from shifu_amd.gym import ShifuVecEnv
+    from shifu_amd.units import Box
+
+    class PushBoxCameraConfig(CameraSensorConfig):
+        name = 'rgbd_camera'
+        local_lookat_positions = [[0.7, 0., 0.7], [0., 0., 0.1]]
+        image_types = [ga.IMAGE_COLOR, ga.IMAGE_DEPTH, ga.IMAGE_SEGMENTATION]
+        image_normalization = True
+
+        class camera_props(CameraSensorConfig.camera_props):
+            width, height, horizontal_fov, near_plane, far_plane = 128, 128, 42, 0.1, 3
+
+    class AbbPushBoxVision(AbbPushBox):
+        def __init__(self, cfg):
+            ShifuVecEnv.__init__(self, cfg)
+            self.robot = AbbRobot(AbbRobotConfig())
+            self.table, self.cube, self.goal = Box(TableConfig()), RandPosBox(PushBoxConfig()), GoalBox(GoalBoxConfig())
+            self.camera = CameraSensor(PushBoxCameraConfig())
+            self.isg_env.create_envs(robot=self.robot, objects=[self.table, self.cube, self.goal], sensors=[self.camera])
+            self.success_buf = torch.zeros(self.num_envs, device=self.device, dtype=torch.float)
+
+    cfg = PriorStageEnvConfig()
+    cfg.num_envs = n
+    return AbbPushBoxVision(cfg)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=1000)
+    ap.add_argument("--renders", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    a = ap.parse_args()
+    import torch
+    env = make_env(a.envs)
+    env.reset()
+    g = torch.Generator().manual_seed(0)
+    for _ in range(3):
+        env.step((2 * torch.rand(env.num_envs, env.num_actions, generator=g) - 1).to(env.device))
+    gym, sim, cam = env.isg_env.gym, env.isg_env.sim, env.camera
+    for _ in range(a.warmup):
+        gym.render_camera_group(sim, cam.camera_handle)
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(a.renders):
+        gym.render_camera_group(sim, cam.camera_handle)
+    t1.record()
+    torch.cuda.synchronize()
+    ms = t0.elapsed_time(t1) / a.renders
+    W, H = cam.width, cam.height
+    rays = a.envs * W * H
+    seg = cam.segmentation_buf
+    out = dict(bench="camera_render", scene="abb_pushbox_vision", envs=a.envs, width=W, height=H,
+               image_types=["color", "depth", "segmentation"], renders=a.renders, ms_per_render=round(ms, 4),
+               rays_per_s=round(rays / (ms * 1e-3), 1), bytes_written=rays * (4 + 4 + 4),
+               write_gb_per_s=round(rays * 12 / (ms * 1e-3) / 1e9, 1), target_ms=TARGET_MS,
+               pixels_on_cube=round(float((seg == env.cube.segmentation_id).float().mean()), 4),
+               pixels_on_arm=round(float((seg == env.robot.segmentation_id).float().mean()), 4),
+               device=torch.cuda.get_device_name(0))
+    if a.envs == 1000:
+        out["meets_target"] = bool(ms <= TARGET_MS)
+    print(json.dumps(out))
+    env.destroy()
+
+
+if __name__ == "__main__":
+    main()

@@ -791,16 +791,68 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
 #endif
     const float* Wcol = tail + T::W + (own ? l : 0) * T::WS;     // (KC = 8) block (l, c) sits at Wcol + c * KC * WS
     const int li = own ? l : 0;
-    // one visit of the sweep: contact c (oracle: hard_solve, sweeps)
+    // (KC = 8) this lane's block of column c: four 8-byte reads and one word (W and WS are even)
+    auto wload8 = [&](int c, float* Wb) {
+      const float2* b2 = reinterpret_cast<const float2*>(Wcol + c * KC * T::WS);
+      const float2 w01 = b2[0], w23 = b2[1], w45 = b2[2], w67 = b2[3];
+      Wb[0] = w01.x; Wb[1] = w01.y; Wb[2] = w23.x; Wb[3] = w23.y; Wb[4] = w45.x; Wb[5] = w45.y; Wb[6] = w67.x; Wb[7] = w67.y;
+      Wb[8] = Wcol[c * KC * T::WS + 8];
+    };
+    const unsigned long long ownm = __ballot(own);      // (bit c: c < K of env A, bit 32 + c: of env B)
+    // KC = 8: one visit of the sweep, contact c a constant (oracle: hard_solve, sweeps).  The sweep is eight of them unrolled:
+    // no loop counter, no lane index in a register, W's block (l, c) at a fixed offset.  Per visit one wave-uniform branch (the
+    // skip rule) and one more only when contact c of one of the two envs slides; the committing lanes take the update by selects,
+    // and DPP moves broadcast the change of the impulse.
+    auto visit8 = [&](auto cc, float tg, const float* Wb) {
+      constexpr int c = decltype(cc)::value;
+      constexpr unsigned long long lanes_c = (1ull << c) | (1ull << (32 + c));       // lane c of each env
+      // an open, unloaded contact whose normal velocity keeps it open asks for nothing (oracle: the same test): when that
+      // is so for contact c of both envs of the wavefront the visit is skipped.  The test as a lane mask -- !(p0 == 0 && p1 == 0
+      // && p2 == 0 && !(u0 < tg)), a ballot per compare -- and the committing lanes as its bits c and 32 + c
+      const unsigned long long act = __ballot(O.p[0] != 0.0f) | __ballot(O.p[1] != 0.0f) | __ballot(O.p[2] != 0.0f) | __ballot(O.u[0] < tg);
+      const unsigned long long cm = act & ownm & lanes_c;
+      if (cm == 0ull) return;
+      const bool commit = __builtin_amdgcn_inverse_ballot_w64(cm);      // l == c && c < K && act
+      // every owner lane computes its own update; lane c's is the one that counts
+      const float pn0 = O.p[0];
+      const float pn = rmaxf(fmaf(-(O.u[0] - tg), O.iwnn, pn0), 0.0f);
+      const float dn = pn - pn0;
+      const float ut1 = fmaf(dn, O.w10, O.u[1]), ut2 = fmaf(dn, O.w20, O.u[2]);
+      float ps1 = O.p[1] - fmaf(O.Ti[1], ut2, O.Ti[0] * ut1), ps2 = O.p[2] - fmaf(O.Ti[2], ut2, O.Ti[1] * ut1);
+      const float lim = O.mu * pn, lim2 = lim * lim;
+      // the sliding step: the wavefront runs it only when contact c of one of its envs really slides; on the other lanes its
+      // result is not selected (and on the owner lanes other than c it is discarded below)
+      const bool slide = fmaf(ps2, ps2, ps1 * ps1) > lim2;
+      if ((cm & __ballot(slide)) != 0ull) {
+        float q1 = fmaf(-O.rt, ut1, O.p[1]), q2 = fmaf(-O.rt, ut2, O.p[2]);
+        const float nt2 = fmaf(q2, q2, q1 * q1);
+        const float sc1 = nt2 > rmaxf(lim2, 1e-30f) ? lim * rsqrt_spec(nt2) : 1.0f;   // (1e-30: a subnormal |p_t|^2 over a zero cone would make 0 * inf)
+        q1 *= sc1; q2 *= sc1;
+        ps1 = slide ? q1 : ps1; ps2 = slide ? q2 : ps2;
+      }
+      // the change is new - old: pn - pn0 = dn on the committing lane, exactly 0 on the others
+      const float n0 = commit ? pn : O.p[0], n1 = commit ? ps1 : O.p[1], n2 = commit ? ps2 : O.p[2];
+      const float dp0 = n0 - O.p[0], dp1 = n1 - O.p[1], dp2 = n2 - O.p[2];
+      O.p[0] = n0; O.p[1] = n1; O.p[2] = n2;
+      // the change of contact c's impulse, from its owner lane (lane c of each env: wave lanes c and 32 + c) to the owner lanes
+      const float b0 = hard_row_bcast<c>(dp0), b1 = hard_row_bcast<c>(dp1), b2 = hard_row_bcast<c>(dp2);
+      const bool take = own && c < K;
+#pragma unroll
+      for (int r = 0; r < 3; r++) {
+        const float ur = fmaf(Wb[3 * r + 2], b2, fmaf(Wb[3 * r + 1], b1, fmaf(Wb[3 * r], b0, O.u[r])));
+        O.u[r] = take ? ur : O.u[r];
+      }
+    };
+    // KC = 16: one visit of the sweep, contact c a loop counter (oracle: hard_solve, sweeps)
     auto visit = [&](int c, float tg) {
       // an open, unloaded contact whose normal velocity keeps it open asks for nothing (oracle: the same test): when that
       // is so for contact c of both envs of the wavefront the visit is skipped
       const bool act = !(O.p[0] == 0.0f && O.p[1] == 0.0f && O.p[2] == 0.0f && !(O.u[0] < tg));
       if (__ballot(l == c && c < K && act) == 0ull) return;
-      // this lane's block of column c: in flight while the update is computed
+      // this lane's block of column c, in flight while the update is computed: block (l, c) from the upper triangle, as stored
+      // when l <= c, else the transpose of block (c, l)
       float Wb[9];
-      if constexpr (T::PACKED) {
-        // block (l, c) from the upper triangle: as stored when l <= c, else the transpose of block (c, l)
+      {
         const bool tr = li > c;
         const float* blk = hard_wblock<CD, KC>(L, tail, tr ? c : li, tr ? li : c);
         float Ws[9];
@@ -810,11 +862,6 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
         for (int r = 0; r < 3; r++)
 #pragma unroll
           for (int k = 0; k < 3; k++) Wb[3 * r + k] = tr ? Ws[3 * k + r] : Ws[3 * r + k];
-      } else {
-        const float2* b2 = reinterpret_cast<const float2*>(Wcol + c * KC * T::WS);      // (8-byte aligned: W and WS are even)
-        const float2 w01 = b2[0], w23 = b2[1], w45 = b2[2], w67 = b2[3];
-        Wb[0] = w01.x; Wb[1] = w01.y; Wb[2] = w23.x; Wb[3] = w23.y; Wb[4] = w45.x; Wb[5] = w45.y; Wb[6] = w67.x; Wb[7] = w67.y;
-        Wb[8] = Wcol[c * KC * T::WS + 8];
       }
       // every owner lane computes its own update; lane c's is the one that counts
       const float pn0 = O.p[0];
@@ -862,11 +909,16 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
 #pragma unroll 1
           for (int c = 0; c < Kw; c++) visit(c, tg);       // (a loop: sixteen unrolled visits would not fit the instruction cache)
         } else {
-#pragma unroll
-          for (int c = 0; c < KC; c++) {
-            if (c >= Kw) break;
-            visit(c, tg);
-          }
+          // block (l, c + 1) is read while visit c runs (W holds all KC x KC blocks: reading the one after the last visit is harmless)
+          float Wb[KC][9];
+          wload8(0, Wb[0]);
+          hard_static_while<0, KC>([&](auto cc) {
+            constexpr int c = decltype(cc)::value;
+            if (c >= Kw) return false;
+            if constexpr (c + 1 < KC) wload8(c + 1, Wb[c + 1]);
+            visit8(cc, tg, Wb[c]);
+            return true;
+          });
         }
         if constexpr (TGS) {
           if (phase == 0) {

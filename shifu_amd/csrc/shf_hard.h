@@ -63,6 +63,23 @@ __host__ __device__ inline int hard_total_slots(int nbase, bool link) {   // con
 #define HB_FDL 21       /* root / box record: LDL^T factors in words 0..20, then the velocity rate */
 
 DEV float hard_readlane(float x, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), lane)); }
+// lane c of every row of 16 lanes to the whole row (DPP row_newbcast:c, one move): with c < 8, wave lane c reaches lanes 0-7 (env A's
+// owner lanes at 32 lanes per env) and lane 32 + c lanes 32-39 (env B's); rows 1 and 3 get values no owner reads
+template <int c>
+DEV float hard_row_bcast(float x) {
+  static_assert(c >= 0 && c < 16, "row_newbcast selects a lane of a row of 16");
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x150 + c, 0xf, 0xf, true));
+}
+// hard_static_while<C, N>(f): f(HardIdx<C>()), .. f(HardIdx<N - 1>()) while f returns true -- an unrolled loop whose index is a
+// constant expression in every copy, each copy nested in the one before (what one copy computes is there for the next, no copies)
+template <int N>
+struct HardIdx { static constexpr int value = N; };
+template <int C, int N, class F>
+DEV void hard_static_while(F&& f) {
+  if constexpr (C < N) {
+    if (f(HardIdx<C>())) hard_static_while<C + 1, N>(f);
+  }
+}
 // point velocity of the spatial velocity v6 (about O) at r
 DEV void hard_point(const float* v6, const float* r, float* o) {
   float t[3];

@@ -3,6 +3,7 @@
 
     python tools/phase_clock.py build         # here (no GPU): debug library with -DSHF_PHASE_CLOCK
     python tools/phase_clock.py [G] [steps] [--abb]   # on the MI355X box
+    python tools/phase_clock.py --chain --tgs       # the TGS form of the velocity-level solve (k_a1_chain_tgs, bench.py's default)
 
 Thread 0 of block 0 accumulates the cycle count between PHASE_MARKs (csrc/shf_device.h); the marks
 serialise the wave a little (s_memtime + waitcnt), so the total is a few % above the production kernel.
@@ -36,10 +37,13 @@ def main():
     split = "--split" in sys.argv     # --abb: arm and boxes on different waves (k_abb_step_ws); marks 24-29 are the arm wave's
     link = "--link" in sys.argv       # --abb: with link contacts (the run-time-shaped kernel)
     pgs = "--pgs" in sys.argv         # --chain: the velocity-level contact solve (k_a1_chain_pgs, csrc/shf_chain_hard.h)
+    tgs = "--tgs" in sys.argv         # --chain: the same solve with sub-stepped position iterations (k_a1_chain_tgs)
+    solver = "tgs" if tgs else ("pgs" if pgs else "compliant")
+    pgs = pgs or tgs                  # (the two share the kernel's phases and marks)
     selfc = "--self" in sys.argv      # --chain: with self-collision
     terrain = "trimesh" if "--trimesh" in sys.argv else "heightfield"
     hull = "--hull" in sys.argv       # --abb --link: the links as convex hulls (the EXT instantiation of the run-time-shaped kernel)
-    argv = [a for a in sys.argv if a not in ("--abb", "--chain", "--levels", "--split", "--link", "--pgs", "--self", "--trimesh", "--hull")]
+    argv = [a for a in sys.argv if a not in ("--abb", "--chain", "--levels", "--split", "--link", "--pgs", "--tgs", "--self", "--trimesh", "--hull")]
     G = int(argv[1]) if len(argv) > 1 else 32
     steps = int(argv[2]) if len(argv) > 2 else 100
     from shifu_amd import build as b
@@ -53,8 +57,8 @@ def main():
     from shifu_amd.gym.abb_fused import FusedAbbEnv
     # --abb: the sub-step phases (0-10) of the push-box env; its kernel has no marks outside the sub-steps
     env = (FusedAbbEnv(num_envs=4096, group=G, link_contacts=link, mapping="split" if split else ("body" if (levels or link) else "chain"),
-                       solver="pgs" if pgs else "compliant", **({"link_shapes": "hull"} if hull else {})) if abb else
-           FusedA1Env(num_envs=4096, group=G, mapping="chain" if chain else "body", solver="pgs" if pgs else "compliant",
+                       solver=solver, **({"link_shapes": "hull"} if hull else {})) if abb else
+           FusedA1Env(num_envs=4096, group=G, mapping="chain" if chain else "body", solver=solver,
                       self_collision=selfc, terrain=terrain))
     if chain:
         NAMES[0] = "dof lanes: drive efforts + local joint rotations"; NAMES[1] = "chain lanes: poses, velocities, motion subspaces"

@@ -10,12 +10,22 @@ __global__ __launch_bounds__(256, (G == 32 ? 2 : 1)) void k_a1_chain(A1Args A) {
 
 // the same step under the velocity-level contact solve (ShfSimParams.solver == SHF_SOLVER_PGS / SHF_SOLVER_TGS; csrc/shf_chain_hard.h):
 // k_a1_chain_pgs / _tgs hold 8 constraints per env, ..16 up to 16 (ShfSimParams.max_contacts > 8: the response matrix's upper triangle, packed)
+// Columns of the response matrix W a lane holds in registers through the sweeps (KC = 8; csrc/shf_chain_hard.h, H3).  The fused
+// step runs two waves per SIMD whatever it does and has the registers for the whole row in all eight forms; the hook path's
+// sub-step runs three or four waves per SIMD at 124 - 131 registers and would pay for the row with occupancy
+// (profiles/r08_wreg.md).  Overridable for experiment builds.
+#ifndef SHF_WR_FUSED
+#define SHF_WR_FUSED 8
+#endif
+#ifndef SHF_WR_HOOK
+#define SHF_WR_HOOK 0
+#endif
 template <bool TW, bool SELF>
-__global__ __launch_bounds__(256, 2) void k_a1_chain_pgs(A1Args A) { a1_chain_step_body<32, A1Chain, TW, SELF, true>(A); }
+__global__ __launch_bounds__(256, 2) void k_a1_chain_pgs(A1Args A) { a1_chain_step_body<32, A1Chain, TW, SELF, true, 8, false, SHF_WR_FUSED>(A); }
 template <bool TW, bool SELF>
 __global__ __launch_bounds__(256, 2) void k_a1_chain_pgs16(A1Args A) { a1_chain_step_body<32, A1Chain, TW, SELF, true, 16>(A); }
 template <bool TW, bool SELF>
-__global__ __launch_bounds__(256, 2) void k_a1_chain_tgs(A1Args A) { a1_chain_step_body<32, A1Chain, TW, SELF, true, 8, true>(A); }
+__global__ __launch_bounds__(256, 2) void k_a1_chain_tgs(A1Args A) { a1_chain_step_body<32, A1Chain, TW, SELF, true, 8, true, SHF_WR_FUSED>(A); }
 template <bool TW, bool SELF>
 __global__ __launch_bounds__(256, 2) void k_a1_chain_tgs16(A1Args A) { a1_chain_step_body<32, A1Chain, TW, SELF, true, 16, true>(A); }
 #define SHF_PICK4(K, warped, self) ((self) ? ((warped) ? reinterpret_cast<const void*>(K<true, true>) : reinterpret_cast<const void*>(K<false, true>)) \
@@ -57,7 +67,7 @@ DEV void sim_step_chain_pgs_body(const SimArgs& A) {
   ChainPoints<NR> LP;
   chain_points_load<G>(m, CD::NEV, l, C.sp.contact_offset + C.sp.rest_offset, LP);
   const RowLane RL = row_lane_load<CD>(l);
-  chain_substep_hard<G, CD, TW, SELF, KC, TGS>(C, L, l, X, LP, RL, A.body_force ? A.body_force + (size_t)e * nb * 3 : nullptr, mu, L.xch);
+  chain_substep_hard<G, CD, TW, SELF, KC, TGS, (KC == 8 ? SHF_WR_HOOK : 0)>(C, L, l, X, LP, RL, A.body_force ? A.body_force + (size_t)e * nb * 3 : nullptr, mu, L.xch);
   if (l < nd) {
     A.dof[((size_t)e * nd + l) * 2] = X.q;
     A.dof[((size_t)e * nd + l) * 2 + 1] = X.qd;

@@ -12,7 +12,8 @@
 //         down every constrained chain                                                  (<= 24 column lanes)
 //   H2    per contact: free velocity, targets, regularised diagonal block and its normal / tangential inverses   (owner lanes)
 //   H3    projected Gauss-Seidel: contact after contact; the owner lane of contact c computes its new impulse, every
-//         owner lane moves its contact's velocity by W[i][c] dp (one 3x3 block from LDS)
+//         owner lane moves its contact's velocity by W[i][c] dp (one 3x3 block -- KC = 8, fused step: from the lane's row of W,
+//         held in registers from H2b to the end of H3; else from LDS)
 //   H4    the impulses as forces: one vector pass inward / root / outward               (body, chain, root lanes)
 //         -- after the position iterations (poses) and after the velocity iterations (velocities)
 //   H5    integration
@@ -81,11 +82,22 @@ DEV HardLink hard_link_load(const float* rec) {
 // joint terms of the links on bs's chain up to bs (oracle: hc_impulse) ...
 template <class CD>
 struct HardResp { int cs, ks; float ub[CD::NLK], dv0[6]; };
+// the link records of moving body b's chain (the root's: chain 0), all reads in flight together
 template <class CD>
+DEV void hard_links_load(const ChainLds& L, int b, HardLink* Lk) {
+  constexpr int NLK = CD::NLK;
+  const int c = b > 0 ? (b - 1) / (NLK + 1) : 0;
+#pragma unroll
+  for (int k = 0; k < NLK; k++) Lk[k] = hard_link_load(L.jrec + (c * NLK + k) * JREC_STRIDE);
+}
+// BATCH: the chain's link records are read before the recursion (one LDS round trip) instead of one behind each link's test
+template <class CD, bool BATCH = false>
 DEV void hard_impulse(const ChainLds& L, const float* tail, int bs, const float* r, const float* e, HardResp<CD>& q) {
   constexpr int NLK = CD::NLK;
   q.cs = bs > 0 ? (bs - 1) / (NLK + 1) : 0;
   q.ks = bs > 0 ? (bs - 1) % (NLK + 1) : -1;
+  HardLink Lb[NLK];
+  if constexpr (BATCH) hard_links_load<CD>(L, bs, Lb);
   float p6[6], t[3];
   cross3(r, e, t);
 #pragma unroll
@@ -94,7 +106,7 @@ DEV void hard_impulse(const ChainLds& L, const float* tail, int bs, const float*
   for (int k = NLK - 1; k >= 0; k--) {
     q.ub[k] = 0.0f;
     if (k <= q.ks) {
-      const HardLink Lk = hard_link_load(L.jrec + (q.cs * NLK + k) * JREC_STRIDE);
+      const HardLink Lk = BATCH ? Lb[k] : hard_link_load(L.jrec + (q.cs * NLK + k) * JREC_STRIDE);
       float sp = Lk.S[0] * p6[0];
 #pragma unroll
       for (int j = 1; j < 6; j++) sp = fmaf(Lk.S[j], p6[j], sp);
@@ -129,6 +141,40 @@ DEV void hard_velocity(const ChainLds& L, const float* tail, const HardResp<CD>&
     }
   }
   hard_point(dv, r, vel);
+}
+
+// hard_velocity with the link records of bt's chain already in registers (hard_links_load)
+template <class CD>
+DEV void hard_velocity_links(const HardResp<CD>& q, int bt, const HardLink* Lc, const float* r, float* vel) {
+  constexpr int NLK = CD::NLK;
+  if (bt < 0) { vel[0] = 0.0f; vel[1] = 0.0f; vel[2] = 0.0f; return; }
+  const int ct = bt > 0 ? (bt - 1) / (NLK + 1) : 0, kt = bt > 0 ? (bt - 1) % (NLK + 1) : -1;
+  float dv[6];
+#pragma unroll
+  for (int j = 0; j < 6; j++) dv[j] = q.dv0[j];
+#pragma unroll
+  for (int k = 0; k < NLK; k++) {
+    if (k <= kt) {
+      const HardLink& Lk = Lc[k];
+      const float ubk = (ct == q.cs && k <= q.ks) ? q.ub[k] : 0.0f;
+      float ua = Lk.U[0] * dv[0];
+#pragma unroll
+      for (int j = 1; j < 6; j++) ua = fmaf(Lk.U[j], dv[j], ua);
+      const float dq = (ubk - ua) * Lk.invD;
+#pragma unroll
+      for (int j = 0; j < 6; j++) dv[j] = fmaf(Lk.S[j], dq, dv[j]);
+    }
+  }
+  hard_point(dv, r, vel);
+}
+// A target of a column of W (H1): what the column lane reads of contact i's record -- point, frame, solver body (no second body)
+struct HardTarget { float r[3], n[3], t1[3], t2[3]; int ba; };
+DEV HardTarget hard_target_load(const float* h) {
+  HardTarget t;
+#pragma unroll
+  for (int k = 0; k < 3; k++) { t.r[k] = h[HC_R + k]; t.n[k] = h[HC_N + k]; t.t1[k] = h[HC_T1 + k]; t.t2[k] = h[HC_T2 + k]; }
+  t.ba = __float_as_int(h[HC_BODY]);
+  return t;
 }
 
 // H4: the impulses in the constraint records as forces on their bodies -> what they add to the accelerations.  Both
@@ -264,14 +310,21 @@ DEV void chain_hard_apply(const ShfModel* m, const ChainLds& L, float* tail, int
 }
 
 // One gym.simulate() for one env under the velocity-level contact solve; lane roles as chain_substep at 32 lanes per env.
-template <int G, class CD, bool TW, bool SELF, int KC, bool TGS>
-DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane& X, const ChainPoints<(CD::NEV + G - 1) / G>& P,
+// WR (KC = 8): the columns of W whose block (l, c) the lane holds in registers from H2b to the end of H3; a form that holds
+// any re-reads its sample-point constants from the staged model every sub-step (PIN is not read) instead of carrying them
+// through the solve -- the registers are the row's.
+template <int G, class CD, bool TW, bool SELF, int KC, bool TGS, int WR>
+DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane& X, const ChainPoints<(CD::NEV + G - 1) / G>& PIN,
                             const RowLane& RL, const float* fext, float mu_shape, float* contact_out) {
   static_assert(G == 32, "the velocity-level solve is written for two envs per wavefront");
   constexpr int NCH = CD::NCH, NLK = CD::NLK, NB = CD::NB, ND = CD::ND, NR = (CD::NEV + G - 1) / G;
   typedef HardTail<CD, KC> T;
   static_assert(T::END <= CD::NPC * PT_STRIDE, "the solve's LDS fits the contact-slot region");
   static_assert((KC == 8 || KC == 16) && KC <= G / 2 + 8 && ND < 16, "owner lanes; a lane per column of the response matrix, in one or two passes");
+  static_assert(WR >= 0 && WR <= KC && (WR == 0 || !T::PACKED), "the register row is the KC = 8 layout's");
+  // the fused KC = 8 forms without self-collision: H1's LDS reads batched and requested an iteration ahead (with self-collision
+  // the second body's link records do not fit the registers: 100 B of scratch)
+  constexpr bool PIPE = WR > 0 && !SELF;
   const ShfModel* m = C.m;
   const float dt = C.sp.dt, idt = 1.0f / dt;
   const float gon = (float)m->gravity_on;
@@ -287,6 +340,9 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
   const int myb = lb < ND ? CD::body(lb / NLK, lb % NLK) : 0;
   const int lane0 = (int)(threadIdx.x & 63u) - l;
   PHASE_BEGIN();
+  ChainPoints<NR> PL;
+  if constexpr (WR > 0) chain_points_load<G>(C.m, CD::NEV, l, C.sp.contact_offset + C.sp.rest_offset, PL);
+  const ChainPoints<NR>& P = WR > 0 ? PL : PIN;
 
   // ---- A. dof lanes: drive effort and the joint's local rotation -> joint record
   if (isdof) {
@@ -712,12 +768,43 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
       const float* ej = hj + (ax == 0 ? HC_N : (ax == 1 ? HC_T1 : HC_T2));     // axis ax of contact j's frame
       const float e[3] = {ej[0], ej[1], ej[2]};
       HardResp<CD> qa, qb;
-      hard_impulse<CD>(L, tail, bsa, rj, e, qa);
+      hard_impulse<CD, PIPE>(L, tail, bsa, rj, e, qa);
       if constexpr (SELF) {
-        if (__ballot(bsb >= 0) != 0ull) hard_impulse<CD>(L, tail, bsb >= 0 ? bsb : 0, rj, e, qb);
+        if (__ballot(bsb >= 0) != 0ull) hard_impulse<CD, PIPE>(L, tail, bsb >= 0 ? bsb : 0, rj, e, qb);
       }
       // One block of every symmetric pair (oracle: hard_solve, "columns"): block (i, j) from this column for i = j, j - 1, .. j - K / 2
       // (modulo K; for even K the pair at distance K / 2 belongs to the columns j >= K / 2): K / 2 + 1 targets per lane at most
+      // PIPE: target d + 1's record is requested before target d is computed, and the link records of a target's chain are read
+      // together: an iteration waits on one LDS round trip (the links) instead of one per record and per link.  The same
+      // operations on the same values.  (Requesting the links an iteration ahead as well, the loop unrolled, does not fit the
+      // registers H1 has: 20 - 36 B of scratch.)
+      if constexpr (PIPE) {
+        static_assert(!SELF && !T::PACKED, "one chain per target; W in full");
+        auto target_rec = [&](int d) {       // contact i(d)'s record; a lane without that target reads record 0
+          int i = j - d;
+          if (i < 0) i += K;
+          return tail + T::HC + ((i >= 0 && i < KC) ? i : 0) * HC_STRIDE;
+        };
+        HardTarget nxt = hard_target_load(target_rec(0));
+#pragma unroll 1
+        for (int d = 0; 2 * d <= KC; d++) {
+          if (__ballot(2 * d <= K) == 0ull) break;
+          const bool todo = col && 2 * d <= K && d < K && !(d > 0 && 2 * d == K && 2 * j < K);
+          int i = j - d;
+          if (i < 0) i += K;
+          const HardTarget cur = nxt;
+          nxt = hard_target_load(target_rec(d + 1));
+          if (!todo) continue;
+          HardLink curL[NLK];
+          hard_links_load<CD>(L, cur.ba, curL);
+          float vw[3];      // (the second bodies' terms are zeros here: (aa - 0) - (0 - 0) = aa, bit for bit)
+          hard_velocity_links<CD>(qa, cur.ba, curL, cur.r, vw);
+          const float w0 = dot3(cur.n, vw), w1 = dot3(cur.t1, vw), w2 = dot3(cur.t2, vw);    // column ax of block (i, j): the velocity in contact i's frame
+          float* Wb = hard_wblock<CD, KC>(L, tail, i, j) + ax;
+          Wb[0] = w0; Wb[3] = w1; Wb[6] = w2;
+          if (i != j) { float* Wt = hard_wblock<CD, KC>(L, tail, j, i) + 3 * ax; Wt[0] = w0; Wt[1] = w1; Wt[2] = w2; }     // row ax of block (j, i)
+        }
+      } else
 #pragma unroll 1
       for (int d = 0; 2 * d <= KC; d++) {
         if (__ballot(2 * d <= K) == 0ull) break;
@@ -798,6 +885,13 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
       Wb[0] = w01.x; Wb[1] = w01.y; Wb[2] = w23.x; Wb[3] = w23.y; Wb[4] = w45.x; Wb[5] = w45.y; Wb[6] = w67.x; Wb[7] = w67.y;
       Wb[8] = Wcol[c * KC * T::WS + 8];
     };
+    // (KC = 8) the lane's row of W: blocks (l, 0 .. WR - 1), read once behind H2b's barrier (the owners have written the regularised
+    // diagonal back), all reads in flight together.  W does not change until the next sub-step's H1.
+    float Wrow[WR > 0 ? WR : 1][9];
+    if constexpr (WR > 0) {
+#pragma unroll
+      for (int c = 0; c < WR; c++) wload8(c, Wrow[c]);
+    }
     const unsigned long long ownm = __ballot(own);      // (bit c: c < K of env A, bit 32 + c: of env B)
     // KC = 8: one visit of the sweep, contact c a constant (oracle: hard_solve, sweeps).  The sweep is eight of them unrolled:
     // no loop counter, no lane index in a register, W's block (l, c) at a fixed offset.  Per visit one wave-uniform branch (the
@@ -909,14 +1003,15 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
 #pragma unroll 1
           for (int c = 0; c < Kw; c++) visit(c, tg);       // (a loop: sixteen unrolled visits would not fit the instruction cache)
         } else {
-          // block (l, c + 1) is read while visit c runs (W holds all KC x KC blocks: reading the one after the last visit is harmless)
+          // columns c < WR from the register row: no LDS between the visits.  A column the row does not hold: block (l, c + 1) is
+          // read while visit c runs (W holds all KC x KC blocks: reading the one after the last visit is harmless)
           float Wb[KC][9];
-          wload8(0, Wb[0]);
+          if constexpr (WR == 0) wload8(0, Wb[0]);
           hard_static_while<0, KC>([&](auto cc) {
             constexpr int c = decltype(cc)::value;
             if (c >= Kw) return false;
-            if constexpr (c + 1 < KC) wload8(c + 1, Wb[c + 1]);
-            visit8(cc, tg, Wb[c]);
+            if constexpr (c + 1 < KC && c + 1 >= WR) wload8(c + 1, Wb[c + 1]);
+            if constexpr (c < WR) visit8(cc, tg, Wrow[c]); else visit8(cc, tg, Wb[c]);
             return true;
           });
         }

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SHF_ABI_VERSION 16
+#define SHF_ABI_VERSION 17
 
 #define SHF_MAX_BODIES 32 /* reported rigid bodies per articulation        */
 #define SHF_MAX_DOFS 32
@@ -631,7 +631,7 @@ int shf_abb_reset_all(ShfAbbTask* task, void* stream);
  * (shifu/runner/policy_runner.py:4,52-73): ActorCritic MLPs of nn.Linear + ELU (shifu/configs/policy_config.py:8-16).
  * These three entry points are one layer's forward and backward as MFMA GEMMs (bf16 operands converted on the fly from
  * the fp32 tensors, fp32 accumulation) with bias / ELU / ELU' fused; row-major fp32 tensors, no torch types.
- *   forward          y[M,N]  = act(x[M,K] w[N,K]^T + b[N])                        act: 0 = identity, 1 = ELU
+ *   forward          y[M,N]  = act(x[M,K] w[N,K]^T + b[N])                        act: 0 = identity, 1 = ELU, 2 = ReLU (forward only)
  *   backward_input   dx[M,K] = (dy (.) act'(y))[M,N] w[N,K]                       y = the forward's output, or NULL (identity)
  *   backward_weight  dw[N,K] = (dy (.) act'(y))^T x,  db[N] = column sums          workspace: see *_workspace (floats)
  * Operand precision (process-wide, shf_mlp_set_precision): SHF_MLP_BF16X3 (default) splits every fp32 operand value
@@ -649,6 +649,9 @@ int shf_mlp_get_precision(void);
 const char* shf_mlp_last_error(void);
 int shf_mlp_linear_forward(const float* x, const float* w, const float* b, float* y, int32_t M, int32_t K, int32_t N,
                            int32_t act, void* stream);
+/* The same forward with row strides (in elements, ldx >= K, ldy >= N): y may be a column block of a wider matrix. */
+int shf_mlp_linear_forward_ld(const float* x, int32_t ldx, const float* w, const float* b, float* y, int32_t ldy, int32_t M,
+                              int32_t K, int32_t N, int32_t act, void* stream);
 int shf_mlp_linear_backward_input(const float* dy, const float* y_or_null, const float* w, float* dx, int32_t M, int32_t K,
                                   int32_t N, void* stream);
 /* Row-panel forms of forward / backward_input (round 4; results equal the two calls above bit for bit).  The weights
@@ -683,6 +686,35 @@ int shf_mlp_chain_fits(const ShfMlpChain* chain);
 int shf_mlp_backward_weight_workspace(int32_t M, int32_t K, int32_t N, int64_t* floats);
 int shf_mlp_linear_backward_weight(const float* dy, const float* y_or_null, const float* x, float* dw, float* db,
                                    float* workspace, int32_t M, int32_t K, int32_t N, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Conv-encoder inference (ABI v17; csrc/shf_conv.hip): the vision stage's regressor in eval mode
+ * (shifu/models/autoencoders.py: Conv2d(3 x 3, stride 2, padding 1) + BatchNorm2d + ReLU stacks).  One layer:
+ *   y[n, oy, ox, co] = relu( (sum_{ci,ky,kx} x[n, ci, 2 oy + ky - 1, 2 ox + kx - 1] w[co, ci, ky, kx]) * scale[co] + shift[co] )
+ * as an implicit GEMM on the matrix cores with the operand scheme and precision switch of the trainer kernels above
+ * (shf_mlp_set_precision).  scale / shift carry the eval-mode batch norm and the conv bias (scale = gamma / sqrt(var + eps),
+ * shift = beta + (bias - mean) scale), applied in fp32 after the accumulation.  Any C_in >= 1, any C_out, even H and W.
+ *   pack     w[C_out, C_in, 3, 3] (fp32, contiguous) laid out once in fragment order in a caller-owned device buffer of
+ *            shf_conv_pack_bytes(C_in, C_out) bytes (16-byte aligned); repack whenever w changes
+ *   x        read in place through the element strides {image, channel, row, column}:
+ *            SHF_CONV_SRC_F32 fp32; SHF_CONV_SRC_F32_NEG fp32, negated; SHF_CONV_SRC_U8_UNORM bytes, (float)x * (1.0f / 255.0f)
+ *            -- the fp32 reciprocal, not a division: that is what torch.div(u8 tensor, 255.0) computes on the GPU (it
+ *            multiplies by the rounded reciprocal; 126 of the 256 byte values differ in the last bit from x / 255.0f), and
+ *            CameraSensor's normalised color_buf is made that way -- the two input forms give identical bits
+ *   y        fp32 [n, H/2, W/2, C_out] (flatten = 0: the next layer's input, strides {H/2 W/2 C_out, 1, W/2 C_out, C_out}) or
+ *            [n, C_out, H/2, W/2] (flatten = 1: torch.flatten order for a following linear layer)
+ * An output value depends on its own image only and not on the batch size.  A non-finite input value makes the outputs of
+ * its image that it reaches NaN, no others.  No atomics, no host synchronisation: capturable in a hipGraph.
+ * ---------------------------------------------------------------------- */
+#define SHF_CONV_SRC_F32 0
+#define SHF_CONV_SRC_F32_NEG 1
+#define SHF_CONV_SRC_U8_UNORM 2
+const char* shf_conv_last_error(void);
+int shf_conv_pack_bytes(int32_t cin, int32_t cout, int64_t* bytes);
+int shf_conv_pack_weights(const float* w, void* pack, int32_t cin, int32_t cout, void* stream);
+int shf_conv3x3s2_forward(const void* x, int32_t src_kind, const int64_t* strides, const void* pack, const float* scale,
+                          const float* shift, float* y, int32_t flatten, int32_t nimg, int32_t cin, int32_t h, int32_t w,
+                          int32_t cout, void* stream);
 
 /* PPO mini-batch loss with its gradient, one pass (rsl_rl's PPO.update loss block [EXT], which the reference's runner
  * drives: shifu/runner/policy_runner.py:52-73 with PPOConfig.algorithm, shifu/configs/policy_config.py:18-31):

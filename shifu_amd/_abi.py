@@ -1,7 +1,7 @@
 """ctypes mirrors of the PODs in include/shifu_amd.h (keep in lock-step)."""
 import ctypes as C
 
-SHF_ABI_VERSION = 16
+SHF_ABI_VERSION = 17
 MAP_BODY, MAP_CHAIN, MAP_CHAIN_SPLIT = 0, 1, 2   # shf_sim_set_mapping
 MAX_BODIES = 32
 MAX_DOFS = 32
@@ -152,5 +152,9 @@ REFRESH_DOF, REFRESH_ROOT, REFRESH_BODY, REFRESH_CONTACT, REFRESH_JACOBIAN, REFR
 (A1_ACTIONS, A1_OBS, A1_REW, A1_RESET, A1_TIMEOUT, A1_EP_LEN, A1_COMMAND, A1_HISTORY, A1_REW_SUMS, A1_TORQUES,
  A1_BASE_VEL, A1_HEIGHTS, A1_HPOINTS, A1_PUSH, A1_ORIGINS, A1_LEVELS, A1_TYPES, A1_TORIGINS, A1_RESET_COUNT,
  A1_DONE_SUMS, A1_STATS, A1_PARAMS, A1_STATS_ACC, A1_COUNT) = range(24)
+
+# conv-encoder inference (ABI v17; csrc/shf_conv.hip)
+CONV_SRC_F32, CONV_SRC_F32_NEG, CONV_SRC_U8_UNORM = 0, 1, 2
+ACT_NONE, ACT_ELU, ACT_RELU = 0, 1, 2
 
 DTYPE_F32, DTYPE_I32, DTYPE_I16, DTYPE_U8, DTYPE_I64 = range(5)

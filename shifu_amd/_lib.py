@@ -56,6 +56,7 @@ _SIGS = {
     "shf_abb_step_random": ([vp, vp], i32),
     "shf_abb_reset_all": ([vp, vp], i32),
     "shf_mlp_linear_forward": ([vp, vp, vp, vp, i32, i32, i32, i32, vp], i32),
+    "shf_mlp_linear_forward_ld": ([vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "shf_mlp_linear_backward_input": ([vp, vp, vp, vp, i32, i32, i32, vp], i32),
     "shf_mlp_backward_weight_workspace": ([i32, i32, i32, C.POINTER(i64)], i32),
     "shf_mlp_pack_bytes": ([i32, i32, C.POINTER(i64)], i32),
@@ -86,8 +87,12 @@ _SIGS = {
     "shf_ppo_loss": ([vp] * 10 + [i64, i32, C.c_float, C.c_float, C.c_float, i32] + [vp] * 6, i32),
     # camera sensors (csrc/shf_render.hip)
     "shf_render_cameras": ([vp, C.POINTER(_abi.ShfTerrain), vp, C.POINTER(_abi.ShfCamera), i32] + [vp] * 7 + [vp], i32),
+    # conv-encoder inference (csrc/shf_conv.hip)
+    "shf_conv_pack_bytes": ([i32, i32, C.POINTER(i64)], i32),
+    "shf_conv_pack_weights": ([vp, vp, i32, i32, vp], i32),
+    "shf_conv3x3s2_forward": ([vp, i32, C.POINTER(i64), vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
 }
-EXPORTS = sorted(list(_SIGS) + ["shf_last_error", "shf_mlp_last_error"])
+EXPORTS = sorted(list(_SIGS) + ["shf_last_error", "shf_mlp_last_error", "shf_conv_last_error"])
 
 
 class BackendError(RuntimeError):
@@ -109,6 +114,7 @@ def lib():
             f.argtypes, f.restype = args, res
         l.shf_last_error.restype = C.c_char_p
         l.shf_mlp_last_error.restype = C.c_char_p
+        l.shf_conv_last_error.restype = C.c_char_p
         if l.shf_abi_version() != _abi.SHF_ABI_VERSION:
             raise BackendError("libshifu_amd.so ABI version mismatch: rebuild")
         _lib = l

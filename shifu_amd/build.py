@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "libshifu_amd.so")
 # (csrc/shf_kernel_list.h) so that they compile side by side -- as one unit the library took 4.5 minutes to build.
 KERNEL_UNITS = ["shf_k_sim.hip", "shf_k_sim_link.hip", "shf_k_sim_hard.hip", "shf_k_sim_hard_wide.hip", "shf_k_a1.hip", "shf_k_abb.hip",
                 "shf_k_abb_link.hip", "shf_k_abb_hard.hip", "shf_k_abb_ws.hip", "shf_k_abb_ws_hard.hip", "shf_k_sim_ext.hip", "shf_k_abb_ext.hip", "shf_k_hull_test.hip"]
-UNITY_SOURCES = ["shf_api.hip", "shf_a1_chain.hip", "shf_glue.hip", "shf_mlp.hip", "shf_k_hull_test.hip", "shf_render.hip"]      # with -DSHF_UNITY: shf_api.hip instantiates every kernel
+UNITY_SOURCES = ["shf_api.hip", "shf_a1_chain.hip", "shf_glue.hip", "shf_mlp.hip", "shf_k_hull_test.hip", "shf_render.hip", "shf_conv.hip"]      # with -DSHF_UNITY: shf_api.hip instantiates every kernel
 SOURCES = UNITY_SOURCES + [u for u in KERNEL_UNITS if u not in UNITY_SOURCES]
 HEADERS = ["shf_device.h", "shf_boxes.h", "shf_task.h", "shf_chain.h", "shf_chain_hard.h", "shf_hard.h", "shf_link.h", "shf_arm.h", "shf_kernels.h",
            "shf_kernel_list.h", "shf_hull.h", os.path.join("..", "..", "include", "shifu_amd.h")]
@@ -84,7 +84,11 @@ BUDGETS = [("_Z16k_a1_step_a1_g32", 256, 0),          # default: A1, two envs pe
            ("_Z18k_abb_step_ws_hardILb1EE", 256, 64), ("_Z18k_abb_step_ws_hardILb0EE", 256, 0),
            ("_Z10k_sim_stepILi32ELb0ELb0ELb0ELb1ELb0EE", 168, 0), ("_Z10k_sim_stepILi32ELb1ELb0ELb1ELb1ELb0EE", 256, 32),
            # the camera ray caster (csrc/shf_render.hip): per-pixel state in registers, none on the stack
-           ("_Z16k_render_cameras", 128, 0)]
+           ("_Z16k_render_cameras", 128, 0),
+           # the conv-encoder layer (csrc/shf_conv.hip), every instantiation: 214 registers at most in the first clean build (64
+           # accumulators, a chunk's weight fragments, the gathered rows in flight) plus a margin of 10 for compiler drift -- still
+           # two waves per SIMD; nothing on the stack
+           ("_ZN12_GLOBAL__N_111k_conv3x3s2", 224, 0)]
 
 
 def parse_resources(remarks: str) -> dict:

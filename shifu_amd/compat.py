@@ -25,8 +25,13 @@ _ALIASES = {
     "shifu.gym": "shifu_amd.gym",
     "shifu.units": "shifu_amd.units",
     "shifu.runner": "shifu_amd.runner",
+    "shifu.runner.module_runner": "shifu_amd.runner.module_runner",
+    "shifu.models": "shifu_amd.models",
+    "shifu.models.module": "shifu_amd.models.module",
+    "shifu.models.autoencoders": "shifu_amd.models.autoencoders",
     "shifu.utils": "shifu_amd.utils",
     "shifu.utils.train": "shifu_amd.utils.train",
+    "shifu.utils.data": "shifu_amd.utils.data",
     "shifu.utils.terrain": "shifu_amd.utils.terrain",
     "shifu.utils.torch_utils": "shifu_amd.utils.torch_utils",
 }

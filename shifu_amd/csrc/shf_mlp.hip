@@ -191,7 +191,7 @@ struct Epilogue {
   float* c;            // output [rows, cols], row-major, ld = ldc
   int ldc;
   const float* bias;   // per column, or null
-  int act;             // 0 none, 1 ELU
+  int act;             // 0 none, 1 ELU, 2 ReLU (keeps NaN)
   float* colsum;       // optional [gridDim.z][cols] partial column sums of the A operand (db), written by blockIdx.y == 0
 };
 
@@ -339,6 +339,7 @@ __global__ __launch_bounds__(256) void k_mlp_gemm(Operand A, Operand B, int red,
         if (E.act == 1) v = v > 0.0f ? v : __expf(v) - 1.0f;     // ELU, alpha = 1 (exp(x) - 1, as the stock elu kernel)
 #endif
 #endif
+        if (E.act == 2) v = v < 0.0f ? 0.0f : v;
         T[((reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)) * EPI_TS + (lane & 31)] = v;
       }
       __builtin_amdgcn_wave_barrier();
@@ -1169,15 +1170,27 @@ extern "C" int shf_mlp_set_precision(int32_t mode) {
 }
 extern "C" int shf_mlp_get_precision(void) { return g_mlp_precision; }
 
+// y[M, N] (row stride ldy) = act(x[M, K] (row stride ldx) W[N, K]^T + b); `who` names the entry point in the error text
+static int linear_forward(const char* who, const float* x, int32_t ldx, const float* w, const float* b, float* y, int32_t ldy,
+                          int32_t M, int32_t K, int32_t N, int32_t act, void* stream) {
+  const std::string name(who);
+  if (!x || !w || !y) return mlp_fail(name + ": null tensor");
+  if (M <= 0 || K <= 0 || N <= 0 || ldx < K || ldy < N || act < 0 || act > 2) return mlp_fail(name + ": bad shape / activation");
+  if (too_big(M, ldx, ldy) || too_big(M, K, N)) return mlp_fail(name + ": a tensor has 2^32 elements or more");
+  Operand A{x, nullptr, ldx, M}, B{w, nullptr, K, N};
+  Epilogue E{y, ldy, b, act, nullptr};
+  launch_gemm<true, true, false>((hipStream_t)stream, A, B, K, K, 1, E, M, N);
+  return hipGetLastError() == hipSuccess ? 0 : mlp_fail(name + ": launch failed");
+}
+
 extern "C" int shf_mlp_linear_forward(const float* x, const float* w, const float* b, float* y, int32_t M, int32_t K, int32_t N,
                                       int32_t act, void* stream) {
-  if (!x || !w || !y) return mlp_fail("shf_mlp_linear_forward: null tensor");
-  if (M <= 0 || K <= 0 || N <= 0 || act < 0 || act > 1) return mlp_fail("shf_mlp_linear_forward: bad shape / activation");
-  if (too_big(M, K, N)) return mlp_fail("shf_mlp_linear_forward: a tensor has 2^32 elements or more");
-  Operand A{x, nullptr, K, M}, B{w, nullptr, K, N};
-  Epilogue E{y, N, b, act, nullptr};
-  launch_gemm<true, true, false>((hipStream_t)stream, A, B, K, K, 1, E, M, N);
-  return hipGetLastError() == hipSuccess ? 0 : mlp_fail("shf_mlp_linear_forward: launch failed");
+  return linear_forward("shf_mlp_linear_forward", x, K, w, b, y, N, M, K, N, act, stream);
+}
+
+extern "C" int shf_mlp_linear_forward_ld(const float* x, int32_t ldx, const float* w, const float* b, float* y, int32_t ldy, int32_t M,
+                                         int32_t K, int32_t N, int32_t act, void* stream) {
+  return linear_forward("shf_mlp_linear_forward_ld", x, ldx, w, b, y, ldy, M, K, N, act, stream);
 }
 
 extern "C" int shf_mlp_linear_backward_input(const float* dy, const float* y_or_null, const float* w, float* dx, int32_t M,

@@ -107,6 +107,11 @@ class CameraSensor(Sensor):
         """This sensor's camera group, rendered for every env (one launch)."""
         self.gym.render_camera_group(self.sim, self.camera_handle)
 
+    def raw_images(self):
+        """The camera group's own image tensors as rendered, before refresh() converts them: {"rgba": (N, H, W, 4) u8,
+        "depth": (N, H, W) f32, negative view depth, "seg": (N, H, W) i32}.  Views, not copies."""
+        return self._images
+
     def refresh(self):
         self.refresh_image_tensors()
 

@@ -17,7 +17,8 @@ if ROOT not in sys.path:
 TARGET_MS = 1.0     # per render at 1000 envs, all three images
 
 
-def make_env(n):
+def vision_env_class():
+    """(env class, env config class): the push-box scene of stage a with the vision stage's camera added."""
     import torch
     from shifu_amd import compat
     compat.install()
@@ -47,9 +48,14 @@ def make_env(n):
             self.isg_env.create_envs(robot=self.robot, objects=[self.table, self.cube, self.goal], sensors=[self.camera])
             self.success_buf = torch.zeros(self.num_envs, device=self.device, dtype=torch.float)
 
-    cfg = PriorStageEnvConfig()
+    return AbbPushBoxVision, PriorStageEnvConfig
+
+
+def make_env(n):
+    env_class, cfg_class = vision_env_class()
+    cfg = cfg_class()
     cfg.num_envs = n
-    return AbbPushBoxVision(cfg)
+    return env_class(cfg)
 
 
 def main():

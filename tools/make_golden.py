@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generate tests/golden/*.npz by running the REFERENCE's own Python on synthetic CPU
-tensors (vectors G1-G11).  Runs only in the build container, where
+tensors (vectors G1-G12).  Runs only in the build container, where
 /root/reference exists; the reference never travels -- only these input/output arrays do.
 
 The reference cannot be imported as is: `isaacgym`, `rsl_rl` (and cv2, pybullet, ...) are
@@ -10,7 +10,8 @@ helpers restated from SURVEY appendices C/D), everything else by empty modules. 
 vectors pin is therefore the reference's *glue* (shifu/gym/env.py, shifu/gym/isaac_gym.py,
 shifu/utils/*.py, examples/*), given those helper definitions.
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py            # all vectors
+    PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py g12        # only those whose name starts with g12
 """
 import os
 import sys
@@ -324,6 +325,83 @@ def g11_configs(rng):
     save("g11_configs", effective=np.array(json.dumps(eff, sort_keys=True)), ppo=np.array(json.dumps(ppo, sort_keys=True)))
 
 
+def g12_models(rng):
+    """The vision stage's model classes (shifu/models): state_dict names / shapes of the full-size regressor of
+    examples/abb_pushbox_vision/b_regression_stage.py:106-126, and a small instance with its complete state dict (batch-norm
+    statistics and affine terms randomised: with the fresh 0 / 1 the outputs barely depend on the input), two images per
+    modality, its eval- and train-mode outputs and the loss_func values against recorded labels."""
+    import copy
+    import inspect
+    import json
+    import shifu.models.autoencoders as ae
+    assert inspect.getsourcefile(ae).startswith(REF + "/"), inspect.getsourcefile(ae)
+
+    def regressor(latent, hidden=None, dec=(16, 8)):
+        kw = {} if hidden is None else dict(hidden_dims=hidden)
+        act = torch.nn.ReLU(True)
+        enc = {"rgb": ae.ConvEncoder(in_channels=3, latent_dim=latent, activation=act, **kw),
+               "depth": ae.ConvEncoder(in_channels=1, latent_dim=latent, activation=act, **kw)}
+        decs = {k: ae.Decoder(input_dim=latent, output_dim=2, hidden_dims=list(dec)) for k in ("obj_pos", "goal_pos", "ee_pos")}
+        return ae.MultimodalAE(encoders=enc, decoders=decs, latent_dim=latent, device="cpu")
+
+    full = regressor(32)
+    full_sd = full.state_dict()
+    layout = [[k, list(v.shape)] for k, v in full_sd.items()]
+    nparam = sum(p.numel() for p in full.parameters())
+
+    small = regressor(8, hidden=(4, 4, 8, 8, 8, 16))
+    g = torch.Generator().manual_seed(12)
+    with torch.no_grad():
+        for name, buf in small.named_buffers():
+            if name.endswith("running_mean"):
+                buf.copy_(0.3 * torch.randn(buf.shape, generator=g))
+            elif name.endswith("running_var"):
+                buf.copy_(0.5 + torch.rand(buf.shape, generator=g))
+        for mod in small.modules():
+            if isinstance(mod, torch.nn.BatchNorm2d):
+                mod.weight.copy_(0.7 + 0.6 * torch.rand(mod.weight.shape, generator=g))
+                mod.bias.copy_(0.2 * torch.randn(mod.bias.shape, generator=g))
+            elif isinstance(mod, torch.nn.Conv2d):
+                mod.weight.mul_(3.0)        # the default initialisation shrinks the signal layer by layer: keep activations O(1)
+            elif isinstance(mod, torch.nn.Linear):
+                mod.weight.mul_(2.0)
+    sd = {k: v.clone() for k, v in small.state_dict().items()}
+    # two different scenes: smooth ramps with a bright / near box in different places, plus pixel noise
+    yy, xx = torch.meshgrid(torch.arange(128.0), torch.arange(128.0), indexing="ij")
+    rgb = torch.zeros(2, 3, 128, 128)
+    depth = torch.zeros(2, 1, 128, 128)
+    for i, (cy, cx, half) in enumerate(((40, 90, 14), (85, 30, 22))):
+        box = ((yy - cy).abs() < half) & ((xx - cx).abs() < half)
+        for c in range(3):
+            ramp = (xx if (c + i) % 2 else yy) / 127.0
+            rgb[i, c] = torch.where(box, torch.tensor(0.9 - 0.3 * c), 0.15 + 0.5 * ramp)
+        depth[i, 0] = torch.where(box, torch.tensor(0.8 + 0.2 * i), 1.2 + 0.9 * yy / 127.0)
+    rgb = (255.0 * (rgb + 0.05 * torch.rand(rgb.shape, generator=g)).clamp(0, 1)).round() / 255.0
+    depth = depth + 0.02 * torch.rand(depth.shape, generator=g)
+    labels = {k: torch.randn(2, 2, generator=g) for k in ("obj_pos", "goal_pos", "ee_pos")}
+    small.eval()
+    with torch.no_grad():
+        ev = small({"rgb": rgb.clone(), "depth": depth.clone()})
+        ev_loss, ev_logs = small.loss_func(ev, labels)
+    tr_model = copy.deepcopy(small)
+    tr_model.train()
+    with torch.no_grad():
+        tr = tr_model({"rgb": rgb.clone(), "depth": depth.clone()})
+        tr_loss, tr_logs = tr_model.loss_func(tr, labels)
+    arrays = {"full_layout": np.array(json.dumps(layout)), "full_num_params": np.array(nparam),
+              "small_keys": np.array(json.dumps(list(sd.keys()))), "small_num_params": np.array(sum(p.numel() for p in small.parameters())),
+              "rgb": rgb, "depth": depth, "eval_loss": ev_loss, "train_loss": tr_loss}
+    for k, v in sd.items():
+        arrays["sd/" + k] = v
+    for k in labels:
+        arrays["label/" + k] = labels[k]
+        arrays["eval/" + k] = ev[k]
+        arrays["train/" + k] = tr[k]
+        arrays["eval_loss/" + k] = ev_logs[k]
+        arrays["train_loss/" + k] = tr_logs[k]
+    save("g12_models", **arrays)
+
+
 def main():
     if not os.path.isdir(REF):
         raise SystemExit("the reference tree is not present: golden vectors can only be (re)generated in the build container")
@@ -334,8 +412,11 @@ def main():
     for mod in (ref_a1, ref_env):   # the vectors must come from the REFERENCE's code, not this repo's mirror
         assert inspect.getsourcefile(mod).startswith(REF + "/"), inspect.getsourcefile(mod)
     rng = np.random.default_rng(20261001)
+    only = sys.argv[1:]
     for fn in (g1_observations, g2_termination, g3_rewards, g4_history, g5_reset_log, g6_heights, g7_curriculum,
-               g8_terrain, g9_ik, g10_abb, g11_configs):
+               g8_terrain, g9_ik, g10_abb, g11_configs, g12_models):
+        if only and not any(fn.__name__.startswith(o) for o in only):
+            continue
         torch.manual_seed(0)
         fn(rng)
 

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SHF_ABI_VERSION 17
+#define SHF_ABI_VERSION 18
 
 #define SHF_MAX_BODIES 32 /* reported rigid bodies per articulation        */
 #define SHF_MAX_DOFS 32
@@ -439,6 +439,18 @@ int shf_sim_set_mapping(ShfSim* sim, int32_t mapping);
 
 /* gym.simulate (a1_conditional.py:69, robot.py:69, isaac_gym.py:140) */
 int shf_sim_step(ShfSim* sim, void* stream);
+/* What a step entry launches for the configuration as it stands (ABI v18): the kernel's mangled symbol (a string owned by
+ * the library), workgroups, threads per workgroup and dynamic LDS per workgroup.  shf_sim_step / shf_a1_step / shf_abb_step
+ * launch exactly what shf_sim_step_plan / shf_a1_step_plan / shf_abb_step_plan report -- both go through one selection -- so
+ * resource tables, benchmarks and tests name the kernel that runs.  Host only: no tensor needs to be bound and no GPU to be
+ * present.  Returns 0, or non-zero with shf_last_error() set to the message the step entry gives for this configuration.
+ * For shf_sim_step a force armed by shf_sim_apply_body_force* is part of the configuration (it clears with the launch). */
+typedef struct ShfLaunchPlan {
+  const char* kernel;
+  int32_t grid, block;
+  int64_t lds_bytes;
+} ShfLaunchPlan;
+int shf_sim_step_plan(const ShfSim* sim, ShfLaunchPlan* plan);
 /* gym.refresh_{dof_state,actor_root_state,rigid_body_state,jacobian,
  * net_contact_force}_tensor(s) (isaac_gym.py:145-154, a1_conditional.py:72) */
 int shf_sim_refresh(ShfSim* sim, int32_t mask, void* stream);
@@ -556,6 +568,8 @@ int shf_a1_step(ShfA1Task* task, const float* raw_actions_dev, void* stream);
  * global env id, vec-step index, dof), so that a random-action roll-out is one launch per vec-step and a sharded run
  * draws what the unsharded one does.  The clipped, scaled actions land in SHF_A1_ACTIONS as usual. */
 int shf_a1_step_random(ShfA1Task* task, void* stream);
+/* The kernel shf_a1_step / shf_a1_step_random launch (ShfLaunchPlan above). */
+int shf_a1_step_plan(const ShfA1Task* task, ShfLaunchPlan* plan);
 /* ShifuVecEnv.reset_idx(arange(N)) part of reset() (env.py:108-112). */
 int shf_a1_reset_all(ShfA1Task* task, void* stream);
 
@@ -620,8 +634,10 @@ int shf_abb_bind(ShfAbbTask* task, int32_t id, void* device_ptr);
 int shf_abb_step(ShfAbbTask* task, const float* raw_actions_dev, void* stream);
 /* run_policy('random') for the ABB task: as shf_a1_step_random (three end-effector action components per env). */
 int shf_abb_step_random(ShfAbbTask* task, void* stream);
-/* Introspection (resource tables, tests): 1 when shf_abb_step runs this task under SHF_SOLVER_PGS on the 512-thread form of the
- * run-time-shaped kernel (sixteen envs per workgroup: chosen where their LDS fits one CU), else 0. */
+/* The kernel shf_abb_step / shf_abb_step_random launch (ShfLaunchPlan above). */
+int shf_abb_step_plan(const ShfAbbTask* task, ShfLaunchPlan* plan);
+/* 1 when that kernel is the 512-thread form of the run-time-shaped velocity-level step (k_abb_step_pgs_wide: sixteen envs per
+ * workgroup, chosen where their LDS fits one CU), else 0. */
 int shf_abb_step_pgs_is_wide(const ShfAbbTask* task);
 /* reset_idx(arange(N)) (env.py:108-112). */
 int shf_abb_reset_all(ShfAbbTask* task, void* stream);

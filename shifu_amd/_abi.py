@@ -1,7 +1,7 @@
 """ctypes mirrors of the PODs in include/shifu_amd.h (keep in lock-step)."""
 import ctypes as C
 
-SHF_ABI_VERSION = 17
+SHF_ABI_VERSION = 18
 MAP_BODY, MAP_CHAIN, MAP_CHAIN_SPLIT = 0, 1, 2   # shf_sim_set_mapping
 MAX_BODIES = 32
 MAX_DOFS = 32
@@ -56,6 +56,10 @@ class ShfModel(C.Structure):
 class ShfBoxDesc(C.Structure):
     _fields_ = [("dim", f32 * 3), ("mass", f32), ("friction", f32), ("fixed", i32),
                 ("pos", f32 * 3), ("quat", f32 * 4)]
+
+
+class ShfLaunchPlan(C.Structure):     # shf_sim_step_plan / shf_a1_step_plan / shf_abb_step_plan
+    _fields_ = [("kernel", C.c_char_p), ("grid", i32), ("block", i32), ("lds_bytes", C.c_int64)]
 
 
 class ShfScene(C.Structure):

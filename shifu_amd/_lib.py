@@ -31,6 +31,7 @@ _SIGS = {
     "shf_sim_bind": ([vp, i32, vp], i32),
     "shf_sim_reset_all": ([vp, vp, vp, vp, vp], i32),
     "shf_sim_step": ([vp, vp], i32),
+    "shf_sim_step_plan": ([vp, C.POINTER(_abi.ShfLaunchPlan)], i32),
     "shf_sim_refresh": ([vp, i32, vp], i32),
     "shf_sim_set_dof_command": ([vp, i32, vp, vp], i32),
     "shf_sim_set_pos_target_indexed": ([vp, vp, vp, i32, vp], i32),
@@ -47,6 +48,7 @@ _SIGS = {
     "shf_a1_bind": ([vp, i32, vp], i32),
     "shf_a1_step": ([vp, vp, vp], i32),
     "shf_a1_step_random": ([vp, vp], i32),
+    "shf_a1_step_plan": ([vp, C.POINTER(_abi.ShfLaunchPlan)], i32),
     "shf_a1_reset_all": ([vp, vp], i32),
     "shf_abb_create": ([vp, C.POINTER(_abi.ShfAbbTaskParams), C.POINTER(vp)], i32),
     "shf_abb_destroy": ([vp], i32),
@@ -54,6 +56,7 @@ _SIGS = {
     "shf_abb_bind": ([vp, i32, vp], i32),
     "shf_abb_step": ([vp, vp, vp], i32),
     "shf_abb_step_random": ([vp, vp], i32),
+    "shf_abb_step_plan": ([vp, C.POINTER(_abi.ShfLaunchPlan)], i32),
     "shf_abb_reset_all": ([vp, vp], i32),
     "shf_mlp_linear_forward": ([vp, vp, vp, vp, i32, i32, i32, i32, vp], i32),
     "shf_mlp_linear_forward_ld": ([vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),

@@ -89,6 +89,18 @@ def _struct_to_device(s, device) -> torch.Tensor:
     return torch.frombuffer(bytearray(bytes(s)), dtype=torch.uint8).to(device)
 
 
+def _plan_symbol(plan_fn, handle) -> str:
+    """The kernel a step entry launches (shf_*_step_plan), as the build's resource table names it up to the parameter list:
+    the mangled symbol without the encoding of its one by-value argument block."""
+    p = _abi.ShfLaunchPlan()
+    check(plan_fn(handle, C.byref(p)))
+    name = p.kernel.decode()
+    for tail in ("v7SimArgs", "v6A1Args", "v7AbbArgs", "6A1Args"):      # (templates encode their void return type)
+        if name.endswith(tail):
+            return name[:-len(tail)]
+    return name
+
+
 def heightfield_nz_min(samples: np.ndarray, hscale: float, vscale: float) -> float:
     """ShfTerrain.nz_min: a lower bound on n_z of every normal a height-field query can return.  The query's gradients
     are differences of neighbouring samples along x and along y (either triangle of a cell), so the steepest normal is
@@ -239,6 +251,10 @@ class Sim:
         check(lib().shf_sim_set_mapping(self._h, _abi.MAP_CHAIN_SPLIT))
         self.mapping = "split"
         return True
+
+    def kernel_symbol(self) -> str:
+        """Mangled name (without its parameter list) of the kernel gym.simulate (shf_sim_step) launches: shf_sim_step_plan."""
+        return _plan_symbol(lib().shf_sim_step_plan, self._h)
 
     def bind_contact_hist(self, on: bool = True):
         """SHF_T_CONTACT_HIST (velocity-level solve): per env, how many sub-steps offered k candidate constraints before the
@@ -472,23 +488,8 @@ class A1Task:
         return idx % (self.tensors[_abi.A1_STATS].shape[0] - 1)
 
     def kernel_symbol(self) -> str:
-        """Mangled-name prefix of the instantiation shf_a1_step launches for this sim (build resource table)."""
-        g, warped = self.sim.group, bool(self.sim.terrain.warped)
-        mdl = self.sim.model
-        if self.sim.params.solver != _abi.SOLVER_COMPLIANT:
-            k16 = int(self.sim.params.max_contacts) > 8      # up to 16 constraints per env: the packed-response-matrix kernel
-            name = ("k_a1_chain_tgs" if self.sim.params.solver == _abi.SOLVER_TGS else "k_a1_chain_pgs") + ("16" if k16 else "")
-            return f"_Z{len(name)}{name}ILb{int(warped)}ELb{int(bool(mdl.self_collide and mdl.npair > 0))}EE"
-        if getattr(self.sim, "mapping", "body") == "chain":
-            return f"_Z10k_a1_chainILi{g}ELb{int(warped)}ELb{int(bool(mdl.self_collide and mdl.npair > 0))}EE"
-        a1 = mdl.nb == 17 and mdl.nd == 12 and mdl.np == 76
-        if mdl.self_collide and mdl.npair > 0:
-            if a1:
-                return "_Z21k_a1_step_self_a1_g32" if not warped else "_Z14k_a1_step_selfILi32E9FixedDims"
-            return f"_Z14k_a1_step_selfILi{g}E7DynDims"
-        if a1:
-            return "_Z16k_a1_step_a1_g32" if (g == 32 and not warped) else f"_Z9k_a1_stepILi{g}E9FixedDims"
-        return f"_Z9k_a1_stepILi{g}E7DynDims"
+        """Mangled name (without its parameter list) of the kernel shf_a1_step launches for this sim: shf_a1_step_plan."""
+        return _plan_symbol(lib().shf_a1_step_plan, self._h)
 
     @_on_device
     def reset_all(self):
@@ -555,31 +556,8 @@ class AbbTask:
         return idx % (self.tensors[_abi.ABB_STATS].shape[0] - 1)
 
     def kernel_symbol(self) -> str:
-        """Mangled-name prefix of the instantiation shf_abb_step launches for this sim (build resource table)."""
-        mdl = self.sim.model
-        link = bool(mdl.link_collide and self.sim.nboxes > 0)
-        fixed = mdl.nb == 7 and mdl.np == (59 if link else 3) and self.sim.nboxes == 3
-        pre = f"_Z10k_abb_stepILi{self.sim.group}E"
-        if mdl.nhull > 0 or getattr(self.sim, "scene_flags", 0):     # the convex narrow phase compiled in (csrc/shf_hull.h): run-time shapes
-            hard = int(self.sim.params.solver != _abi.SOLVER_COMPLIANT)
-            return f"_Z10k_abb_stepILi{32 if hard else self.sim.group}E7DynDims8DynSceneLb1ELi0ELb{hard}ELb1EE"
-        if self.sim.params.solver != _abi.SOLVER_COMPLIANT and getattr(self.sim, "mapping", "body") == "split":
-            return f"_Z18k_abb_step_ws_hardILb{int(link)}EE"     # arm wave + box wave, the solve regrouped at 32 lanes per env
-        if self.sim.params.solver != _abi.SOLVER_COMPLIANT:    # the generic velocity-level solve: run-time shapes, 32 lanes per env
-            if lib().shf_abb_step_pgs_is_wide(self._h):   # sixteen envs per workgroup of 512 threads
-                return f"_Z19k_abb_step_pgs_wideILb{int(link)}EE"
-            return f"_Z10k_abb_stepILi32E7DynDims8DynSceneLb{int(link)}ELi0ELb1ELb0EE"
-        if not fixed:
-            return pre + "7DynDims"
-        if link:    # the shipped arm with its link volumes in the shipped scene (AbbLinkDims, AbbScene)
-            if getattr(self.sim, "mapping", "body") == "split":
-                return "_Z13k_abb_step_wsILi512ELb1EE"
-            return pre + "9FixedDimsILi7ELi6ELi59ELi6ELi6EE10FixedSceneILi3ELi1ELi2EELb1ELi0ELb0ELb0EE"
-        mp = getattr(self.sim, "mapping", "body")
-        if mp == "split":
-            return "_Z13k_abb_step_wsILi256ELb0EE"
-        arm = 6 if mp == "chain" else 0
-        return pre + f"9FixedDimsILi7ELi6ELi3ELi6ELi6EE10FixedSceneILi3ELi1ELi2EELb0ELi{arm}ELb0ELb0EE"
+        """Mangled name (without its parameter list) of the kernel shf_abb_step launches for this sim: shf_abb_step_plan."""
+        return _plan_symbol(lib().shf_abb_step_plan, self._h)
 
     @_on_device
     def reset_all(self):

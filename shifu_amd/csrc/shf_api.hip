@@ -4,6 +4,7 @@
 // (shf_sim_bind / shf_a1_bind), kernels are launched on the stream handed in
 // and nothing here synchronises.  gfx950 only.
 #include <hip/hip_runtime.h>
+#include <dlfcn.h>
 
 #include <cstdio>
 #include <cstring>
@@ -101,14 +102,27 @@ static int sim_ndyn(const ShfSim* s) {   // free boxes: the only ones that own c
   for (int k = 0; k < s->nboxes; k++) n += (!s->boxes[k].fixed && s->boxes[k].mass > 0.0f) ? 1 : 0;
   return n;
 }
-static size_t sim_lds_bytes(const ShfSim* s, int head_words, int min_tail, bool boxes = false) {
-  const int epb = 256 / s->group;
+// dynamic LDS of one 256-thread block of the body-mapped kernels at `lanes` lanes per env
+static size_t sim_lds_bytes(const ShfSim* s, int lanes, int head_words, int min_tail, bool boxes = false) {
+  const int epb = 256 / lanes;
   const int nbx = boxes ? s->nboxes : 0;
   int nslots = s->model.np + (boxes ? box_slot_count(nbx, sim_ndyn(s), s->model.nsph) : 0) + (sim_self(s) ? SHF_MAX_SELF_CONTACTS : 0) +
                ((boxes && sim_link(s)) ? 2 * SHF_MAX_LINK_CONTACTS : 0);
   if (s->sp.solver != SHF_SOLVER_COMPLIANT) nslots = hard_total_slots(nslots, boxes && sim_link(s));
   return ((size_t)MODEL_WORDS + head_words + (boxes ? SCENE_WORDS : 0) +
           (size_t)epb * env_lds_words(s->model.nb + nbx, s->model.nd, nslots, min_tail, 1 + (boxes ? nbx : s->nboxes))) * 4;
+}
+// ... and of one workgroup of the ABB step kernels (and k_sim_step_ws_hard, which shares their layout): the header plus `epb`
+// envs.  hard: the slot region of the velocity-level solves (csrc/shf_hard.h); extra_tail: words behind an env's slots and
+// targets -- ARM_TAIL for the kernels that keep the arm recursions' link records, WS_LINK_STASH_WORDS on top for the
+// wave-specialised ones that park the free box per env
+constexpr int ARM_TAIL = ARM_KREC_WORDS(SHF_ARM_MAX_LINKS);
+static_assert(ABB_TAIL_WORDS(8, 6) == ABB_TAIL_WORDS_NOARM(8, 6) + ARM_TAIL, "ABB_TAIL_WORDS = the arm-less tail + the link records");
+static size_t abb_lds_bytes(const ShfSim* s, int epb, int extra_tail, bool hard) {
+  const int nbx = s->nboxes, base = s->model.np + box_slot_count(nbx, sim_ndyn(s), s->model.nsph) + (sim_link(s) ? 2 * SHF_MAX_LINK_CONTACTS : 0);
+  const int nslots = hard ? hard_total_slots(base, sim_link(s)) : base;
+  return ((size_t)MODEL_WORDS + SCENE_WORDS + ABB_WORDS + STATS_LDS_WORDS +
+          (size_t)epb * env_lds_words(s->model.nb + nbx, s->model.nd, nslots, ABB_TAIL_WORDS_NOARM(nslots, s->model.nd) + extra_tail, 1 + nbx)) * 4;
 }
 
 extern "C" int shf_sim_create(const ShfSimParams* params, ShfSim** out) {
@@ -387,18 +401,19 @@ static SimArgs sim_args(const ShfSim* s, bool internal) {
   return A;
 }
 
-template <typename K, typename... Args>
-static int launch(K kernel, dim3 grid, dim3 block, size_t lds, void* stream, Args... args) {
-  if (lds > 160 * 1024) return fail("kernel needs " + std::to_string(lds) + " B of LDS per block, the CU has 160 KiB");
+static int lds_fits(size_t lds) {
+  return lds > 160 * 1024 ? fail("kernel needs " + std::to_string(lds) + " B of LDS per block, the CU has 160 KiB") : 0;
+}
+// above the default dynamic-LDS limit a kernel has to opt in -- once per (device, kernel, size): the attribute call is not
+// a stream operation and must not recur while the caller's stream is being captured into a hipGraph (shifu_amd/rl captures
+// whole rollouts).  fn: the kernel's host function pointer
+static int grant_lds(const void* fn, size_t lds) {
+  if (int r = lds_fits(lds)) return r;
   if (lds > 48 * 1024) {
-    // above the default dynamic-LDS limit the kernel has to opt in -- once per (device, kernel, size): the
-    // attribute call is not a stream operation and must not recur while the caller's stream is being captured
-    // into a hipGraph (shifu_amd/rl captures whole rollouts)
     static std::mutex mu;
     static std::map<std::pair<int, const void*>, size_t> granted;
     int dev = 0;
     HIP_OK(hipGetDevice(&dev));
-    const void* fn = reinterpret_cast<const void*>(kernel);
     std::lock_guard<std::mutex> lock(mu);
     size_t& have = granted[{dev, fn}];
     if (have < lds) {
@@ -406,28 +421,16 @@ static int launch(K kernel, dim3 grid, dim3 block, size_t lds, void* stream, Arg
       have = lds;
     }
   }
+  return 0;
+}
+template <typename K, typename... Args>
+static int launch(K kernel, dim3 grid, dim3 block, size_t lds, void* stream, Args... args) {
+  if (int r = grant_lds(reinterpret_cast<const void*>(kernel), lds)) return r;
   hipLaunchKernelGGL(kernel, grid, block, lds, (hipStream_t)stream, args...);
   HIP_OK(hipGetLastError());
   return 0;
 }
-
-// the same for a kernel of another translation unit, given as its host function pointer and one by-value argument block
-static int grant_lds(const void* fn, size_t lds) {
-  if (lds > 160 * 1024) return fail("kernel needs " + std::to_string(lds) + " B of LDS per block, the CU has 160 KiB");
-  if (lds > 48 * 1024) {
-    static std::mutex mu;
-    static std::map<std::pair<int, const void*>, size_t> granted;
-    int dev = 0;
-    HIP_OK(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    size_t& have = granted[{dev, fn}];
-    if (have < lds) {
-      HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      have = lds;
-    }
-  }
-  return 0;
-}
+// the same for a kernel given as its host function pointer and one by-value argument block (SimArgs / A1Args / AbbArgs)
 template <typename ArgBlock>
 static int launch_ptr(const void* fn, dim3 grid, dim3 block, size_t lds, void* stream, ArgBlock& A) {
   if (int r = grant_lds(fn, lds)) return r;
@@ -436,145 +439,127 @@ static int launch_ptr(const void* fn, dim3 grid, dim3 block, size_t lds, void* s
   return 0;
 }
 
+// What one step entry launches for a configuration: decided by sim_step_plan / a1_step_plan / abb_step_plan below, which
+// validate the configuration and choose -- they change nothing and launch nothing; shf_sim_step / shf_a1_step / shf_abb_step
+// launch the plan, shf_*_step_plan report it.
+struct Plan {
+  const void* fn = nullptr;
+  dim3 grid, block;
+  size_t lds = 0;
+};
+static int set_plan(Plan& P, const void* fn, int n, int envs_per_block, int threads, size_t lds) {
+  P.fn = fn; P.grid = dim3((n + envs_per_block - 1) / envs_per_block); P.block = dim3(threads); P.lds = lds;
+  return 0;
+}
+#define KFN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+static const void* pick_lanes(int g, const void* k64, const void* k32, const void* k16) {
+  switch (g) {
+    case 64: return k64;
+    case 32: return k32;
+    default: return k16;
+  }
+}
+// K<64, ...>, K<32, ...> or K<16, ...>: the instantiation of a body-mapped kernel for g lanes per env
+#define PICK_LANES(g, K, ...) pick_lanes(g, KFN(K<64, __VA_ARGS__>), KFN(K<32, __VA_ARGS__>), KFN(K<16, __VA_ARGS__>))
+static int export_plan(int rc, const Plan& P, ShfLaunchPlan* out) {
+  if (rc) return rc;
+  if (int r = lds_fits(P.lds)) return r;
+  Dl_info di;
+  if (!dladdr(P.fn, &di) || !di.dli_sname) return fail("shf_*_step_plan: the kernel's symbol is not in the library's dynamic symbol table");
+  out->kernel = di.dli_sname;
+  out->grid = (int32_t)P.grid.x; out->block = (int32_t)P.block.x; out->lds_bytes = (int64_t)P.lds;
+  return 0;
+}
+
 // gym.simulate of the shipped arm in the shipped scene under the velocity-level solves has a kernel of its own (k_sim_step_ws_hard:
-// arm wave + box wave, the solve regrouped; csrc/shf_kernels.h) -- chosen with the split mapping.  What it is compiled for:
+// arm wave + box wave, the solve regrouped; csrc/shf_kernels.h) -- chosen with the split mapping.  What it is compiled for
+// (abb_shipped: the part it shares with the chain and split branches of shf_abb_step -- the shipped arm, with or without its
+// link volumes, in the shipped scene):
+static bool abb_shipped(const ShfSim* s) {
+  return ArmChain<6>::matches(s->model) && (sim_link(s) ? AbbLinkDims::matches(s->model) : AbbDims::matches(s->model)) &&
+         AbbScene::matches(s->nboxes, s->boxes, s->model.nsph);
+}
 static bool sim_ws_hard_ok(const ShfSim* s) {
   if (!s->finalized || s->sp.solver == SHF_SOLVER_COMPLIANT || s->nboxes == 0 || !sim_plain(s) || sim_self(s) || s->terr.warped) return false;
   if (s->sp.pos_iters < 1 || s->sp.max_contacts > HCK) return false;
-  if (!ArmChain<6>::matches(s->model) || !AbbScene::matches(s->nboxes, s->boxes, s->model.nsph)) return false;
-  if (!(sim_link(s) ? AbbLinkDims::matches(s->model) : AbbDims::matches(s->model))) return false;
+  if (!abb_shipped(s)) return false;
   for (int d = 0; d < s->model.nd; d++)
     if (s->model.drive_mode[d] == SHF_DOF_MODE_VEL) return false;      // (the arm lanes' drive law takes position targets and efforts)
   return true;
 }
 extern "C" int shf_sim_step_split_supported(const ShfSim* sim) { return (sim && sim_ws_hard_ok(sim)) ? 1 : 0; }
 
+// gym.simulate's kernel.  An armed force (shf_sim_apply_body_force*) is part of the configuration: two kernels take none,
+// or none with points of application.
+static int sim_step_plan(const ShfSim* s, Plan& P) {
+  const bool hard = s->sp.solver != SHF_SOLVER_COMPLIANT, boxes = s->nboxes > 0, self = sim_self(s), link = sim_link(s);
+  const bool force = s->force_armed && s->t[SHF_T_BODY_FORCE], force_pos = s->force_armed && s->force_at_pos && s->t[SHF_T_BODY_FORCE_POS];
+  const int g = s->group, n = s->n;
+  if (!sim_plain(s) && boxes) {
+    // a scene with ShfScene.flags or hulls: the run-time-shaped kernels with the convex narrow phase compiled in (csrc/shf_hull.h)
+    if (!link || self) return fail("shf_sim_step: scene flags / hulls need link contacts (ShfModel.link_collide) and no self-collision");
+    if (s->terr.warped) return fail("shf_sim_step: trimesh terrain with box actors is not supported");
+    if (hard) {
+      if (s->sp.max_contacts > HCK || s->sp.pos_iters < 1) return fail("shf_sim_step: SHF_SOLVER_PGS needs pos_iters >= 1 and max_contacts <= 8");
+      if (s->model.nlevels > HG_LEV || s->model.nb + s->nboxes > 32) return fail("shf_sim_step: SHF_SOLVER_PGS: at most 8 tree levels and 32 bodies + box actors");
+      return set_plan(P, KFN(k_sim_step<32, true, false, true, true, true>), n, 8, 256, sim_lds_bytes(s, 32, 0, 0, true));
+    }
+    if (s->model.nb + s->nboxes > g) return fail("shf_sim_step: bodies + boxes exceed the lane group");
+    return set_plan(P, PICK_LANES(g, k_sim_step, true, false, true, false, true), n, 256 / g, 256, sim_lds_bytes(s, g, 0, 0, true));
+  }
+  if (hard) {
+    // the velocity-level contact solve: built for A1-shaped articulations on their own (csrc/shf_chain_hard.h)
+    if (s->sp.max_contacts > shf_a1_chain_pgs_max_contacts() || s->sp.pos_iters < 1) return fail("shf_sim_step: SHF_SOLVER_PGS needs pos_iters >= 1 and max_contacts <= 16");
+    if (s->mapping == SHF_MAP_CHAIN && s->mapping_split && !force && sim_ws_hard_ok(s))     // arm wave + box wave: 512 threads = 16 envs per workgroup
+      return set_plan(P, link ? KFN(k_sim_step_ws_hard<true>) : KFN(k_sim_step_ws_hard<false>), n, 16, 512, abb_lds_bytes(s, 16, ARM_TAIL + WS_LINK_STASH_WORDS, true));
+    if (!boxes && shf_a1_chain_matches(s->model) && !force_pos)
+      return set_plan(P, shf_sim_step_chain_pgs_kernel(s->terr.warped != 0, self, s->sp.max_contacts > HCK, s->sp.solver == SHF_SOLVER_TGS), n, 8, 256,
+                      shf_sim_step_chain_pgs_lds_bytes(self));
+    if (s->sp.max_contacts > HCK) return fail("shf_sim_step: more than 8 constraints per env (ShfSimParams.max_contacts) are held by the chain-mapped A1 kernels only");
+    // any other articulation / a scene with box actors: the body-per-lane sub-step with the generic solve (csrc/shf_hard.h), 32 lanes per env
+    if (s->model.nlevels > HG_LEV) return fail("shf_sim_step: SHF_SOLVER_PGS walks trees of at most 8 levels");
+    if (s->model.nb + s->nboxes > 32) return fail("shf_sim_step: SHF_SOLVER_PGS runs at 32 lanes per env: at most 32 bodies + box actors");
+    if (s->terr.warped && boxes) return fail("shf_sim_step: trimesh terrain with box actors is not supported");
+    const size_t hlds = sim_lds_bytes(s, 32, 0, 0, boxes);
+    if (boxes && link) {
+      const size_t head = ((size_t)MODEL_WORDS + SCENE_WORDS) * 4, env8 = hlds - head, cu = (size_t)160 * 1024;
+      if (head + 2 * env8 <= cu && 2 * hlds > cu)      // sixteen envs per workgroup fit a CU, two workgroups of eight do not
+        return set_plan(P, self ? KFN(k_sim_step_pgs_wide<true>) : KFN(k_sim_step_pgs_wide<false>), n, 16, 512, head + 2 * env8);
+    }
+    const void* fn = !boxes ? (self ? KFN(k_sim_step<32, false, true, false, true>) : KFN(k_sim_step<32, false, false, false, true>))
+                     : link ? (self ? KFN(k_sim_step<32, true, true, true, true>) : KFN(k_sim_step<32, true, false, true, true>))
+                            : (self ? KFN(k_sim_step<32, true, true, false, true>) : KFN(k_sim_step<32, true, false, false, true>));
+    return set_plan(P, fn, n, 8, 256, hlds);
+  }
+  if (boxes && s->model.nb + s->nboxes > g) return fail("shf_sim_step: bodies + boxes exceed the lane group");
+  // (with link contacts, ShfModel.link_collide: the run-time-shaped kernels with the candidate pass compiled in)
+  const void* fn = !boxes ? (self ? PICK_LANES(g, k_sim_step, false, true) : PICK_LANES(g, k_sim_step, false, false))
+                   : link ? (self ? PICK_LANES(g, k_sim_step, true, true, true) : PICK_LANES(g, k_sim_step, true, false, true))
+                          : (self ? PICK_LANES(g, k_sim_step, true, true) : PICK_LANES(g, k_sim_step, true, false));
+  return set_plan(P, fn, n, 256 / g, 256, sim_lds_bytes(s, g, 0, 0, boxes));
+}
+extern "C" int shf_sim_step_plan(const ShfSim* sim, ShfLaunchPlan* out) {
+  if (!sim || !sim->finalized) return fail("shf_sim_step: sim not finalized");
+  if (!out) return fail("shf_sim_step_plan: null argument");
+  Plan P;
+  return export_plan(sim_step_plan(sim, P), P, out);
+}
+
 extern "C" int shf_sim_step(ShfSim* sim, void* stream) {
   if (int r = need(sim, {SHF_T_SIM_DOF, SHF_T_SIM_ROOT, SHF_T_SIM_CONTACT, SHF_T_MODEL}, "shf_sim_step")) return r;
   if (sim->model.nhull > 0 && sim->model.link_collide != 0 && sim->nboxes > 0 && !sim->t[SHF_T_HULLS]) return fail("shf_sim_step: the articulation's hulls (SHF_T_HULLS) are not bound");
   if (sim->terr.rows > 0 && !sim->t[SHF_T_HEIGHTS]) return fail("shf_sim_step: heightfield samples not bound");
+  if (sim->sp.solver == SHF_SOLVER_COMPLIANT && sim->nboxes > 0 && sim_plain(sim) && !sim->t[SHF_T_SCENE]) return fail("shf_sim_step: scene (box actors) not bound");
   SimArgs A = sim_args(sim, true);
   if (sim->force_armed) {
     A.body_force = (const float*)sim->t[SHF_T_BODY_FORCE];
     if (sim->force_at_pos) A.body_force_pos = (const float*)sim->t[SHF_T_BODY_FORCE_POS];
   }
-  if (!sim_plain(sim) && sim->nboxes > 0) {
-    // a scene with ShfScene.flags or hulls: the run-time-shaped kernels with the convex narrow phase compiled in (csrc/shf_hull.h)
-    if (!sim_link(sim) || sim_self(sim)) return fail("shf_sim_step: scene flags / hulls need link contacts (ShfModel.link_collide) and no self-collision");
-    if (sim->terr.warped) return fail("shf_sim_step: trimesh terrain with box actors is not supported");
-    if (sim->sp.solver != SHF_SOLVER_COMPLIANT) {
-      if (sim->sp.max_contacts > HCK || sim->sp.pos_iters < 1) return fail("shf_sim_step: SHF_SOLVER_PGS needs pos_iters >= 1 and max_contacts <= 8");
-      if (sim->model.nlevels > HG_LEV || sim->model.nb + sim->nboxes > 32) return fail("shf_sim_step: SHF_SOLVER_PGS: at most 8 tree levels and 32 bodies + box actors");
-      sim->force_armed = false; sim->force_at_pos = false;
-      const int keep = sim->group;
-      sim->group = 32;
-      const size_t hlds = sim_lds_bytes(sim, 0, 0, true);
-      sim->group = keep;
-      return launch(k_sim_step<32, true, false, true, true, true>, dim3((sim->n + 7) / 8), dim3(256), hlds, stream, A);
-    }
-    sim->force_armed = false; sim->force_at_pos = false;
-    if (sim->model.nb + sim->nboxes > sim->group) return fail("shf_sim_step: bodies + boxes exceed the lane group");
-    const int epb = 256 / sim->group;
-    const dim3 grid((sim->n + epb - 1) / epb), block(256);
-    const size_t lds = sim_lds_bytes(sim, 0, 0, true);
-    switch (sim->group) {
-      case 64: return launch(k_sim_step<64, true, false, true, false, true>, grid, block, lds, stream, A);
-      case 32: return launch(k_sim_step<32, true, false, true, false, true>, grid, block, lds, stream, A);
-      default: return launch(k_sim_step<16, true, false, true, false, true>, grid, block, lds, stream, A);
-    }
-  }
-  if (sim->sp.solver != SHF_SOLVER_COMPLIANT) {
-    // the velocity-level contact solve: built for A1-shaped articulations on their own (csrc/shf_chain_hard.h)
-    if (sim->sp.max_contacts > shf_a1_chain_pgs_max_contacts() || sim->sp.pos_iters < 1) return fail("shf_sim_step: SHF_SOLVER_PGS needs pos_iters >= 1 and max_contacts <= 16");
-    if (sim->mapping == SHF_MAP_CHAIN && sim->mapping_split && !A.body_force && sim_ws_hard_ok(sim)) {
-      const bool link = sim_link(sim);
-      const int nbx = sim->nboxes, wepb = 16;
-      const int nslots = hard_total_slots(sim->model.np + box_slot_count(nbx, sim_ndyn(sim), sim->model.nsph) + (link ? 2 * SHF_MAX_LINK_CONTACTS : 0), link);
-      const size_t wlds = ((size_t)MODEL_WORDS + SCENE_WORDS + ABB_WORDS + STATS_LDS_WORDS +
-                           (size_t)wepb * env_lds_words(sim->model.nb + nbx, sim->model.nd, nslots, ABB_TAIL_WORDS(nslots, sim->model.nd) + WS_LINK_STASH_WORDS, 1 + nbx)) * 4;
-      const dim3 wgrid((sim->n + wepb - 1) / wepb), wblock(512);
-      return link ? launch(k_sim_step_ws_hard<true>, wgrid, wblock, wlds, stream, A) : launch(k_sim_step_ws_hard<false>, wgrid, wblock, wlds, stream, A);
-    }
-    sim->force_armed = false;
-    sim->force_at_pos = false;
-    if (sim->nboxes == 0 && shf_a1_chain_matches(sim->model) && !A.body_force_pos)
-      return launch_ptr(shf_sim_step_chain_pgs_kernel(sim->terr.warped != 0, sim_self(sim), sim->sp.max_contacts > HCK, sim->sp.solver == SHF_SOLVER_TGS), dim3((sim->n + 7) / 8), dim3(256), shf_sim_step_chain_pgs_lds_bytes(sim_self(sim)), stream, A);
-    if (sim->sp.max_contacts > HCK) return fail("shf_sim_step: more than 8 constraints per env (ShfSimParams.max_contacts) are held by the chain-mapped A1 kernels only");
-    // any other articulation / a scene with box actors: the body-per-lane sub-step with the generic solve (csrc/shf_hard.h), 32 lanes per env
-    if (sim->model.nlevels > HG_LEV) return fail("shf_sim_step: SHF_SOLVER_PGS walks trees of at most 8 levels");
-    if (sim->model.nb + sim->nboxes > 32) return fail("shf_sim_step: SHF_SOLVER_PGS runs at 32 lanes per env: at most 32 bodies + box actors");
-    if (sim->terr.warped && sim->nboxes > 0) return fail("shf_sim_step: trimesh terrain with box actors is not supported");
-    const int keep = sim->group;
-    sim->group = 32;
-    const size_t hlds = sim_lds_bytes(sim, 0, 0, sim->nboxes > 0);
-    sim->group = keep;
-    const dim3 hgrid((sim->n + 7) / 8), hblock(256);
-    if (sim->nboxes > 0 && sim_link(sim)) {
-      const size_t head = ((size_t)MODEL_WORDS + SCENE_WORDS) * 4, env8 = hlds - head, cu = (size_t)160 * 1024;
-      if (head + 2 * env8 <= cu && 2 * hlds > cu) {      // sixteen envs per workgroup fit a CU, two workgroups of eight do not
-        const dim3 wgrid((sim->n + 15) / 16), wblock(512);
-        return sim_self(sim) ? launch(k_sim_step_pgs_wide<true>, wgrid, wblock, head + 2 * env8, stream, A)
-                             : launch(k_sim_step_pgs_wide<false>, wgrid, wblock, head + 2 * env8, stream, A);
-      }
-    }
-    if (sim->nboxes > 0) {
-      if (sim_link(sim)) return sim_self(sim) ? launch(k_sim_step<32, true, true, true, true>, hgrid, hblock, hlds, stream, A)
-                                              : launch(k_sim_step<32, true, false, true, true>, hgrid, hblock, hlds, stream, A);
-      return sim_self(sim) ? launch(k_sim_step<32, true, true, false, true>, hgrid, hblock, hlds, stream, A)
-                           : launch(k_sim_step<32, true, false, false, true>, hgrid, hblock, hlds, stream, A);
-    }
-    return sim_self(sim) ? launch(k_sim_step<32, false, true, false, true>, hgrid, hblock, hlds, stream, A)
-                         : launch(k_sim_step<32, false, false, false, true>, hgrid, hblock, hlds, stream, A);
-  }
+  Plan P;
+  if (int r = sim_step_plan(sim, P)) return r;
   sim->force_armed = false;
   sim->force_at_pos = false;
-  const int epb = 256 / sim->group;
-  dim3 grid((sim->n + epb - 1) / epb), block(256);
-  if (sim->nboxes > 0) {
-    if (!sim->t[SHF_T_SCENE]) return fail("shf_sim_step: scene (box actors) not bound");
-    if (sim->model.nb + sim->nboxes > sim->group) return fail("shf_sim_step: bodies + boxes exceed the lane group");
-    const size_t lds = sim_lds_bytes(sim, 0, 0, true);
-    if (sim_link(sim)) {
-      // link contacts (ShfModel.link_collide): the run-time-shaped kernels with the candidate pass compiled in
-      if (sim_self(sim)) {
-        switch (sim->group) {
-          case 64: return launch(k_sim_step<64, true, true, true>, grid, block, lds, stream, A);
-          case 32: return launch(k_sim_step<32, true, true, true>, grid, block, lds, stream, A);
-          default: return launch(k_sim_step<16, true, true, true>, grid, block, lds, stream, A);
-        }
-      }
-      switch (sim->group) {
-        case 64: return launch(k_sim_step<64, true, false, true>, grid, block, lds, stream, A);
-        case 32: return launch(k_sim_step<32, true, false, true>, grid, block, lds, stream, A);
-        default: return launch(k_sim_step<16, true, false, true>, grid, block, lds, stream, A);
-      }
-    }
-    if (sim_self(sim)) {
-      switch (sim->group) {
-        case 64: return launch(k_sim_step<64, true, true>, grid, block, lds, stream, A);
-        case 32: return launch(k_sim_step<32, true, true>, grid, block, lds, stream, A);
-        default: return launch(k_sim_step<16, true, true>, grid, block, lds, stream, A);
-      }
-    }
-    switch (sim->group) {
-      case 64: return launch(k_sim_step<64, true, false>, grid, block, lds, stream, A);
-      case 32: return launch(k_sim_step<32, true, false>, grid, block, lds, stream, A);
-      default: return launch(k_sim_step<16, true, false>, grid, block, lds, stream, A);
-    }
-  }
-  const size_t lds = sim_lds_bytes(sim, 0, 0);
-  if (sim_self(sim)) {
-    switch (sim->group) {
-      case 64: return launch(k_sim_step<64, false, true>, grid, block, lds, stream, A);
-      case 32: return launch(k_sim_step<32, false, true>, grid, block, lds, stream, A);
-      default: return launch(k_sim_step<16, false, true>, grid, block, lds, stream, A);
-    }
-  }
-  switch (sim->group) {
-    case 64: return launch(k_sim_step<64, false, false>, grid, block, lds, stream, A);
-    case 32: return launch(k_sim_step<32, false, false>, grid, block, lds, stream, A);
-    default: return launch(k_sim_step<16, false, false>, grid, block, lds, stream, A);
-  }
+  return launch_ptr(P.fn, P.grid, P.block, P.lds, stream, A);
 }
 
 extern "C" int shf_sim_refresh(ShfSim* sim, int32_t mask, void* stream) {
@@ -592,7 +577,7 @@ extern "C" int shf_sim_refresh(ShfSim* sim, int32_t mask, void* stream) {
   if (bs || jac) {
     const int epb = 256 / sim->group;
     dim3 grid((sim->n + epb - 1) / epb), block(256);
-    const size_t lds = sim_lds_bytes(sim, 0, 0);
+    const size_t lds = sim_lds_bytes(sim, sim->group, 0, 0);
     const ShfModel* gm = (const ShfModel*)sim->t[SHF_T_MODEL];
     const float* dof = (const float*)sim->t[SHF_T_SIM_DOF];
     const float* root = (const float*)sim->t[SHF_T_SIM_ROOT];
@@ -779,69 +764,58 @@ static int a1_args(ShfA1Task* task, const float* raw_actions_dev, const char* wh
   return 0;
 }
 
-static int a1_step_launch(ShfA1Task* task, const float* raw_actions_dev, void* stream);
-extern "C" int shf_a1_step(ShfA1Task* task, const float* raw_actions_dev, void* stream) {
-  if (!raw_actions_dev) return fail("shf_a1_step: null actions");
-  return a1_step_launch(task, raw_actions_dev, stream);
-}
-extern "C" int shf_a1_step_random(ShfA1Task* task, void* stream) { return a1_step_launch(task, nullptr, stream); }
-static int a1_step_launch(ShfA1Task* task, const float* raw_actions_dev, void* stream) {
-  A1Args A;
-  if (int r = a1_args(task, raw_actions_dev, "shf_a1_step", A)) return r;
-  ShfSim* s = task->sim;
+// the fused A1 step's kernel
+static int a1_step_plan(const ShfA1Task* task, Plan& P) {
+  const ShfSim* s = task->sim;
   const int nobs = 12 + 2 * s->model.nd + s->model.nd * task->tp.num_history + task->tp.num_height_points;
-  const int epb = 256 / s->group;
-  dim3 grid((s->n + epb - 1) / epb), block(256);
-  const size_t lds = sim_lds_bytes(s, TASK_WORDS + STATS_LDS_WORDS, SCR_OBS + nobs);
-  int r;
+  const int g = s->group, n = s->n;
+  const bool self = sim_self(s), warped = s->terr.warped != 0;
   if (s->sp.solver != SHF_SOLVER_COMPLIANT) {
     // the velocity-level contact solve: the chain mapping at two envs per wavefront (csrc/shf_chain_hard.h)
     if (s->mapping != SHF_MAP_CHAIN || s->chain_group != 32 || !shf_a1_chain_matches(s->model))
       return fail("shf_a1_step: ShfSimParams.solver = SHF_SOLVER_PGS runs on the chain mapping at 32 lanes per env (shf_sim_set_mapping)");
     if (s->sp.max_contacts > shf_a1_chain_pgs_max_contacts()) return fail("shf_a1_step: the fused A1 step's solve holds at most 16 constraints per env (ShfSimParams.max_contacts)");
     if (s->sp.pos_iters < 1) return fail("shf_a1_step: ShfSimParams.pos_iters must be >= 1 with SHF_SOLVER_PGS");
-    return launch_ptr(shf_a1_chain_pgs_kernel(s->terr.warped != 0, sim_self(s), s->sp.max_contacts > HCK, s->sp.solver == SHF_SOLVER_TGS), dim3((s->n + 7) / 8), block, shf_a1_chain_lds_bytes(32, nobs, sim_self(s)), stream, A);
+    return set_plan(P, shf_a1_chain_pgs_kernel(warped, self, s->sp.max_contacts > HCK, s->sp.solver == SHF_SOLVER_TGS), n, 8, 256, shf_a1_chain_lds_bytes(32, nobs, self));
   }
   if (s->mapping == SHF_MAP_CHAIN) {
     if (!shf_a1_chain_matches(s->model)) return fail("shf_a1_step: the articulation does not fit the chain mapping");
-    const void* fn = shf_a1_chain_kernel(s->chain_group, s->terr.warped != 0, sim_self(s));
-    if (!fn) return fail(sim_self(s) ? "shf_a1_step: the chain mapping with self-collision runs at 32 lanes per env"
-                                     : "shf_a1_step: the chain mapping runs at 16 or 32 lanes per env");
-    const int cepb = 256 / s->chain_group;
-    return launch_ptr(fn, dim3((s->n + cepb - 1) / cepb), block, shf_a1_chain_lds_bytes(s->chain_group, nobs, sim_self(s)), stream, A);
+    const void* fn = shf_a1_chain_kernel(s->chain_group, warped, self);
+    if (!fn) return fail(self ? "shf_a1_step: the chain mapping with self-collision runs at 32 lanes per env"
+                              : "shf_a1_step: the chain mapping runs at 16 or 32 lanes per env");
+    return set_plan(P, fn, n, 256 / s->chain_group, 256, shf_a1_chain_lds_bytes(s->chain_group, nobs, self));
   }
-  if (s->terr.warped && s->group == 64)
+  if (warped && g == 64)
     return fail("shf_a1_step: a trimesh terrain needs 16 or 32 lanes per env (the 128-VGPR instantiation has no room for it)");
-  if (sim_self(s)) {
-    // self-collision: its own instantiations (the capped-VGPR default entry point stays as it is)
-    if (s->group == 64) return fail("shf_a1_step: self-collision needs 16 or 32 lanes per env (no register room in the 128-VGPR instantiation)");
-    if (A1Dims::matches(s->model)) {
-      if (s->group != 32) return fail("shf_a1_step: A1 has 17 bodies, the lane group must be 32 or 64");
-      return s->terr.warped ? launch(k_a1_step_self<32, A1Dims>, grid, block, lds, stream, A)
-                            : launch(k_a1_step_self_a1_g32, grid, block, lds, stream, A);
-    }
-    return s->group == 32 ? launch(k_a1_step_self<32, DynDims>, grid, block, lds, stream, A)
-                          : launch(k_a1_step_self<16, DynDims>, grid, block, lds, stream, A);
-  }
-  if (A1Dims::matches(s->model)) {
-    switch (s->group) {
-      case 64: r = launch(k_a1_step<64, A1Dims>, grid, block, lds, stream, A); break;
-      case 32:
-        // the capped-VGPR entry point is height-field only; a trimesh terrain takes the generic instantiation
-        r = s->terr.warped ? launch(k_a1_step<32, A1Dims>, grid, block, lds, stream, A)
-                           : launch(k_a1_step_a1_g32, grid, block, lds, stream, A);
-        break;
-      default: return fail("shf_a1_step: A1 has 17 bodies, the lane group must be 32 or 64");
-    }
-  } else {
-    switch (s->group) {
-      case 64: r = launch(k_a1_step<64, DynDims>, grid, block, lds, stream, A); break;
-      case 32: r = launch(k_a1_step<32, DynDims>, grid, block, lds, stream, A); break;
-      default: r = launch(k_a1_step<16, DynDims>, grid, block, lds, stream, A); break;
-    }
-  }
-  return r;
+  if (self && g == 64) return fail("shf_a1_step: self-collision needs 16 or 32 lanes per env (no register room in the 128-VGPR instantiation)");
+  const bool a1 = A1Dims::matches(s->model);
+  if (a1 && g == 16) return fail("shf_a1_step: A1 has 17 bodies, the lane group must be 32 or 64");
+  // the A1 at two envs per wavefront on a height field has capped-VGPR entry points of its own; a trimesh terrain takes the
+  // generic instantiation.  Self-collision: its own instantiations
+  const void* fn;
+  if (!a1) fn = self ? (g == 32 ? KFN(k_a1_step_self<32, DynDims>) : KFN(k_a1_step_self<16, DynDims>)) : PICK_LANES(g, k_a1_step, DynDims);
+  else if (self) fn = warped ? KFN(k_a1_step_self<32, A1Dims>) : KFN(k_a1_step_self_a1_g32);
+  else fn = g == 64 ? KFN(k_a1_step<64, A1Dims>) : warped ? KFN(k_a1_step<32, A1Dims>) : KFN(k_a1_step_a1_g32);
+  return set_plan(P, fn, n, 256 / g, 256, sim_lds_bytes(s, g, TASK_WORDS + STATS_LDS_WORDS, SCR_OBS + nobs));
 }
+extern "C" int shf_a1_step_plan(const ShfA1Task* task, ShfLaunchPlan* out) {
+  if (!task) return fail("shf_a1_step: null task");
+  if (!out) return fail("shf_a1_step_plan: null argument");
+  Plan P;
+  return export_plan(a1_step_plan(task, P), P, out);
+}
+static int a1_step_launch(ShfA1Task* task, const float* raw_actions_dev, void* stream) {
+  A1Args A;
+  if (int r = a1_args(task, raw_actions_dev, "shf_a1_step", A)) return r;
+  Plan P;
+  if (int r = a1_step_plan(task, P)) return r;
+  return launch_ptr(P.fn, P.grid, P.block, P.lds, stream, A);
+}
+extern "C" int shf_a1_step(ShfA1Task* task, const float* raw_actions_dev, void* stream) {
+  if (!raw_actions_dev) return fail("shf_a1_step: null actions");
+  return a1_step_launch(task, raw_actions_dev, stream);
+}
+extern "C" int shf_a1_step_random(ShfA1Task* task, void* stream) { return a1_step_launch(task, nullptr, stream); }
 
 extern "C" int shf_a1_reset_all(ShfA1Task* task, void* stream) {
   A1Args A;
@@ -913,7 +887,6 @@ static int abb_args(ShfAbbTask* task, const float* raw_actions_dev, const char* 
   for (int id = 0; id < SHF_ABB_COUNT; id++)
     if (!task->t[id]) return fail(std::string(who) + ": task tensor " + std::to_string(id) + " not bound");
   if (s->model.nhull > 0 && s->model.link_collide != 0 && !s->t[SHF_T_HULLS]) return fail(std::string(who) + ": the articulation's hulls (SHF_T_HULLS) are not bound");
-  if (s->model.nb + s->nboxes > s->group) return fail(std::string(who) + ": bodies + boxes exceed the lane group");
   A.S = sim_args(s, false);
   A.tp = (const ShfAbbTaskParams*)task->t[SHF_ABB_PARAMS];
   A.env_off = s->env_off;
@@ -934,151 +907,100 @@ static int abb_args(ShfAbbTask* task, const float* raw_actions_dev, const char* 
   return 0;
 }
 
-static int abb_step_launch(ShfAbbTask* task, const float* raw_actions_dev, void* stream);
+// The generic velocity-level step of config 5: sixteen envs per workgroup of 512 threads (k_abb_step_pgs_wide) where their LDS
+// fits one CU and eight would leave a CU to a single workgroup (the shipped scene with link contacts: 8.7 KB per env); else
+// eight per workgroup of 256 (the rod-only scene: two workgroups per CU).
+static bool abb_pgs_wide(const ShfSim* s) {
+  const size_t cu = (size_t)160 * 1024;
+  return abb_lds_bytes(s, 16, 0, true) <= cu && 2 * abb_lds_bytes(s, 8, 0, true) > cu;
+}
+// the fused ABB step's kernel
+static int abb_step_plan(const ShfAbbTask* task, Plan& P) {
+  const ShfSim* s = task->sim;
+  const bool hard = s->sp.solver != SHF_SOLVER_COMPLIANT, link = sim_link(s), chain = s->mapping == SHF_MAP_CHAIN, split = chain && s->mapping_split;
+  const int g = s->group, n = s->n, epb = 256 / g;
+  if (s->model.nb + s->nboxes > g) return fail("shf_abb_step: bodies + boxes exceed the lane group");
+  if (!sim_plain(s)) {
+    // a scene with ShfScene.flags or hulls: the run-time-shaped step with the convex narrow phase compiled in (csrc/shf_hull.h)
+    if (!link) return fail("shf_abb_step: scene flags / hulls need link contacts (ShfModel.link_collide)");
+    if (s->mapping != SHF_MAP_BODY) return fail("shf_abb_step: scene flags / hulls run on the body mapping (shf_sim_set_mapping(SHF_MAP_BODY))");
+    if (hard) {
+      if (s->sp.max_contacts > HCK || s->sp.pos_iters < 1) return fail("shf_abb_step: SHF_SOLVER_PGS needs pos_iters >= 1 and max_contacts <= 8");
+      if (s->model.nlevels > HG_LEV || s->model.nb + s->nboxes > 32) return fail("shf_abb_step: SHF_SOLVER_PGS: at most 8 tree levels and 32 bodies + box actors");
+      return set_plan(P, KFN(k_abb_step<32, DynDims, DynScene, true, 0, true, true>), n, 8, 256, abb_lds_bytes(s, 8, 0, true));
+    }
+    return set_plan(P, PICK_LANES(g, k_abb_step, DynDims, DynScene, true, 0, false, true), n, epb, 256, abb_lds_bytes(s, epb, ARM_TAIL, false));
+  }
+  if (hard) {
+    // the velocity-level contact solve: the run-time-shaped body-per-lane step at 32 lanes per env (csrc/shf_hard.h)
+    if (s->sp.max_contacts > HCK || s->sp.pos_iters < 1) return fail("shf_abb_step: SHF_SOLVER_PGS needs pos_iters >= 1 and max_contacts <= 8");
+    if (s->model.nlevels > HG_LEV || s->model.nb + s->nboxes > 32) return fail("shf_abb_step: SHF_SOLVER_PGS: at most 8 tree levels and 32 bodies + box actors");
+    if (split) {
+      // the shipped arm in the shipped scene: arm wave + box wave for the free solve and the candidates, the solve regrouped at 32
+      // lanes per env (k_abb_step_ws_hard): 512 threads = 16 envs per workgroup
+      if (!abb_shipped(s) || g != 16)
+        return fail("shf_abb_step: the split mapping under SHF_SOLVER_PGS / _TGS needs the shipped arm, the table / cube / pad scene and 16 "
+                    "lanes per env");
+      return set_plan(P, link ? KFN(k_abb_step_ws_hard<true>) : KFN(k_abb_step_ws_hard<false>), n, 16, 512, abb_lds_bytes(s, 16, ARM_TAIL + WS_LINK_STASH_WORDS, true));
+    }
+    if (abb_pgs_wide(s)) return set_plan(P, link ? KFN(k_abb_step_pgs_wide<true>) : KFN(k_abb_step_pgs_wide<false>), n, 16, 512, abb_lds_bytes(s, 16, 0, true));
+    return set_plan(P, link ? KFN(k_abb_step<32, DynDims, DynScene, true, 0, true>) : KFN(k_abb_step<32, DynDims, DynScene, false, 0, true>), n, 8, 256,
+                    abb_lds_bytes(s, 8, 0, true));
+  }
+  const size_t lds = abb_lds_bytes(s, epb, ARM_TAIL, false);
+  const bool scene = AbbScene::matches(s->nboxes, s->boxes, s->model.nsph);
+  if (link && split) {
+    // arm wave + box wave with the link contacts on the box wave: 512 threads = 16 envs per workgroup
+    if (!abb_shipped(s) || g != 16)
+      return fail("shf_abb_step: the split mapping with link contacts needs the shipped arm (59 sample points), the table / cube / pad "
+                  "scene and 16 lanes per env");
+    return set_plan(P, KFN(k_abb_step_ws<512, true>), n, 16, 512, abb_lds_bytes(s, 16, ARM_TAIL + WS_LINK_STASH_WORDS, false));
+  }
+  // the shipped arm with its link volumes in the shipped scene: compile-time loop bounds, ballot-driven folds
+  if (link && !chain && AbbLinkDims::matches(s->model) && scene) return set_plan(P, PICK_LANES(g, k_abb_step, AbbLinkDims, AbbScene, true), n, epb, 256, lds);
+  if (link && chain)
+    return fail("shf_abb_step: the chain mapping (arm recursions on one lane) is compiled without link contacts -- with link contacts use "
+                "the split mapping (shf_sim_set_mapping(SHF_MAP_CHAIN_SPLIT), 16 lanes) or the body mapping");
+  if (link) return set_plan(P, PICK_LANES(g, k_abb_step, DynDims, DynScene, true), n, epb, 256, lds);
+  if (chain) {
+    // the arm's recursions on one lane (shf_arm.h): compiled for the shipped arm in the shipped scene only
+    if (!abb_shipped(s) || g == 64)
+      return fail("shf_abb_step: the chain mapping needs the 6-link arm with 3 sample points and one capsule, the table / cube / pad "
+                  "scene, no link contacts, and 16 or 32 lanes per env");
+    if (split && g != 16) return fail("shf_abb_step: the split chain mapping runs at 16 lanes per env");
+    // split: arm and boxes on different waves of the workgroup (k_abb_step_ws): 256 threads = 8 envs per block
+    if (split) return set_plan(P, KFN(k_abb_step_ws<256>), n, 8, 256, abb_lds_bytes(s, 8, ARM_TAIL, false));
+    return set_plan(P, g == 32 ? KFN(k_abb_step<32, AbbDims, AbbScene, false, 6>) : KFN(k_abb_step<16, AbbDims, AbbScene, false, 6>), n, epb, 256, lds);
+  }
+  if (AbbDims::matches(s->model) && scene) return set_plan(P, PICK_LANES(g, k_abb_step, AbbDims, AbbScene), n, epb, 256, lds);
+  return set_plan(P, PICK_LANES(g, k_abb_step, DynDims, DynScene), n, epb, 256, lds);
+}
+extern "C" int shf_abb_step_plan(const ShfAbbTask* task, ShfLaunchPlan* out) {
+  if (!task) return fail("shf_abb_step: null task");
+  if (!out) return fail("shf_abb_step_plan: null argument");
+  Plan P;
+  return export_plan(abb_step_plan(task, P), P, out);
+}
+extern "C" int shf_abb_step_pgs_is_wide(const ShfAbbTask* task) {
+  Plan P;
+  return (task && !abb_step_plan(task, P) && (P.fn == KFN(k_abb_step_pgs_wide<true>) || P.fn == KFN(k_abb_step_pgs_wide<false>))) ? 1 : 0;
+}
+static int abb_step_launch(ShfAbbTask* task, const float* raw_actions_dev, void* stream) {
+  AbbArgs A;
+  if (int r = abb_args(task, raw_actions_dev, "shf_abb_step", A)) return r;
+  Plan P;
+  if (int r = abb_step_plan(task, P)) return r;
+  return launch_ptr(P.fn, P.grid, P.block, P.lds, stream, A);
+}
 extern "C" int shf_abb_step(ShfAbbTask* task, const float* raw_actions_dev, void* stream) {
   if (!raw_actions_dev) return fail("shf_abb_step: null actions");
   return abb_step_launch(task, raw_actions_dev, stream);
 }
 extern "C" int shf_abb_step_random(ShfAbbTask* task, void* stream) { return abb_step_launch(task, nullptr, stream); }
-// The generic velocity-level step of config 5: sixteen envs per workgroup of 512 threads (k_abb_step_pgs_wide) where their LDS
-// fits one CU and eight would leave a CU to a single workgroup (the shipped scene with link contacts: 8.7 KB per env); else
-// eight per workgroup of 256 (the rod-only scene: two workgroups per CU).
-static bool abb_pgs_wide(const ShfSim* s, size_t* env_bytes, size_t* head_bytes) {
-  const int nbx = s->nboxes;
-  const int nslots = hard_total_slots(s->model.np + box_slot_count(nbx, sim_ndyn(s), s->model.nsph) + (sim_link(s) ? 2 * SHF_MAX_LINK_CONTACTS : 0), sim_link(s));
-  *env_bytes = (size_t)env_lds_words(s->model.nb + nbx, s->model.nd, nslots, ABB_TAIL_WORDS_NOARM(nslots, s->model.nd), 1 + nbx) * 4;
-  *head_bytes = ((size_t)MODEL_WORDS + SCENE_WORDS + ABB_WORDS + STATS_LDS_WORDS) * 4;
-  const size_t cu = (size_t)160 * 1024;
-  return *head_bytes + 16 * *env_bytes <= cu && 2 * (*head_bytes + 8 * *env_bytes) > cu;
-}
-extern "C" int shf_abb_step_pgs_is_wide(const ShfAbbTask* task) {
-  if (!task || !task->sim || task->sim->sp.solver == SHF_SOLVER_COMPLIANT) return 0;
-  size_t a, b;
-  return abb_pgs_wide(task->sim, &a, &b) ? 1 : 0;
-}
-static int abb_step_launch(ShfAbbTask* task, const float* raw_actions_dev, void* stream) {
-  AbbArgs A;
-  if (int r = abb_args(task, raw_actions_dev, "shf_abb_step", A)) return r;
-  ShfSim* s = task->sim;
-  if (!sim_plain(s)) {
-    // a scene with ShfScene.flags or hulls: the run-time-shaped step with the convex narrow phase compiled in (csrc/shf_hull.h)
-    if (!sim_link(s)) return fail("shf_abb_step: scene flags / hulls need link contacts (ShfModel.link_collide)");
-    if (s->mapping != SHF_MAP_BODY) return fail("shf_abb_step: scene flags / hulls run on the body mapping (shf_sim_set_mapping(SHF_MAP_BODY))");
-    if (s->sp.solver != SHF_SOLVER_COMPLIANT) {
-      if (s->sp.max_contacts > HCK || s->sp.pos_iters < 1) return fail("shf_abb_step: SHF_SOLVER_PGS needs pos_iters >= 1 and max_contacts <= 8");
-      if (s->model.nlevels > HG_LEV || s->model.nb + s->nboxes > 32) return fail("shf_abb_step: SHF_SOLVER_PGS: at most 8 tree levels and 32 bodies + box actors");
-      size_t env_bytes, head_bytes;
-      abb_pgs_wide(s, &env_bytes, &head_bytes);
-      return launch(k_abb_step<32, DynDims, DynScene, true, 0, true, true>, dim3((s->n + 7) / 8), dim3(256), head_bytes + 8 * env_bytes, stream, A);
-    }
-    const int epbx = 256 / s->group;
-    const dim3 gridx((s->n + epbx - 1) / epbx), blockx(256);
-    const int nbxx = s->nboxes, nslotsx = s->model.np + box_slot_count(nbxx, sim_ndyn(s), s->model.nsph) + 2 * SHF_MAX_LINK_CONTACTS;
-    const size_t ldsx = ((size_t)MODEL_WORDS + SCENE_WORDS + ABB_WORDS + STATS_LDS_WORDS +
-                         (size_t)epbx * env_lds_words(s->model.nb + nbxx, s->model.nd, nslotsx, ABB_TAIL_WORDS(nslotsx, s->model.nd), 1 + nbxx)) * 4;
-    switch (s->group) {
-      case 64: return launch(k_abb_step<64, DynDims, DynScene, true, 0, false, true>, gridx, blockx, ldsx, stream, A);
-      case 32: return launch(k_abb_step<32, DynDims, DynScene, true, 0, false, true>, gridx, blockx, ldsx, stream, A);
-      default: return launch(k_abb_step<16, DynDims, DynScene, true, 0, false, true>, gridx, blockx, ldsx, stream, A);
-    }
-  }
-  if (s->sp.solver != SHF_SOLVER_COMPLIANT) {
-    // the velocity-level contact solve: the run-time-shaped body-per-lane step at 32 lanes per env (csrc/shf_hard.h)
-    if (s->sp.max_contacts > HCK || s->sp.pos_iters < 1) return fail("shf_abb_step: SHF_SOLVER_PGS needs pos_iters >= 1 and max_contacts <= 8");
-    if (s->model.nlevels > HG_LEV || s->model.nb + s->nboxes > 32) return fail("shf_abb_step: SHF_SOLVER_PGS: at most 8 tree levels and 32 bodies + box actors");
-    if (s->mapping == SHF_MAP_CHAIN && s->mapping_split) {
-      // the shipped arm in the shipped scene: arm wave + box wave for the free solve and the candidates, the solve regrouped at 32
-      // lanes per env (k_abb_step_ws_hard): 512 threads = 16 envs per workgroup
-      const bool link = sim_link(s);
-      if (!ArmChain<6>::matches(s->model) || !(link ? AbbLinkDims::matches(s->model) : AbbDims::matches(s->model)) ||
-          !AbbScene::matches(s->nboxes, s->boxes, s->model.nsph) || s->group != 16)
-        return fail("shf_abb_step: the split mapping under SHF_SOLVER_PGS / _TGS needs the shipped arm, the table / cube / pad scene and 16 "
-                    "lanes per env");
-      const int nbx = s->nboxes, wepb = 16;
-      const int nslots = hard_total_slots(s->model.np + box_slot_count(nbx, sim_ndyn(s), s->model.nsph) + (link ? 2 * SHF_MAX_LINK_CONTACTS : 0), link);
-      const size_t wlds = ((size_t)MODEL_WORDS + SCENE_WORDS + ABB_WORDS + STATS_LDS_WORDS +
-                           (size_t)wepb * env_lds_words(s->model.nb + nbx, s->model.nd, nslots, ABB_TAIL_WORDS(nslots, s->model.nd) + WS_LINK_STASH_WORDS, 1 + nbx)) * 4;
-      const dim3 wgrid((s->n + wepb - 1) / wepb), wblock(512);
-      return link ? launch(k_abb_step_ws_hard<true>, wgrid, wblock, wlds, stream, A) : launch(k_abb_step_ws_hard<false>, wgrid, wblock, wlds, stream, A);
-    }
-    size_t env_bytes, head_bytes;
-    if (abb_pgs_wide(s, &env_bytes, &head_bytes)) {
-      const dim3 wgrid((s->n + 15) / 16), wblock(512);
-      return sim_link(s) ? launch(k_abb_step_pgs_wide<true>, wgrid, wblock, head_bytes + 16 * env_bytes, stream, A)
-                         : launch(k_abb_step_pgs_wide<false>, wgrid, wblock, head_bytes + 16 * env_bytes, stream, A);
-    }
-    const size_t lds = head_bytes + 8 * env_bytes;
-    const dim3 hgrid((s->n + 7) / 8), hblock(256);
-    return sim_link(s) ? launch(k_abb_step<32, DynDims, DynScene, true, 0, true>, hgrid, hblock, lds, stream, A)
-                       : launch(k_abb_step<32, DynDims, DynScene, false, 0, true>, hgrid, hblock, lds, stream, A);
-  }
-  const int epb = 256 / s->group;
-  dim3 grid((s->n + epb - 1) / epb), block(256);
-  const int nbx = s->nboxes, nslots = s->model.np + box_slot_count(nbx, sim_ndyn(s), s->model.nsph) + (sim_link(s) ? 2 * SHF_MAX_LINK_CONTACTS : 0);
-  const size_t lds = ((size_t)MODEL_WORDS + SCENE_WORDS + ABB_WORDS + STATS_LDS_WORDS +
-                      (size_t)epb * env_lds_words(s->model.nb + nbx, s->model.nd, nslots, ABB_TAIL_WORDS(nslots, s->model.nd), 1 + nbx)) * 4;
-  if (sim_link(s) && s->mapping == SHF_MAP_CHAIN && s->mapping_split) {
-    // arm wave + box wave with the link contacts on the box wave: 512 threads = 16 envs per workgroup
-    if (!ArmChain<6>::matches(s->model) || !AbbLinkDims::matches(s->model) || !(sim_plain(s) && AbbScene::matches(s->nboxes, s->boxes, s->model.nsph)) || s->group != 16)
-      return fail("shf_abb_step: the split mapping with link contacts needs the shipped arm (59 sample points), the table / cube / pad "
-                  "scene and 16 lanes per env");
-    const int wt = 512, wepb = wt / 32;
-    const size_t wlds = ((size_t)MODEL_WORDS + SCENE_WORDS + ABB_WORDS + STATS_LDS_WORDS +
-                         (size_t)wepb * env_lds_words(s->model.nb + nbx, s->model.nd, nslots, ABB_TAIL_WORDS(nslots, s->model.nd) + WS_LINK_STASH_WORDS, 1 + nbx)) * 4;
-    return launch(k_abb_step_ws<512, true>, dim3((s->n + wepb - 1) / wepb), dim3(wt), wlds, stream, A);
-  }
-  if (sim_link(s) && s->mapping != SHF_MAP_CHAIN && AbbLinkDims::matches(s->model) && (sim_plain(s) && AbbScene::matches(s->nboxes, s->boxes, s->model.nsph))) {
-    // the shipped arm with its link volumes in the shipped scene: compile-time loop bounds, ballot-driven folds
-    switch (s->group) {
-      case 64: return launch(k_abb_step<64, AbbLinkDims, AbbScene, true>, grid, block, lds, stream, A);
-      case 32: return launch(k_abb_step<32, AbbLinkDims, AbbScene, true>, grid, block, lds, stream, A);
-      default: return launch(k_abb_step<16, AbbLinkDims, AbbScene, true>, grid, block, lds, stream, A);
-    }
-  }
-  if (sim_link(s) && s->mapping == SHF_MAP_CHAIN)
-    return fail("shf_abb_step: the chain mapping (arm recursions on one lane) is compiled without link contacts -- with link contacts use "
-                "the split mapping (shf_sim_set_mapping(SHF_MAP_CHAIN_SPLIT), 16 lanes) or the body mapping");
-  if (sim_link(s)) {
-    switch (s->group) {
-      case 64: return launch(k_abb_step<64, DynDims, DynScene, true>, grid, block, lds, stream, A);
-      case 32: return launch(k_abb_step<32, DynDims, DynScene, true>, grid, block, lds, stream, A);
-      default: return launch(k_abb_step<16, DynDims, DynScene, true>, grid, block, lds, stream, A);
-    }
-  }
-  if (s->mapping == SHF_MAP_CHAIN) {
-    // the arm's recursions on one lane (shf_arm.h): compiled for the shipped arm in the shipped scene only
-    if (sim_link(s) || !ArmChain<6>::matches(s->model) || !AbbDims::matches(s->model) ||
-        !(sim_plain(s) && AbbScene::matches(s->nboxes, s->boxes, s->model.nsph)) || s->group == 64)
-      return fail("shf_abb_step: the chain mapping needs the 6-link arm with 3 sample points and one capsule, the table / cube / pad "
-                  "scene, no link contacts, and 16 or 32 lanes per env");
-    if (s->mapping_split && s->group != 16) return fail("shf_abb_step: the split chain mapping runs at 16 lanes per env");
-    if (s->group == 16 && s->mapping_split) {
-      // arm and boxes on different waves of the workgroup (k_abb_step_ws): WT / 32 envs per block
-      const int wt = s->mapping_split, wepb = wt / 32;
-      const size_t wlds = ((size_t)MODEL_WORDS + SCENE_WORDS + ABB_WORDS + STATS_LDS_WORDS +
-                           (size_t)wepb * env_lds_words(s->model.nb + nbx, s->model.nd, nslots, ABB_TAIL_WORDS(nslots, s->model.nd), 1 + nbx)) * 4;
-      const dim3 wgrid((s->n + wepb - 1) / wepb);
-      return launch(k_abb_step_ws<256>, wgrid, dim3(wt), wlds, stream, A);
-    }
-    return s->group == 32 ? launch(k_abb_step<32, AbbDims, AbbScene, false, 6>, grid, block, lds, stream, A)
-                          : launch(k_abb_step<16, AbbDims, AbbScene, false, 6>, grid, block, lds, stream, A);
-  }
-  if (AbbDims::matches(s->model) && (sim_plain(s) && AbbScene::matches(s->nboxes, s->boxes, s->model.nsph))) {
-    switch (s->group) {
-      case 64: return launch(k_abb_step<64, AbbDims, AbbScene>, grid, block, lds, stream, A);
-      case 32: return launch(k_abb_step<32, AbbDims, AbbScene>, grid, block, lds, stream, A);
-      default: return launch(k_abb_step<16, AbbDims, AbbScene>, grid, block, lds, stream, A);
-    }
-  }
-  switch (s->group) {
-    case 64: return launch(k_abb_step<64, DynDims, DynScene>, grid, block, lds, stream, A);
-    case 32: return launch(k_abb_step<32, DynDims, DynScene>, grid, block, lds, stream, A);
-    default: return launch(k_abb_step<16, DynDims, DynScene>, grid, block, lds, stream, A);
-  }
-}
 extern "C" int shf_abb_reset_all(ShfAbbTask* task, void* stream) {
   AbbArgs A;
   if (int r = abb_args(task, nullptr, "shf_abb_reset_all", A)) return r;
+  if (task->sim->model.nb + task->sim->nboxes > task->sim->group) return fail("shf_abb_reset_all: bodies + boxes exceed the lane group");
   return launch(k_abb_reset_all, dim3((A.S.n + 127) / 128), dim3(128), 0, stream, A);
 }
 

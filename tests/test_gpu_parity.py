@@ -964,7 +964,8 @@ def test_fused_abb_step_matches_oracle_bitwise(oracle, group, generic):
                       solver="compliant")       # (the kernel forms of the compliant law; the velocity-level solve has its own tests)
     assert env.mapping == ("split" if (split or link_split) else "chain" if (not generic and not link and not levels and group < 64) else "body")
     assert ("FixedDims" in env.task.kernel_symbol() or split or link_split) != bool(generic)
-    assert ("Lb1ELi0ELb0ELb0EE" in env.task.kernel_symbol()) == (link and not generic and not link_split)
+    # (the compile-time-shaped link kernel by its whole name: the run-time-shaped one ends in the same template arguments)
+    assert ("9FixedDimsILi7ELi6ELi59ELi6ELi6EE10FixedSceneILi3ELi1ELi2EELb1ELi0ELb0ELb0EE" in env.task.kernel_symbol()) == (link and not generic and not link_split)
     assert env.task.kernel_symbol().endswith("Li6ELb0ELb0EE") == (env.mapping == "chain")
     env.task.tensors[_abi.ABB_EP_LEN].copy_(torch.randint(0, 200, (n,)))   # staggered time-outs
     torch.cuda.synchronize()

@@ -234,21 +234,32 @@ DEV void chain_hard_apply(const ShfModel* m, const ChainLds& L, float* tail, int
   float ucl[NQ][NLK];
   if (ischain) {
     float pl[NQ][6];
+    // the chain's link records and its links' exchange words, all reads in flight together: one LDS round trip for the pass
+    // instead of one per link behind the link before
+    HardLink Lc[NLK];
+    hard_links_load<CD>(L, CD::body(ci, 0), Lc);
+    float ox[NLK][NQ][6];
+#pragma unroll
+    for (int k = 0; k < NLK; k++)
+#pragma unroll
+      for (int q = 0; q < NQ; q++)
+#pragma unroll
+        for (int j = 0; j < 6; j++) ox[k][q][j] = L.xch[(ci * NLK + k) * XCH_STRIDE + (q == 0 ? 21 : 8) + j];
 #pragma unroll
     for (int k = NLK - 1; k >= 0; k--) {
       const int li = ci * NLK + k;
-      const float* o = L.xch + li * XCH_STRIDE;
-      const HardLink Lk = hard_link_load(L.jrec + li * JREC_STRIDE);
+      const float (*o)[6] = ox[k];
+      const HardLink& Lk = Lc[k];
       const float* S = Lk.S; const float* U = Lk.U;
       const float invD = Lk.invD;
 #pragma unroll
       for (int q = 0; q < NQ; q++) {
         if (k == NLK - 1) {
 #pragma unroll
-          for (int j = 0; j < 6; j++) pl[q][j] = o[(q == 0 ? 21 : 8) + j];
+          for (int j = 0; j < 6; j++) pl[q][j] = o[q][j];
         } else {
 #pragma unroll
-          for (int j = 0; j < 6; j++) pl[q][j] = o[(q == 0 ? 21 : 8) + j] + pl[q][j];
+          for (int j = 0; j < 6; j++) pl[q][j] = o[q][j] + pl[q][j];
         }
         float sp = S[0] * pl[q][0];
 #pragma unroll
@@ -288,10 +299,12 @@ DEV void chain_hard_apply(const ShfModel* m, const ChainLds& L, float* tail, int
     for (int q = 0; q < NQ; q++)
 #pragma unroll
       for (int j = 0; j < 6; j++) ac[q][j] = L.acc[6 * q + j];
+    HardLink Lc[NLK];      // (read together again: held across the two barriers they would cost registers in every lane)
+    hard_links_load<CD>(L, CD::body(ci, 0), Lc);
 #pragma unroll
     for (int k = 0; k < NLK; k++) {
       const int li = ci * NLK + k;
-      const HardLink Lk = hard_link_load(L.jrec + li * JREC_STRIDE);
+      const HardLink& Lk = Lc[k];
       const float* S = Lk.S; const float* U = Lk.U;
       const float invD = Lk.invD;
 #pragma unroll
@@ -895,18 +908,19 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
     const unsigned long long ownm = __ballot(own);      // (bit c: c < K of env A, bit 32 + c: of env B)
     // KC = 8: one visit of the sweep, contact c a constant (oracle: hard_solve, sweeps).  The sweep is eight of them unrolled:
     // no loop counter, no lane index in a register, W's block (l, c) at a fixed offset.  Per visit one wave-uniform branch (the
-    // skip rule) and one more only when contact c of one of the two envs slides; the committing lanes take the update by selects,
-    // and DPP moves broadcast the change of the impulse.
-    auto visit8 = [&](auto cc, float tg, const float* Wb) {
+    // skip rule) and one more only when contact c of one of the two envs slides; the committing lanes take the update by selects
+    // on lane masks (hard_take), and DPP moves broadcast the change of the impulse.
+    // pnz: the lanes whose impulse is not zero, as a lane mask taken once at the top of the sweep.  Visit c reads
+    // only its bits c and 32 + c, and lane c's impulse is written by visit c alone: when visit c runs, its bits still say what
+    // the impulse is.  (The impulses carry over from the last position sweep to the first velocity sweep unchanged.)
+    auto visit8 = [&](auto cc, float tg, unsigned long long pnz, const float* Wb) {
       constexpr int c = decltype(cc)::value;
       constexpr unsigned long long lanes_c = (1ull << c) | (1ull << (32 + c));       // lane c of each env
       // an open, unloaded contact whose normal velocity keeps it open asks for nothing (oracle: the same test): when that
       // is so for contact c of both envs of the wavefront the visit is skipped.  The test as a lane mask -- !(p0 == 0 && p1 == 0
-      // && p2 == 0 && !(u0 < tg)), a ballot per compare -- and the committing lanes as its bits c and 32 + c
-      const unsigned long long act = __ballot(O.p[0] != 0.0f) | __ballot(O.p[1] != 0.0f) | __ballot(O.p[2] != 0.0f) | __ballot(O.u[0] < tg);
-      const unsigned long long cm = act & ownm & lanes_c;
-      if (cm == 0ull) return;
-      const bool commit = __builtin_amdgcn_inverse_ballot_w64(cm);      // l == c && c < K && act
+      // && p2 == 0 && !(u0 < tg)) -- and the committing lanes as its bits c and 32 + c
+      const unsigned long long cm = (pnz | __ballot(O.u[0] < tg)) & ownm & lanes_c;
+      if (cm == 0ull) return;      // (cm: l == c && c < K && act)
       // every owner lane computes its own update; lane c's is the one that counts
       const float pn0 = O.p[0];
       const float pn = rmaxf(fmaf(-(O.u[0] - tg), O.iwnn, pn0), 0.0f);
@@ -915,22 +929,37 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
       float ps1 = O.p[1] - fmaf(O.Ti[1], ut2, O.Ti[0] * ut1), ps2 = O.p[2] - fmaf(O.Ti[2], ut2, O.Ti[1] * ut1);
       const float lim = O.mu * pn, lim2 = lim * lim;
       // the sliding step: the wavefront runs it only when contact c of one of its envs really slides; on the other lanes its
-      // result is not selected (and on the owner lanes other than c it is discarded below)
+      // result is not selected (and on the owner lanes other than c it is discarded below).  Inside it every lane computes the
+      // scale and selects it (no second branch around rsqrt_spec: the lanes that do not take the scale discard it anyway)
       const bool slide = fmaf(ps2, ps2, ps1 * ps1) > lim2;
       if ((cm & __ballot(slide)) != 0ull) {
         float q1 = fmaf(-O.rt, ut1, O.p[1]), q2 = fmaf(-O.rt, ut2, O.p[2]);
         const float nt2 = fmaf(q2, q2, q1 * q1);
-        const float sc1 = nt2 > rmaxf(lim2, 1e-30f) ? lim * rsqrt_spec(nt2) : 1.0f;   // (1e-30: a subnormal |p_t|^2 over a zero cone would make 0 * inf)
+        const float rs = lim * rsqrt_spec(nt2);
+        const float sc1 = nt2 > rmaxf(lim2, 1e-30f) ? rs : 1.0f;   // (1e-30: a subnormal |p_t|^2 over a zero cone would make 0 * inf)
         q1 *= sc1; q2 *= sc1;
         ps1 = slide ? q1 : ps1; ps2 = slide ? q2 : ps2;
       }
-      // the change is new - old: pn - pn0 = dn on the committing lane, exactly 0 on the others
-      const float n0 = commit ? pn : O.p[0], n1 = commit ? ps1 : O.p[1], n2 = commit ? ps2 : O.p[2];
-      const float dp0 = n0 - O.p[0], dp1 = n1 - O.p[1], dp2 = n2 - O.p[2];
-      O.p[0] = n0; O.p[1] = n1; O.p[2] = n2;
-      // the change of contact c's impulse, from its owner lane (lane c of each env: wave lanes c and 32 + c) to the owner lanes
-      const float b0 = hard_row_bcast<c>(dp0), b1 = hard_row_bcast<c>(dp1), b2 = hard_row_bcast<c>(dp2);
-      const bool take = own && c < K;
+      // The committing lanes take the new impulse in place.  What is broadcast from contact c's owner lane (lane c of each env:
+      // wave lanes c and 32 + c) is its change, pn - pn0 = dn, ... as that lane computed it
+      float d0 = dn, d1 = ps1 - O.p[1], d2 = ps2 - O.p[2];
+      bool take;
+      if constexpr (TGS) {
+        // ... as it stands, and only the lanes of the envs whose contact c commits take it (bit c of cm: env A's half of the
+        // wavefront, bit 32 + c: env B's).  The other env's lanes keep u bit for bit -- its -0.0 too, and W's blocks of the columns
+        // c >= K are uninitialised LDS.  (A committing env has c < K; its lanes l >= K own nothing, and nothing reads their u.)
+        const unsigned ca = (unsigned)cm, cb = (unsigned)(cm >> 32);
+        const unsigned ta = (unsigned)((int)(ca << (31 - c)) >> 31), tb = (unsigned)((int)(cb << (31 - c)) >> 31);
+        take = __builtin_amdgcn_inverse_ballot_w64((unsigned long long)ta | ((unsigned long long)tb << 32));
+      } else {
+        // ... or exactly 0 from a lane that does not commit, to the owner lanes.  (PGS: gated as above, k_a1_chain_pgs<0,0> is
+        // left with 68 B of scratch that no instruction touches -- over build.py's budget all the same.)
+        const bool commit = __builtin_amdgcn_inverse_ballot_w64(cm);
+        d0 = commit ? d0 : 0.0f; d1 = commit ? d1 : 0.0f; d2 = commit ? d2 : 0.0f;
+        take = own && c < K;
+      }
+      hard_take(O.p[0], pn, cm); hard_take(O.p[1], ps1, cm); hard_take(O.p[2], ps2, cm);
+      const float b0 = hard_row_bcast<c>(d0), b1 = hard_row_bcast<c>(d1), b2 = hard_row_bcast<c>(d2);
 #pragma unroll
       for (int r = 0; r < 3; r++) {
         const float ur = fmaf(Wb[3 * r + 2], b2, fmaf(Wb[3 * r + 1], b1, fmaf(Wb[3 * r], b0, O.u[r])));
@@ -1007,13 +1036,17 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
           // read while visit c runs (W holds all KC x KC blocks: reading the one after the last visit is harmless)
           float Wb[KC][9];
           if constexpr (WR == 0) wload8(0, Wb[0]);
+          const unsigned long long pnz = __ballot(O.p[0] != 0.0f) | __ballot(O.p[1] != 0.0f) | __ballot(O.p[2] != 0.0f);
           hard_static_while<0, KC>([&](auto cc) {
             constexpr int c = decltype(cc)::value;
             if (c >= Kw) return false;
             if constexpr (c + 1 < KC && c + 1 >= WR) wload8(c + 1, Wb[c + 1]);
-            if constexpr (c < WR) visit8(cc, tg, Wrow[c]); else visit8(cc, tg, Wb[c]);
+            if constexpr (c < WR) visit8(cc, tg, pnz, Wrow[c]); else visit8(cc, tg, pnz, Wb[c]);
             return true;
           });
+          // (TGS: the impulses leave the sweep in the registers the visits keep them in -- without this every visit ends with
+          // copies of two of them, for the sums below.  The PGS forms have no such copies)
+          if constexpr (TGS) asm volatile("" : "+v"(O.p[0]), "+v"(O.p[1]), "+v"(O.p[2]));
         }
         if constexpr (TGS) {
           if (phase == 0) {

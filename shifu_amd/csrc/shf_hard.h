@@ -70,6 +70,12 @@ DEV float hard_row_bcast(float x) {
   static_assert(c >= 0 && c < 16, "row_newbcast selects a lane of a row of 16");
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), 0x150 + c, 0xf, 0xf, true));
 }
+// x = a on the lanes of the mask, in place: one v_cndmask that takes the lane mask from an SGPR pair.  (Written as a select the
+// compiler is free to turn three of them on one condition into an exec-masked block of moves, or to select into a new
+// register and copy it back.)
+DEV void hard_take(float& x, float a, unsigned long long lanes) {
+  asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(x) : "v"(a), "s"(lanes));
+}
 // hard_static_while<C, N>(f): f(HardIdx<C>()), .. f(HardIdx<N - 1>()) while f returns true -- an unrolled loop whose index is a
 // constant expression in every copy, each copy nested in the one before (what one copy computes is there for the next, no copies)
 template <int N>

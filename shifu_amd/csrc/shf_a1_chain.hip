@@ -118,4 +118,13 @@ int shf_a1_chain_phase_cycles(unsigned long long* out, int n, int reset) {
   }
   return 0;
 }
+// the wavefronts' rows (PHASE_NW x 48)
+int shf_a1_chain_phase_waves(unsigned long long* out, int reset) {
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase_wave), sizeof(g_phase_wave)) != hipSuccess) return 1;
+  if (reset) {
+    void* p = nullptr;
+    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_phase_wave)) != hipSuccess || hipMemset(p, 0, sizeof(g_phase_wave)) != hipSuccess) return 1;
+  }
+  return 0;
+}
 #endif

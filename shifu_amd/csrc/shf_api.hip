@@ -71,6 +71,7 @@ const void* shf_sim_step_chain_pgs_kernel(bool warped, bool self, bool k16, bool
 size_t shf_sim_step_chain_pgs_lds_bytes(bool self);
 #ifdef SHF_PHASE_CLOCK
 int shf_a1_chain_phase_cycles(unsigned long long* out, int n, int reset);
+int shf_a1_chain_phase_waves(unsigned long long* out, int reset);
 #endif
 
 extern "C" const char* shf_last_error(void) { return g_err.c_str(); }
@@ -1020,4 +1021,7 @@ extern "C" int shf_debug_phase_cycles(unsigned long long* out, int n, int clear)
   for (int i = 0; i < n && i < 48; i++) out[i] += ch[i];
   return 0;
 }
+// ... and the per-wavefront rows of the chain-mapped kernels (PHASE_NW x 48 words; out holds as many)
+extern "C" int shf_debug_phase_nwaves(void) { return PHASE_NW; }
+extern "C" int shf_debug_phase_waves(unsigned long long* out, int clear) { return shf_a1_chain_phase_waves(out, clear) != 0 ? -1 : 0; }
 #endif

@@ -177,21 +177,38 @@ DEV HardTarget hard_target_load(const float* h) {
   return t;
 }
 
-// H4: the impulses in the constraint records as forces on their bodies -> what they add to the accelerations.  Both
-// impulse sets in one pass through the tree: q = 0 the impulses after the position iterations (HC_P), q = 1 after the
-// velocity iterations (HC_PV; NQ = 1: there are none) -- joint accelerations to dofb[.][2 + q], the root's to ac0[q]
-// (root lane).  Per set the operations of the oracle's hc_apply.
-template <class CD, int NQ, int KC>
-DEV void chain_hard_apply(const ShfModel* m, const ChainLds& L, float* tail, int l, int K, float idt, bool isbody_h0, bool islink, bool isroot,
-                          bool ischain, int ci, int lb, int myb, float (*ac0)[6]) {
-  constexpr int NCH = CD::NCH, NLK = CD::NLK;
+// H4: the impulses in the constraint records as forces on their bodies -> what they add to the accelerations: set 0 the
+// impulses after the position iterations (HC_P), set 1 after the velocity iterations (HC_PV; NQ = 1: there are none) -- joint
+// accelerations to dofb[.][2 + set], the root's to ac0[set] (root lane).  Per set the operations of the oracle's hc_apply.
+//   !SPLIT  both sets in one pass through the tree on the same lanes: body lanes of half 0, the chain lanes, the root lane.
+//   SPLIT   (NQ = 2) set q on half q of the env's lanes: a wavefront issues an instruction in the same time whatever lanes are
+//           active, so the second set rides on lanes that stood idle.  Lane lb of half q is the body lane of set q (gather; the
+//           exchange words 21-26 of set 0 and 8-13 of set 1 are apart), lanes lb = 0, 4, 8, .. its chain lanes and lane lb = ND
+//           its root lane; the root lane proper takes ac0[1] from L.acc[6..11] behind the last barrier.
+//           (Lane lb = 12 is then chain lane 3 and root lane at once, which the other form keeps apart: the two roles are phases
+//           separated by barriers and keep their values in different registers, pl / ucl and pcr.  The roles are derived from lb
+//           and the half here; ischain and ci are the other form's.)
+template <class CD, int NQ, int KC, bool SPLIT>
+DEV void chain_hard_apply(const ShfModel* m, const ChainLds& L, float* tail, int l, int K, float idt, bool isbody, bool islink, bool isroot,
+                          bool ischain, int ci, int lb, int myb, float (*ac0)[6] PHASE_PARAM) {
+  constexpr int NCH = CD::NCH, NLK = CD::NLK, ND = CD::ND;
+  constexpr int NS = SPLIT ? 1 : NQ;                            // impulse sets per lane
   typedef HardTail<CD, KC> T;
-  float pcr[NQ][6];
+  static_assert(!SPLIT || (NQ == 2 && 4 * (NCH - 1) < 16 && ND < 16), "a half of the env's lanes per set, a chain lane per chain in each");
+  const int half = (l >> 4) & 1;
+  const bool gath = SPLIT ? isbody : (isbody && half == 0);
+  const bool chn = SPLIT ? ((lb & 3) == 0 && (lb >> 2) < NCH) : ischain;
+  const bool rt = SPLIT ? lb == ND : isroot;
+  const int cq = SPLIT ? lb >> 2 : ci;                          // the chain of a chain lane
+  // the lane's q-th set and that set's exchange words
+  auto set_of = [&](int q) { return SPLIT ? half : q; };
+  auto xo_of = [&](int q) { return set_of(q) == 0 ? 21 : 8; };
+  float pcr[NS][6];
 #pragma unroll
-  for (int q = 0; q < NQ; q++)
+  for (int q = 0; q < NS; q++)
 #pragma unroll
     for (int j = 0; j < 6; j++) pcr[q][j] = 0.0f;
-  if (isbody_h0) {
+  if (gath) {
     // which constraints act on this body: the ids of all of them in flight at once (a load per iteration behind its own
     // branch would serialise eight LDS round trips)
     unsigned mine_a = 0u, mine_b = 0u;
@@ -208,8 +225,9 @@ DEV void chain_hard_apply(const ShfModel* m, const ChainLds& L, float* tail, int
       const bool ona = (mine_a >> c) & 1u;
       const float r[3] = {h[HC_R], h[HC_R + 1], h[HC_R + 2]};
 #pragma unroll
-      for (int q = 0; q < NQ; q++) {
-        const float f[3] = {h[q == 0 ? HC_P : HC_PV0] * idt, h[q == 0 ? HC_P + 1 : HC_PV1] * idt, h[q == 0 ? HC_P + 2 : HC_PV2] * idt};
+      for (int q = 0; q < NS; q++) {
+        const bool s0 = set_of(q) == 0;
+        const float f[3] = {h[s0 ? HC_P : HC_PV0] * idt, h[s0 ? HC_P + 1 : HC_PV1] * idt, h[s0 ? HC_P + 2 : HC_PV2] * idt};
         float t[3];
         cross3(r, f, t);
         if (ona) {
@@ -225,35 +243,35 @@ DEV void chain_hard_apply(const ShfModel* m, const ChainLds& L, float* tail, int
       // (the exchange slot's inertia words are free by now: set 0 in the bias words 21-26, set 1 in words 8-13)
       float* o = L.xch + lb * XCH_STRIDE;
 #pragma unroll
-      for (int q = 0; q < NQ; q++)
+      for (int q = 0; q < NS; q++)
 #pragma unroll
-        for (int j = 0; j < 6; j++) o[(q == 0 ? 21 : 8) + j] = pcr[q][j];
+        for (int j = 0; j < 6; j++) o[xo_of(q) + j] = pcr[q][j];
     }
   }
   GROUP_SYNC();
-  float ucl[NQ][NLK];
-  if (ischain) {
-    float pl[NQ][6];
+  PHASE_MARK(19);
+  float ucl[NS][NLK];
+  if (chn) {
+    float pl[NS][6];
     // the chain's link records and its links' exchange words, all reads in flight together: one LDS round trip for the pass
     // instead of one per link behind the link before
     HardLink Lc[NLK];
-    hard_links_load<CD>(L, CD::body(ci, 0), Lc);
-    float ox[NLK][NQ][6];
+    hard_links_load<CD>(L, CD::body(cq, 0), Lc);
+    float ox[NLK][NS][6];
 #pragma unroll
     for (int k = 0; k < NLK; k++)
 #pragma unroll
-      for (int q = 0; q < NQ; q++)
+      for (int q = 0; q < NS; q++)
 #pragma unroll
-        for (int j = 0; j < 6; j++) ox[k][q][j] = L.xch[(ci * NLK + k) * XCH_STRIDE + (q == 0 ? 21 : 8) + j];
+        for (int j = 0; j < 6; j++) ox[k][q][j] = L.xch[(cq * NLK + k) * XCH_STRIDE + xo_of(q) + j];
 #pragma unroll
     for (int k = NLK - 1; k >= 0; k--) {
-      const int li = ci * NLK + k;
       const float (*o)[6] = ox[k];
       const HardLink& Lk = Lc[k];
       const float* S = Lk.S; const float* U = Lk.U;
       const float invD = Lk.invD;
 #pragma unroll
-      for (int q = 0; q < NQ; q++) {
+      for (int q = 0; q < NS; q++) {
         if (k == NLK - 1) {
 #pragma unroll
           for (int j = 0; j < 6; j++) pl[q][j] = o[q][j];
@@ -270,56 +288,70 @@ DEV void chain_hard_apply(const ShfModel* m, const ChainLds& L, float* tail, int
         for (int j = 0; j < 6; j++) pl[q][j] = fmaf(U[j], tt, pl[q][j]);
       }
     }
-    float* o = L.xch + (ci * NLK) * XCH_STRIDE;
+    float* o = L.xch + (cq * NLK) * XCH_STRIDE;
 #pragma unroll
-    for (int q = 0; q < NQ; q++)
+    for (int q = 0; q < NS; q++)
 #pragma unroll
-      for (int j = 0; j < 6; j++) o[(q == 0 ? 21 : 8) + j] = pl[q][j];
+      for (int j = 0; j < 6; j++) o[xo_of(q) + j] = pl[q][j];
   }
   GROUP_SYNC();
-  if (isroot) {
+  PHASE_MARK(20);
+  if (rt) {
 #pragma unroll
-    for (int q = 0; q < NQ; q++) {
+    for (int q = 0; q < NS; q++) {
 #pragma unroll
       for (int j = 0; j < 6; j++) {
         float v = pcr[q][j];
 #pragma unroll
-        for (int c = 0; c < NCH; c++) v += L.xch[(c * NLK) * XCH_STRIDE + (q == 0 ? 21 : 8) + j];
+        for (int c = 0; c < NCH; c++) v += L.xch[(c * NLK) * XCH_STRIDE + xo_of(q) + j];
         pcr[q][j] = v;
       }
-      root_factors_apply(L.xroot, pcr[q], ac0[q]);
+      float a[6];
+      root_factors_apply(L.xroot, pcr[q], a);
 #pragma unroll
-      for (int j = 0; j < 6; j++) L.acc[6 * q + j] = ac0[q][j];
+      for (int j = 0; j < 6; j++) L.acc[6 * set_of(q) + j] = a[j];
+      if (!SPLIT || isroot) {
+#pragma unroll
+        for (int j = 0; j < 6; j++) ac0[q][j] = a[j];
+      }
     }
   }
   GROUP_SYNC();
-  if (ischain) {
-    float ac[NQ][6];
+  PHASE_MARK(21);
+  if (chn) {
+    float ac[NS][6];
 #pragma unroll
-    for (int q = 0; q < NQ; q++)
+    for (int q = 0; q < NS; q++)
 #pragma unroll
-      for (int j = 0; j < 6; j++) ac[q][j] = L.acc[6 * q + j];
+      for (int j = 0; j < 6; j++) ac[q][j] = L.acc[6 * set_of(q) + j];
     HardLink Lc[NLK];      // (read together again: held across the two barriers they would cost registers in every lane)
-    hard_links_load<CD>(L, CD::body(ci, 0), Lc);
+    hard_links_load<CD>(L, CD::body(cq, 0), Lc);
 #pragma unroll
     for (int k = 0; k < NLK; k++) {
-      const int li = ci * NLK + k;
+      const int li = cq * NLK + k;
       const HardLink& Lk = Lc[k];
       const float* S = Lk.S; const float* U = Lk.U;
       const float invD = Lk.invD;
 #pragma unroll
-      for (int q = 0; q < NQ; q++) {
+      for (int q = 0; q < NS; q++) {
         float ua = U[0] * ac[q][0];
 #pragma unroll
         for (int j = 1; j < 6; j++) ua = fmaf(U[j], ac[q][j], ua);
         const float qc = (ucl[q][k] - ua) * invD;
 #pragma unroll
         for (int j = 0; j < 6; j++) ac[q][j] = fmaf(S[j], qc, ac[q][j]);
-        L.dofb[li * DOF_STRIDE + 2 + q] = qc;
+        L.dofb[li * DOF_STRIDE + 2 + set_of(q)] = qc;
       }
     }
   }
   GROUP_SYNC();
+  PHASE_MARK(22);
+  if constexpr (SPLIT) {
+    if (isroot) {
+#pragma unroll
+      for (int j = 0; j < 6; j++) ac0[1][j] = L.acc[6 + j];
+    }
+  }
 }
 
 // One gym.simulate() for one env under the velocity-level contact solve; lane roles as chain_substep at 32 lanes per env.
@@ -338,6 +370,9 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
   // the fused KC = 8 forms without self-collision: H1's LDS reads batched and requested an iteration ahead (with self-collision
   // the second body's link records do not fit the registers: 100 B of scratch)
   constexpr bool PIPE = WR > 0 && !SELF;
+  // the fused KC = 8 forms: H4's two impulse sets side by side on the two halves of the env's lanes (the KC = 16 forms with
+  // self-collision pay for it in scratch; they and the hook path's sub-step keep both sets on one half)
+  constexpr bool SPLIT4 = WR > 0;
   const ShfModel* m = C.m;
   const float dt = C.sp.dt, idt = 1.0f / dt;
   const float gon = (float)m->gravity_on;
@@ -1056,7 +1091,9 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
           }
         }
       }
-      if (phase == 1 && nvel == 0) break;
+      // (no velocity iterations: the impulses after the position iterations are the final ones -- but under TGS the passes through
+      // the tree took their mean, and the forces reported are those of the final impulses: oracle, hard_solve)
+      if (phase == 1 && nvel == 0 && !TGS) break;
       if (own) {
         // the impulses of this phase in world axes, for the pass through the tree
         float* h = tail + T::HC + l * HC_STRIDE;
@@ -1071,8 +1108,8 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
     }
     PHASE_MARK(17);
     GROUP_SYNC();
-    if (nvel > 0) chain_hard_apply<CD, 2, KC>(m, L, tail, l, K, idt, isbody && half == 0, islink, isroot, ischain, ci, lb, myb, ac0);
-    else chain_hard_apply<CD, 1, KC>(m, L, tail, l, K, idt, isbody && half == 0, islink, isroot, ischain, ci, lb, myb, ac0);
+    if (nvel > 0) chain_hard_apply<CD, 2, KC, SPLIT4>(m, L, tail, l, K, idt, isbody, islink, isroot, ischain, ci, lb, myb, ac0 PHASE_PASS);
+    else chain_hard_apply<CD, 1, KC, false>(m, L, tail, l, K, idt, isbody, islink, isroot, ischain, ci, lb, myb, ac0 PHASE_PASS);
     PHASE_MARK(18);
   } else {
     if (isdof) { L.dofb[l * DOF_STRIDE + 2] = 0.0f; L.dofb[l * DOF_STRIDE + 3] = 0.0f; }
@@ -1146,7 +1183,8 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
       for (int c = 0; c < KC; c++) {      // (unrolled: the records of all constraints in flight at once)
         const float* h = tail + T::HC + c * HC_STRIDE;
         const int rep = c < K ? __float_as_int(h[HC_REP]) : -9, repb = c < K ? __float_as_int(h[HC_REPB]) : -9;
-        const float pf[3] = {(nvel > 0 ? h[HC_PV0] : h[HC_P]) * idt, (nvel > 0 ? h[HC_PV1] : h[HC_P + 1]) * idt, (nvel > 0 ? h[HC_PV2] : h[HC_P + 2]) * idt};
+        const bool fin = nvel > 0 || TGS;      // (the final impulses are in HC_PV)
+        const float pf[3] = {(fin ? h[HC_PV0] : h[HC_P]) * idt, (fin ? h[HC_PV1] : h[HC_P + 1]) * idt, (fin ? h[HC_PV2] : h[HC_P + 2]) * idt};
         if (rep == myb) { f[0] += pf[0]; f[1] += pf[1]; f[2] += pf[2]; }
         else if (last && rep == myb + 1) { fw[0] += pf[0]; fw[1] += pf[1]; fw[2] += pf[2]; }
         if (repb == myb) { f[0] -= pf[0]; f[1] -= pf[1]; f[2] -= pf[2]; }

@@ -37,17 +37,27 @@
   } while (0)
 
 // Per-phase cycle accounting for tools/phase_clock.py (debug builds with -DSHF_PHASE_CLOCK only):
-// thread 0 of block 0 adds the s_memtime delta since the previous mark to g_phase_cycles[k].
+// thread 0 of block 0 adds the s_memtime delta since the previous mark to g_phase_cycles[k]; the first lane of every wavefront
+// adds it to its wavefront's row of g_phase_wave as well (the first PHASE_NW wavefronts of the grid), from which the tool picks
+// the wavefront with the largest total of each launch -- the one the launch waits for.
 #ifdef SHF_PHASE_CLOCK
-__device__ unsigned long long g_phase_cycles[48];   // 0-23 sub-step phases, 24-31 link stages / counters, 32-37 the generic solve, 38-46 constraint-count histogram
+#define PHASE_NK 48
+#define PHASE_NW 2048
+__device__ unsigned long long g_phase_cycles[PHASE_NK];   // 0-23 sub-step phases, 24-31 link stages / counters, 32-37 the generic solve, 38-46 constraint-count histogram
+__device__ unsigned long long g_phase_wave[PHASE_NW][PHASE_NK];
 #define PHASE_BEGIN() unsigned long long _pc = clock64()
 #define PHASE_MARK(k)                                                                    \
   do {                                                                                   \
     const unsigned long long _now = clock64();                                           \
     if (blockIdx.x == 0 && threadIdx.x == 0) g_phase_cycles[k] += _now - _pc;            \
+    const unsigned _pw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);            \
+    if ((threadIdx.x & 63u) == 0u && _pw < PHASE_NW) atomicAdd(&g_phase_wave[_pw][k], _now - _pc);   \
     _pc = clock64();                                                                     \
   } while (0)
 #define PHASE_RESET() _pc = clock64()
+// a function that sets marks on its caller's clock takes it as its last parameter
+#define PHASE_PARAM , unsigned long long& _pc
+#define PHASE_PASS , _pc
 // the same for one other thread of block 0 (the first lane of the box wave in k_abb_step_ws): its own running clock
 #define PHASE_BEGIN_T() unsigned long long _pct = clock64()
 #define PHASE_MARK_T(k, tid)                                                             \
@@ -62,6 +72,8 @@ __device__ unsigned long long g_phase_cycles[48];   // 0-23 sub-step phases, 24-
 #define PHASE_BEGIN() do {} while (0)
 #define PHASE_MARK(k) do {} while (0)
 #define PHASE_RESET() do {} while (0)
+#define PHASE_PARAM
+#define PHASE_PASS
 #endif
 
 // 1/x (x > 0) and 1/sqrt(x) (x > 0) by Newton's iteration from an integer seed: the fixed operation sequences of the

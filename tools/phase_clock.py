@@ -4,9 +4,18 @@
     python tools/phase_clock.py build         # here (no GPU): debug library with -DSHF_PHASE_CLOCK
     python tools/phase_clock.py [G] [steps] [--abb]   # on the MI355X box
     python tools/phase_clock.py --chain --tgs       # the TGS form of the velocity-level solve (k_a1_chain_tgs, bench.py's default)
+    python tools/phase_clock.py --chain --tgs --lib=PATH   # another debug library, used as it is (e.g. the parent commit's, built beside)
 
 Thread 0 of block 0 accumulates the cycle count between PHASE_MARKs (csrc/shf_device.h); the marks
 serialise the wave a little (s_memtime + waitcnt), so the total is a few % above the production kernel.
+
+--chain with --pgs / --tgs prints a second column: the same phases in the wavefront with the largest total of each
+launch (the first lane of every wavefront keeps its own row; read and cleared after every step here), summed over
+the steps.  All wavefronts of the fused step are resident at once, so that wavefront is the one the launch lasts as
+long as; block 0 / wave 0 is an average one.
+The rows cost one 64-bit atomic add per mark and wavefront (about 115 per wavefront and env-step), which lengthens
+every wavefront a little more than the marks alone do: compare columns of one build with the same columns of another,
+not with the product kernel's time.
 """
 import ctypes
 import os
@@ -43,14 +52,20 @@ def main():
     selfc = "--self" in sys.argv      # --chain: with self-collision
     terrain = "trimesh" if "--trimesh" in sys.argv else "heightfield"
     hull = "--hull" in sys.argv       # --abb --link: the links as convex hulls (the EXT instantiation of the run-time-shaped kernel)
+    other = [a[len("--lib="):] for a in sys.argv if a.startswith("--lib=")]
+    sys.argv = [a for a in sys.argv if not a.startswith("--lib=")]
     argv = [a for a in sys.argv if a not in ("--abb", "--chain", "--levels", "--split", "--link", "--pgs", "--tgs", "--self", "--trimesh", "--hull")]
     G = int(argv[1]) if len(argv) > 1 else 32
     steps = int(argv[2]) if len(argv) > 2 else 100
     from shifu_amd import build as b
     deps = [os.path.join(b.CSRC, d) for d in b.DEPS]
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
-        build()                                  # a stale debug library would miss symbols the product library has
-    os.environ["SHIFU_AMD_LIB"] = LIB
+    if other:
+        lib_path = os.path.abspath(other[0])
+    else:
+        lib_path = LIB
+        if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(d) for d in deps):
+            build()                              # a stale debug library would miss symbols the product library has
+    os.environ["SHIFU_AMD_LIB"] = lib_path
     import torch
     from shifu_amd import _lib
     from shifu_amd.gym.a1_fused import FusedA1Env
@@ -77,19 +92,35 @@ def main():
     fn = lib.shf_debug_phase_cycles
     fn.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_int]
     buf = (ctypes.c_uint64 * 48)()
+    # the slowest wavefront of every launch beside block 0 / wave 0: the chain kernels' rows (a debug library built before
+    # they existed -- --lib -- prints the first column only)
+    slow = pgs and chain and not abb and hasattr(lib, "shf_debug_phase_waves")
+    if slow:
+        NW = lib.shf_debug_phase_nwaves()
+        import numpy as np
+        fw = lib.shf_debug_phase_waves
+        fw.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        rows = np.zeros((NW, 48), np.uint64)
+        worst = np.zeros(48, np.float64)
     env.reset()
     act = torch.empty(env.num_envs, env.num_actions, device=env.device)
     for _ in range(20):
         env.step(act.uniform_(-1, 1))
     torch.cuda.synchronize()
     assert fn(buf, 48, 1) == 0
+    if slow:
+        assert fw(rows.ctypes.data, 1) == 0
     for _ in range(steps):
         env.step(act.uniform_(-1, 1))
+        if slow:
+            torch.cuda.synchronize()
+            assert fw(rows.ctypes.data, 1) == 0
+            worst += rows[int(rows[:, :23].sum(1).argmax())]
     torch.cuda.synchronize()
     assert fn(buf, 48, 0) == 0
     tot = sum(buf[:17]) if not split else sum(buf[11:17]) + sum(buf[24:30])  # (marks 17-23: inside phase 4 for the box scene)
     if pgs and not abb:
-        tot = sum(buf[:19])                       # chain kernel: the solve's parts are marks 5, 10, 17, 18
+        tot = sum(buf[:23])                       # chain kernel: the solve's parts are marks 5, 10, 17 - 22
     if pgs and abb:
         tot = sum(buf[:24]) + sum(buf[32:38]) + (sum(buf[24:29]) if link else 0)    # generic kernel: every mark is its own interval
     if pgs and abb and split:
@@ -115,7 +146,8 @@ def main():
         print(f"  link contacts: {buf[29] / max(buf[31], 1):.2f} live (body, box) pairs per wavefront and sub-step, "
               f"{buf[30] / max(buf[31], 1):.2f} in its first env; stage 0 (broad phase) = mark 24")
     if pgs and not abb:
-        extra_names[0:2] = ['  H3 sweeps (position + velocity iterations)', '  H4 impulse passes (inward / root / outward, x2)']
+        extra_names[0:6] = ['  H3 sweeps (position + velocity iterations)', '  H4 impulse passes: behind the last barrier', '  H4 gather (body lanes)',
+                            '  H4 inward pass (chain lanes)', '  H4 root substitution', '  H4 outward pass (chain lanes)']
         hist = [buf[38 + k] for k in range(9)]
         print("  wavefronts by constraint count Kw = 0..8 (all blocks, per sub-step): " + " ".join(f"{100.0 * h / max(sum(hist), 1):.1f}%" for h in hist))
     hard_names = []
@@ -123,8 +155,12 @@ def main():
         # the generic solve on the body-per-lane sub-step (csrc/shf_hard.h): its parts are marks 32-37
         hard_names = ['hard: body records + velocity rates', 'hard: gather candidates', 'hard: response matrix columns',
                       'hard: owner setup', 'hard: sweeps', 'hard: impulse passes']
+    if slow:
+        wtot = worst[:23].sum()
+        print(f"  the slowest wavefront of each launch: {wtot / steps:.0f} cycles per env-step (second pair of columns)")
     for k, nme in enumerate(NAMES + extra_names):
-        print(f"  {k:2d} {nme:52s} {buf[k] / steps:9.0f}  {100.0 * buf[k] / tot:5.1f} %")
+        print(f"  {k:2d} {nme:52s} {buf[k] / steps:9.0f}  {100.0 * buf[k] / tot:5.1f} %" +
+              (f"  {worst[k] / steps:9.0f}  {100.0 * worst[k] / wtot:5.1f} %" if slow and k < 23 else ""))
     for k, nme in enumerate(hard_names):
         print(f"  {32 + k:2d} {nme:52s} {buf[32 + k] / steps:9.0f}  {100.0 * buf[32 + k] / tot:5.1f} %")
 

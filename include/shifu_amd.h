@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SHF_ABI_VERSION 18
+#define SHF_ABI_VERSION 19
 
 #define SHF_MAX_BODIES 32 /* reported rigid bodies per articulation        */
 #define SHF_MAX_DOFS 32
@@ -404,6 +404,13 @@ int shf_sim_set_hulls(ShfSim* sim, const ShfHullSet* hulls);
  * out_dev (n, 20) = count, normal[3] (from B towards A), then per contact r[3], gap. */
 int shf_convex_manifold(int32_t n, const float* pairs_dev, const ShfHull* hull_a_dev_or_null, float offset, int32_t lanes,
                         float* out_dev, void* stream);
+/* The selection at the contact cap of the chain-mapped velocity-level solve on its own (tests): for each of n envs -- gaps_dev and
+ * flags_dev (n, SHF_CAP_TEST_SLOTS + 32): the gaps of the sample-point slots in slot order, then of 32 self-contact entries, and
+ * which of them are candidates (non-zero); kmax_dev (n) >= 1 -- kept_dev (n, SHF_CAP_TEST_SLOTS + 32) = 1 for the kmax candidates
+ * with the smallest gap, ties by position, 0 elsewhere (all candidates when there are at most kmax).  Two envs share a wavefront
+ * as in the step. */
+#define SHF_CAP_TEST_SLOTS 88
+int shf_cap_select_test(int32_t n, const float* gaps_dev, const uint8_t* flags_dev, const int32_t* kmax_dev, uint8_t* kept_dev, void* stream);
 /* ShfScene.flags for the scene built by shf_sim_add_box (before shf_sim_finalize). */
 int shf_sim_set_scene_flags(ShfSim* sim, int32_t flags);
 /* gym.create_box + create_actor (object.py:28-39) */

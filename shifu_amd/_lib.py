@@ -24,6 +24,7 @@ _SIGS = {
     "shf_sim_set_hulls": ([vp, C.POINTER(_abi.ShfHullSet)], i32),
     "shf_sim_set_scene_flags": ([vp, i32], i32),
     "shf_convex_manifold": ([i32, vp, vp, C.c_float, i32, vp, vp], i32),
+    "shf_cap_select_test": ([i32, vp, vp, vp, vp, vp], i32),
     "shf_sim_finalize": ([vp, i32, i64], i32),
     "shf_sim_set_group": ([vp, i32], i32),
     "shf_sim_set_mapping": ([vp, i32], i32),

@@ -6,7 +6,8 @@
 //
 // One sub-step at 32 lanes per env (two envs per wavefront):
 //   A-C   as shf_chain.h: joint records, chain composition, rigid inertias            (dof / chain / body lanes)
-//   P     sample points -> candidate constraints; the K <= 8 with the smallest gap      (point lanes, ballots)
+//   P     sample points -> candidate constraints; the K <= 8 with the smallest gap      (point lanes, ballots; at the cap:
+//         hard_cap_select, in registers)
 //   E-G   the FREE articulated-body solve (contacts left out); the factors U, 1/D per link and the root's LDL^T stay in LDS
 //   H1    response matrix W = J M^-1 J^T, one lane per column (contact j, axis k): impulse up the chain, root solve,
 //         down every constrained chain                                                  (<= 24 column lanes)
@@ -38,7 +39,8 @@ struct HardTail {
   static constexpr int WS = PACKED ? 9 : 10;       // words per block (KC = 8: padded to ten, so that a block is four 8-byte reads and one word)
   static constexpr int NBLK = PACKED ? KC * (KC + 1) / 2 : KC * KC;
   static constexpr int NB0 = PACKED ? (CD::NPC * PT_STRIDE - W) / 9 : NBLK;          // blocks of W in the contact-slot region
-  // U, 1/D per link (phases E - G) and the selection's gap list (phase P) sit where W will be written (H1): both dead by then
+  // U, 1/D per link (phases E - G) and the gap list of the forms that still rank at the cap (phase P: CAPREG in
+  // chain_substep_hard) sit where W will be written (H1): both dead by then
   static constexpr int UF = W, PHI = W, END = W + NB0 * WS;
   static constexpr int SPARE = CD::NB * POSE_STRIDE + ((CD::NB * 6 + 3) & ~3) + CD::ND * XCH_STRIDE;   // pose | acc | xch words
   static_assert(NEVP + SHF_MAX_SELF_CONTACTS <= NB0 * WS && CD::ND * UF_STRIDE <= NB0 * WS, "the gap list / U, 1/D fit the response matrix's place");
@@ -354,6 +356,85 @@ DEV void chain_hard_apply(const ShfModel* m, const ChainLds& L, float* tail, int
   }
 }
 
+// ---- selection at the cap (phase P): the kmax candidates of an env with the smallest gap, ties by candidate order, chosen in
+// the registers that hold them -- no list, no ranking, no barrier.
+// Order key of a gap as an integer: a < b <=> key(a) < key(b) and a == b <=> key(a) == key(b) as floats (-0.0f and +0.0f both give
+// 0; candidates pass phi < offs, so there is no NaN).  |key| <= 0x7f800000: -key is the reverse order and INT_MIN is no key.
+DEV int hard_gap_key(float x) {
+  const int i = __float_as_int(x);
+  return i < 0 ? (int)(0x80000000u - (unsigned)i) : i;
+}
+// the maximum over the env's 32 lanes (half a wavefront) in every one of them: four DPP steps inside the rows of 16, then the
+// two rows of the half exchanged (v_permlane16_swap: the odd rows of one operand against the even rows of the other)
+DEV int hard_env_max(int v) {
+  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true));       // quad_perm [1, 0, 3, 2]
+  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true));       // quad_perm [2, 3, 0, 1]
+  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true));      // row_half_mirror
+  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, true));      // row_mirror
+  const auto sw = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+  return max((int)sw[0], (int)sw[1]);
+}
+// One extraction: the env's greatest key; among the entries that hold it the LAST in candidate order (row k of the sample-point
+// slots at positions k G + lane, the self-contacts behind them) -- or the first -- leaves (its key becomes INT_MIN) if `on`.
+template <int G, int NR, bool SELF, bool LAST>
+DEV void hard_cap_extract(int l, int lane0, bool on, int* key, int& skey) {
+  constexpr int NQ = NR + (SELF ? 1 : 0);
+  constexpr int NONE = (int)0x80000000;
+  int m = key[0];
+#pragma unroll
+  for (int k = 1; k < NR; k++) m = max(m, key[k]);
+  if constexpr (SELF) m = max(m, skey);
+  m = hard_env_max(m);
+  // per row the env's lanes that hold m; the position of the last (first) of them, none: below (above) every position
+  int p = LAST ? -1 : 0x7fffffff;
+#pragma unroll
+  for (int k = 0; k < NQ; k++) {
+    const unsigned b = (unsigned)(__ballot((k < NR ? key[k < NR ? k : 0] : skey) == m) >> lane0);
+    if constexpr (LAST) p = max(p, (int)((b ? (unsigned)__builtin_clz(b) : ~0u) ^ (unsigned)(k * G + G - 1)));
+    else p = (int)min((unsigned)p, (b ? (unsigned)__builtin_ctz(b) : ~0u) | (unsigned)(k * G));
+  }
+  const int d = on ? p - l : -1;
+#pragma unroll
+  for (int k = 0; k < NR; k++) key[k] = d == k * G ? NONE : key[k];
+  if constexpr (SELF) skey = d == NR * G ? NONE : skey;
+}
+// The selection itself.  cand[k] / ph[k]: the lane's candidate of row k and its gap, scand / sph: its self-contact; total: the
+// env's candidates, more than kmax in some env of the wavefront.  An env with an excess of at most kmax loses its greatest
+// (gap, position) once per excess candidate; one with more keeps its kmax smallest instead, least first: min(total - kmax, kmax)
+// trips either way.  The two envs of the wavefront count for themselves in one instruction stream; one with no excess keeps all.
+// Call it with all 64 lanes active (a wave-uniform branch): the DPP steps and the row exchange read every lane of the env.
+template <int G, int NR, bool SELF>
+DEV void hard_cap_select(int l, int lane0, int total, int kmax, const float* ph, bool* cand, float sph, bool& scand) {
+  static_assert(G == 32 && (NR + 1) * G <= 128, "two envs per wavefront; the positions of an env's candidates");
+  constexpr int NONE = (int)0x80000000;
+  const int excess = total - kmax;
+  const bool keep = excess > kmax;
+  int key[NR], skey = NONE;
+#pragma unroll
+  for (int k = 0; k < NR; k++) {
+    const int q = hard_gap_key(ph[k]);
+    key[k] = cand[k] ? (keep ? -q : q) : NONE;
+  }
+  if constexpr (SELF) {
+    const int q = hard_gap_key(sph);
+    skey = scand ? (keep ? -q : q) : NONE;
+  }
+  int n = keep ? 0 : excess;
+  while (__ballot(n > 0) != 0ull) {
+    hard_cap_extract<G, NR, SELF, true>(l, lane0, n > 0, key, skey);
+    n--;
+  }
+  n = keep ? kmax : 0;
+  while (__ballot(n > 0) != 0ull) {
+    hard_cap_extract<G, NR, SELF, false>(l, lane0, n > 0, key, skey);
+    n--;
+  }
+  // remove: what is left stays; keep: what was taken out stays
+#pragma unroll
+  for (int k = 0; k < NR; k++) cand[k] = cand[k] && ((key[k] == NONE) == keep);
+  if constexpr (SELF) scand = scand && ((skey == NONE) == keep);
+}
+
 // One gym.simulate() for one env under the velocity-level contact solve; lane roles as chain_substep at 32 lanes per env.
 // WR (KC = 8): the columns of W whose block (l, c) the lane holds in registers from H2b to the end of H3; a form that holds
 // any re-reads its sample-point constants from the staged model every sub-step (PIN is not read) instead of carrying them
@@ -373,6 +454,18 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
   // the fused KC = 8 forms: H4's two impulse sets side by side on the two halves of the env's lanes (the KC = 16 forms with
   // self-collision pay for it in scratch; they and the hook path's sub-step keep both sets on one half)
   constexpr bool SPLIT4 = WR > 0;
+  // selection at the cap in registers (hard_cap_select) -- all forms but, with self-collision, the fused KC = 8 ones under TGS
+  // and the KC = 16 ones: the fused ones of these sit at 256 registers and would spill two to four more
+  // (profiles/r12_cap_select.md); they rank through LDS (so does the hook path's KC = 16 sub-step with self-collision, which has
+  // the room: WR is 0 there as in the fused KC = 16 forms, and nothing here tells the two apart).
+  // OPEN: the spilled values live across the whole sub-step loop, not in the selection, and where the allocator's maximum lies
+  // in those forms has not been traced; until it has, there are two selections to maintain and HardTail::PHI stays.  Inside
+  // the step, self entries reach hard_cap_select only in k_a1_chain_pgs<*, true> and the hook path's KC = 8 sub-step.
+  constexpr bool CAPREG = !(SELF && (KC > 8 || (WR > 0 && TGS)));
+  // the drop counter as an atomic add whose answer nothing waits for, where that measured faster than the read-modify-write
+  // with its wait: the fused KC = 8 forms under PGS (+2.7 %); under TGS it measured slower (-0.4 %), the KC = 16 forms and the
+  // hook path's sub-step were not measured and keep the read-modify-write (profiles/r12_cap_select.md)
+  constexpr bool DROPATOM = WR > 0 && !TGS;
   const ShfModel* m = C.m;
   const float dt = C.sp.dt, idt = 1.0f / dt;
   const float gon = (float)m->gravity_on;
@@ -550,42 +643,50 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
     int total = npts + nself;
     contact_hist_count(C, l, total);
     unsigned smask = nself >= 32 ? ~0u : ((1u << nself) - 1u);      // selected self-contacts of this env
+    PHASE_MARK(30);
     if (__ballot(total > kmax) != 0ull) {
       // more candidates than the solve holds (somewhere in this wavefront): keep the kmax with the smallest gap, ties by
       // candidate order (slots, then self-contacts)
-      // The gaps as a compact list in candidate order (sample-point slots ascending, then the self-contacts): a candidate's rank
-      // is the number of entries that come before it in (gap, position).  Read four entries at a time -- a list walked one LDS
-      // round trip per entry was most of this phase for the wavefronts that overflow.
-      float* lp = tail + T::PHI;
-      int pos[NR];
+      if constexpr (CAPREG) {
+        // chosen in the registers that hold the gaps
+        hard_cap_select<G, NR, SELF>(l, lane0, total, kmax, ph, cand, sph, scand);
+      } else {
+        // The gaps as a compact list in candidate order: a candidate's rank is the number of entries that come before it in
+        // (gap, position).  Read four entries at a time.
+        float* lp = tail + T::PHI;
+        int pos[NR];
 #pragma unroll
-      for (int k = 0; k < NR; k++) {
-        const int sl = l + k * G;
-        pos[k] = sl < 64 ? __popcll(act.w[0] & ((1ull << sl) - 1ull)) : __popcll(act.w[0]) + __popcll(act.w[1] & ((1ull << (sl - 64)) - 1ull));
-        if (cand[k]) lp[pos[k]] = ph[k];
-      }
-      const int spos = npts + l;
-      if (scand) lp[spos] = sph;
-      if (l < 4) lp[total + l] = 3.0e38f;          // padding to a multiple of four: behind every gap
-      GROUP_SYNC();
-      if (total > kmax) {
-        int rank[NR], srank = 0;
-#pragma unroll
-        for (int k = 0; k < NR; k++) rank[k] = 0;
-        for (int j4 = 0; j4 < total; j4 += 4) {
-          const float4 pj4 = *reinterpret_cast<const float4*>(lp + j4);
-          const float pj[4] = {pj4.x, pj4.y, pj4.z, pj4.w};
-#pragma unroll
-          for (int e = 0; e < 4; e++) {
-#pragma unroll
-            for (int k = 0; k < NR; k++) rank[k] += (pj[e] < ph[k] || (pj[e] == ph[k] && j4 + e < pos[k])) ? 1 : 0;
-            if constexpr (SELF) srank += (pj[e] < sph || (pj[e] == sph && j4 + e < spos)) ? 1 : 0;
-          }
+        for (int k = 0; k < NR; k++) {
+          const int sl = l + k * G;
+          pos[k] = sl < 64 ? __popcll(act.w[0] & ((1ull << sl) - 1ull)) : __popcll(act.w[0]) + __popcll(act.w[1] & ((1ull << (sl - 64)) - 1ull));
+          if (cand[k]) lp[pos[k]] = ph[k];
         }
+        const int spos = npts + l;
+        if (scand) lp[spos] = sph;
+        if (l < 4) lp[total + l] = 3.0e38f;          // padding to a multiple of four: behind every gap
+        GROUP_SYNC();
+        if (total > kmax) {
+          int rank[NR], srank = 0;
 #pragma unroll
-        for (int k = 0; k < NR; k++) cand[k] = cand[k] && rank[k] < kmax;
-        if constexpr (SELF) scand = scand && srank < kmax;
-        if (l == 0 && C.dropped) *C.dropped += total - kmax;
+          for (int k = 0; k < NR; k++) rank[k] = 0;
+          for (int j4 = 0; j4 < total; j4 += 4) {
+            const float4 pj4 = *reinterpret_cast<const float4*>(lp + j4);
+            const float pj[4] = {pj4.x, pj4.y, pj4.z, pj4.w};
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+#pragma unroll
+              for (int k = 0; k < NR; k++) rank[k] += (pj[e] < ph[k] || (pj[e] == ph[k] && j4 + e < pos[k])) ? 1 : 0;
+              if constexpr (SELF) srank += (pj[e] < sph || (pj[e] == sph && j4 + e < spos)) ? 1 : 0;
+            }
+          }
+#pragma unroll
+          for (int k = 0; k < NR; k++) cand[k] = cand[k] && rank[k] < kmax;
+          if constexpr (SELF) scand = scand && srank < kmax;
+        }
+      }
+      if (total > kmax && l == 0 && C.dropped) {
+        if constexpr (DROPATOM) __hip_atomic_fetch_add(C.dropped, total - kmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else *C.dropped += total - kmax;
       }
       act.w[0] = 0ull; act.w[1] = 0ull;
 #pragma unroll
@@ -595,8 +696,9 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
       }
       smask = (unsigned)((__ballot(scand) >> lane0) & ((1ull << G) - 1ull));
       total = total > kmax ? kmax : total;
-      GROUP_SYNC();
+      if constexpr (!CAPREG) GROUP_SYNC();
     }
+    PHASE_MARK(31);
     K = total;
     const int nps = __popcll(act.w[0]) + __popcll(act.w[1]);        // selected sample points: the self-contacts follow them
     if (SELF && scand) {

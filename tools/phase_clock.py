@@ -84,7 +84,7 @@ def main():
         NAMES[3] = "contact eval: candidate gaps of the terrain points"; NAMES[4] = "candidates of the box / link families + the solve (marks 17-20, 32-37 are its parts)"
         NAMES[9] = "integration + contact force out"
     if pgs and not abb:
-        NAMES[3] = "points -> candidate constraints, selection"; NAMES[4] = "contact solve: H1-H4 (marks 5, 10, 17, 18 are its parts)"
+        NAMES[3] = "P: constraint records of the kept candidates"; NAMES[4] = "contact solve: H1-H4 (marks 5, 10, 17, 18 are its parts)"
         NAMES[5] = "  H1 response matrix W (column lanes)"; NAMES[10] = "  H2 owner setup (u0, targets, block inverses)"
         NAMES[6] = "free inward pass (row lanes)"; NAMES[7] = "root: sum, LDL^T, free acceleration"; NAMES[8] = "free outward pass + velocity rates"
         NAMES[9] = "integration + contact force out"
@@ -115,12 +115,12 @@ def main():
         if slow:
             torch.cuda.synchronize()
             assert fw(rows.ctypes.data, 1) == 0
-            worst += rows[int(rows[:, :23].sum(1).argmax())]
+            worst += rows[int((rows[:, :23].sum(1) + rows[:, 30:32].sum(1)).argmax())]
     torch.cuda.synchronize()
     assert fn(buf, 48, 0) == 0
     tot = sum(buf[:17]) if not split else sum(buf[11:17]) + sum(buf[24:30])  # (marks 17-23: inside phase 4 for the box scene)
     if pgs and not abb:
-        tot = sum(buf[:23])                       # chain kernel: the solve's parts are marks 5, 10, 17 - 22
+        tot = sum(buf[:23]) + sum(buf[30:32])     # chain kernel: the solve's parts are marks 5, 10, 17 - 22; P's first two parts 30, 31
     if pgs and abb:
         tot = sum(buf[:24]) + sum(buf[32:38]) + (sum(buf[24:29]) if link else 0)    # generic kernel: every mark is its own interval
     if pgs and abb and split:
@@ -148,6 +148,8 @@ def main():
     if pgs and not abb:
         extra_names[0:6] = ['  H3 sweeps (position + velocity iterations)', '  H4 impulse passes: behind the last barrier', '  H4 gather (body lanes)',
                             '  H4 inward pass (chain lanes)', '  H4 root substitution', '  H4 outward pass (chain lanes)']
+        # P in three parts: marks 30 and 31 come before mark 3 in the sub-step
+        extra_names += ['P: sample points -> candidate ballots', 'P: selection at the cap (+ drop counter)']
         hist = [buf[38 + k] for k in range(9)]
         print("  wavefronts by constraint count Kw = 0..8 (all blocks, per sub-step): " + " ".join(f"{100.0 * h / max(sum(hist), 1):.1f}%" for h in hist))
     hard_names = []
@@ -156,11 +158,11 @@ def main():
         hard_names = ['hard: body records + velocity rates', 'hard: gather candidates', 'hard: response matrix columns',
                       'hard: owner setup', 'hard: sweeps', 'hard: impulse passes']
     if slow:
-        wtot = worst[:23].sum()
+        wtot = worst[:23].sum() + worst[30:32].sum()
         print(f"  the slowest wavefront of each launch: {wtot / steps:.0f} cycles per env-step (second pair of columns)")
     for k, nme in enumerate(NAMES + extra_names):
         print(f"  {k:2d} {nme:52s} {buf[k] / steps:9.0f}  {100.0 * buf[k] / tot:5.1f} %" +
-              (f"  {worst[k] / steps:9.0f}  {100.0 * worst[k] / wtot:5.1f} %" if slow and k < 23 else ""))
+              (f"  {worst[k] / steps:9.0f}  {100.0 * worst[k] / wtot:5.1f} %" if slow and (k < 23 or k in (30, 31)) else ""))
     for k, nme in enumerate(hard_names):
         print(f"  {32 + k:2d} {nme:52s} {buf[32 + k] / steps:9.0f}  {100.0 * buf[32 + k] / tot:5.1f} %")
 

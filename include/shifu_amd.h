@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SHF_ABI_VERSION 19
+#define SHF_ABI_VERSION 20
 
 #define SHF_MAX_BODIES 32 /* reported rigid bodies per articulation        */
 #define SHF_MAX_DOFS 32
@@ -899,7 +899,8 @@ typedef struct ShfCamera {
 } ShfCamera;
 
 /* Renders one camera per env for num_envs envs with one ShfCamera.  scene_dev: an ShfRenderScene in device memory;
- * terrain / height_samples_dev: as bound to the sim (rows == 0: the plane z = 0; warped trimeshes are refused);
+ * terrain / height_samples_dev: as bound to the sim (rows == 0: the plane z = 0; ShfTerrain.warped: the samples followed
+ * by the per-vertex bytes, the SHF_T_HEIGHTS payload, drawn as the triangle mesh with its vertical risers -- since v20);
  * body_state (num_envs * num_bodies, 13); cam_pose (num_envs, 7) pos + quat xyzw, in the body_state frame; seg_ids
  * (num_envs, num_bodies) int32; colors (num_envs, num_bodies, 3) in [0, 1].  Outputs, each optional (NULL skips it):
  * depth (num_envs, H, W) f32, seg (num_envs, H, W) int32, rgba (num_envs, H, W, 4) u8.  No atomics, no host sync:

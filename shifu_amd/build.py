@@ -85,6 +85,9 @@ BUDGETS = [("_Z16k_a1_step_a1_g32", 256, 0),          # default: A1, two envs pe
            ("_Z10k_sim_stepILi32ELb0ELb0ELb0ELb1ELb0EE", 168, 0), ("_Z10k_sim_stepILi32ELb1ELb0ELb1ELb1ELb0EE", 256, 32),
            # the camera ray caster (csrc/shf_render.hip): per-pixel state in registers, none on the stack
            ("_Z16k_render_cameras", 128, 0),
+           # its warped-trimesh form (a kernel of its own name: the height-field form stays the one k_render_cameras): the walk plus
+           # the cell search with its per-cell vertex arrays unrolled into registers
+           ("_Z19k_render_cameras_tw", 128, 0),
            # the conv-encoder layer (csrc/shf_conv.hip), every instantiation: 214 registers at most in the first clean build (64
            # accumulators, a chunk's weight fragments, the gathered rows in flight) plus a margin of 10 for compiler drift -- still
            # two waves per SIMD; nothing on the stack

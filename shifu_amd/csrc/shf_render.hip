@@ -1,8 +1,11 @@
-// shf_render.hip -- camera sensors (ABI v16): one ray per pixel against the analytic collision shapes of each env, the
-// ground plane or the height field.  No rasteriser: boxes, spheres, capsules and convex polytopes are intersected in
-// closed form, the height field by a 2-D DDA walk over its cells (two triangles each, split as the collision code splits
-// them: along (i+1, j)-(i, j+1)).  Conventions and constants: include/shifu_amd.h (ShfRenderScene); the checker is
-// tests/render_ref.py, an independent float64 brute-force caster.
+// shf_render.hip -- camera sensors (ABI v16; warped trimesh v20): one ray per pixel against the analytic collision shapes
+// of each env, the ground plane, the height field or the warped trimesh.  No rasteriser: boxes, spheres, capsules and
+// convex polytopes are intersected in closed form, the height field by a 2-D DDA walk over its cells (two triangles each,
+// split as the collision code splits them: along (i+1, j)-(i, j+1)).  The warped trimesh (ShfTerrain.warped, the mesh
+// convert_heightfield_to_trimesh makes: shifted vertices, vertical risers, cells split along (i, j)-(i+1, j+1)) takes
+// the same walk, testing in each cell the triangles of the cells whose hint bits say they reach into it (TW form, the kernel
+// k_render_cameras_tw).  Conventions and constants: include/shifu_amd.h (ShfRenderScene); the checkers are tests/render_ref.py
+// and tests/trimesh_render_ref.py, independent float64 brute-force casters.
 //
 // Layout: one 256-thread workgroup per (env, 16 x 16 pixel tile), a wave per 16 x 4 pixel strip.  The env's shape
 // world poses are built once per workgroup into LDS (one thread per shape); each wave then culls the shapes' bounding
@@ -122,9 +125,73 @@ __device__ __forceinline__ bool hf_triangle(const float* o, const float* d, cons
   return true;
 }
 
+// One triangle of the warped mesh (world coordinates) against the ray: a hit counts on the front face (the side of
+// (v1 - v0) x (v2 - v0)), inside the triangle in 3-D (risers have no extent in xy) and inside the walked cell's closed
+// square [x0, x0 + hs] x [y0, y0 + hs], both with the walk's slack.  Collapsed triangles (zero area) are skipped.
+__device__ __forceinline__ void tw_triangle(const float* o, const float* d, const float* v0, const float* v1, const float* v2,
+                                            float s_min, float s_max, float x0, float y0, float ih, float* best, float* n) {
+  const float eps = 1e-5f;
+  const float e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
+  const float c[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+  const float dn = dot3(c, d), cc = dot3(c, c);
+  if (!(dn < 0.0f) || !(cc > 1e-16f)) return;
+  const float w[3] = {v0[0] - o[0], v0[1] - o[1], v0[2] - o[2]};
+  const float idn = 1.0f / dn;
+  const float s = dot3(w, c) * idn;
+  if (!(s >= s_min && s <= s_max && s < *best)) return;
+  // barycentric weights of v1 and v2 (Moeller-Trumbore, from the ray origin: no hit point is formed)
+  const float pv[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
+  const float qv[3] = {w[1] * e1[2] - w[2] * e1[1], w[2] * e1[0] - w[0] * e1[2], w[0] * e1[1] - w[1] * e1[0]};
+  const float bu = dot3(w, pv) * idn, bv = dot3(d, qv) * idn;
+  if (!(bu >= -eps && bv >= -eps && bu + bv <= 1.0f + eps)) return;
+  const float u = (o[0] + s * d[0] - x0) * ih, v = (o[1] + s * d[1] - y0) * ih;
+  if (!(u >= -eps && u <= 1.0f + eps && v >= -eps && v <= 1.0f + eps)) return;
+  const float il = 1.0f / sqrtf(cc);
+  *best = s;
+  n[0] = c[0] * il; n[1] = c[1] * il; n[2] = c[2] * il;
+}
+
+// nearest front-facing surface of the warped mesh inside cell (i0, j0)'s closed square, s in [s_min, s_max]: the cell's
+// own two triangles and those of the neighbouring rows / columns its hint bits name (bits 4-7 of the cell's byte,
+// warp_map_from_shifts: every triangle whose horizontal projection meets the closed square, risers standing on its
+// boundary included -- the set does not depend on the direction of the query, so it serves rays as it serves the
+// collision code's vertical queries).  Vertex (i, j) sits at cell coordinates (i + dx, j + dy), as terrain_query_warped
+// reads them.
+__device__ float tw_cell(const ShfTerrain& T, const int16_t* __restrict__ H, int i0, int j0, const float* o, const float* d,
+                         float s_min, float s_max, float* n) {
+  const int rows = T.rows, cols = T.cols;
+  const uint8_t* Wb = reinterpret_cast<const uint8_t*>(H + (size_t)rows * cols);
+  const float hs = T.hscale, vs = T.vscale, bd = T.border, ih = 1.0f / hs;
+  const int wc = Wb[(size_t)i0 * cols + j0];
+  const int ilo = ((wc >> 4) & 1) && i0 > 0 ? i0 - 1 : i0, ihi = ((wc >> 5) & 1) && i0 < rows - 2 ? i0 + 1 : i0;
+  const int jlo = ((wc >> 6) & 1) && j0 > 0 ? j0 - 1 : j0, jhi = ((wc >> 7) & 1) && j0 < cols - 2 ? j0 + 1 : j0;
+  const float x0 = (float)i0 * hs - bd, y0 = (float)j0 * hs - bd;
+  float best = INFINITY;
+  for (int i = ilo; i <= ihi; i++)
+    for (int j = jlo; j <= jhi; j++) {
+      float P[4][3];
+#pragma unroll
+      for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++) {
+          const size_t idx = (size_t)(i + a) * cols + (j + b);
+          const int wv = Wb[idx];
+          P[2 * a + b][0] = (float)(i + a + (wv & 3) - 1) * hs - bd;
+          P[2 * a + b][1] = (float)(j + b + ((wv >> 2) & 3) - 1) * hs - bd;
+          P[2 * a + b][2] = (float)H[idx] * vs;
+        }
+      tw_triangle(o, d, P[0], P[3], P[1], s_min, s_max, x0, y0, ih, &best, n);
+      tw_triangle(o, d, P[0], P[2], P[3], s_min, s_max, x0, y0, ih, &best, n);
+    }
+  return best;
+}
+
 // nearest front-facing height-field surface with s in [near, s_max]; the walk covers [near, s_max] clipped to the field's
 // bounding box, cell by cell in ray order (the first cell with a hit holds the nearest one: a front face is entered at most
-// once per cell, the two triangles being a graph over it)
+// once per cell, the two triangles being a graph over it).  TW: the warped trimesh instead -- the same clip (shifted
+// vertices stay inside the grid, zmin / zmax bound z) and the same walk; a cell takes the nearest of the hits inside its
+// square (tw_cell), so the first cell with a hit again holds the nearest one.
+template <bool TW>
 __device__ float hit_heightfield(const ShfTerrain& T, const int16_t* __restrict__ H, float zmin, float zmax, const float* o,
                                  const float* d, float s_min, float s_max, float* n) {
   const int rows = T.rows, cols = T.cols;
@@ -152,22 +219,27 @@ __device__ float hit_heightfield(const ShfTerrain& T, const int16_t* __restrict_
   float sy = d[1] != 0.0f ? ((float)(j + (sj > 0 ? 1 : 0)) * hs - bd - o[1]) / d[1] : INFINITY;
   const float eps = 1e-5f;
   for (int it = 0; it < rows + cols; it++) {
-    const int16_t* r0 = H + (size_t)i * cols + j;
-    const int16_t* r1 = r0 + cols;
-    const float x0 = (float)i * hs - bd, y0 = (float)j * hs - bd, x1 = x0 + hs, y1 = y0 + hs;
-    const float v00[3] = {x0, y0, (float)r0[0] * vs}, v10[3] = {x1, y0, (float)r1[0] * vs};
-    const float v01[3] = {x0, y1, (float)r0[1] * vs}, v11[3] = {x1, y1, (float)r1[1] * vs};
-    float best = INFINITY, s, nn[3];
-    // lower triangle (u + v <= 1) and upper one (u + v >= 1), (u, v) the hit's position in the cell
-    if (hf_triangle(o, d, v00, v10, v01, &s, nn) && s >= s_min && s <= s_max) {
-      const float u = (o[0] + s * d[0] - x0) * ih, v = (o[1] + s * d[1] - y0) * ih;
-      if (u >= -eps && v >= -eps && u + v <= 1.0f + eps && s < best) { best = s; n[0] = nn[0]; n[1] = nn[1]; n[2] = nn[2]; }
+    if constexpr (TW) {
+      const float bt = tw_cell(T, H, i, j, o, d, s_min, s_max, n);
+      if (bt < INFINITY) return bt;
+    } else {
+      const int16_t* r0 = H + (size_t)i * cols + j;
+      const int16_t* r1 = r0 + cols;
+      const float x0 = (float)i * hs - bd, y0 = (float)j * hs - bd, x1 = x0 + hs, y1 = y0 + hs;
+      const float v00[3] = {x0, y0, (float)r0[0] * vs}, v10[3] = {x1, y0, (float)r1[0] * vs};
+      const float v01[3] = {x0, y1, (float)r0[1] * vs}, v11[3] = {x1, y1, (float)r1[1] * vs};
+      float best = INFINITY, s, nn[3];
+      // lower triangle (u + v <= 1) and upper one (u + v >= 1), (u, v) the hit's position in the cell
+      if (hf_triangle(o, d, v00, v10, v01, &s, nn) && s >= s_min && s <= s_max) {
+        const float u = (o[0] + s * d[0] - x0) * ih, v = (o[1] + s * d[1] - y0) * ih;
+        if (u >= -eps && v >= -eps && u + v <= 1.0f + eps && s < best) { best = s; n[0] = nn[0]; n[1] = nn[1]; n[2] = nn[2]; }
+      }
+      if (hf_triangle(o, d, v11, v01, v10, &s, nn) && s >= s_min && s <= s_max) {
+        const float u = (o[0] + s * d[0] - x0) * ih, v = (o[1] + s * d[1] - y0) * ih;
+        if (u <= 1.0f + eps && v <= 1.0f + eps && u + v >= 1.0f - eps && s < best) { best = s; n[0] = nn[0]; n[1] = nn[1]; n[2] = nn[2]; }
+      }
+      if (best < INFINITY) return best;
     }
-    if (hf_triangle(o, d, v11, v01, v10, &s, nn) && s >= s_min && s <= s_max) {
-      const float u = (o[0] + s * d[0] - x0) * ih, v = (o[1] + s * d[1] - y0) * ih;
-      if (u <= 1.0f + eps && v <= 1.0f + eps && u + v >= 1.0f - eps && s < best) { best = s; n[0] = nn[0]; n[1] = nn[1]; n[2] = nn[2]; }
-    }
-    if (best < INFINITY) return best;
     if (fminf(sx, sy) > s1) break;
     if (sx < sy) {
       i += si; sx += tdx;
@@ -187,12 +259,15 @@ __device__ __forceinline__ uint32_t shade_u8(float c, float lam) {
 
 }  // namespace
 
-__global__ void __launch_bounds__(RT_THREADS) k_render_cameras(const ShfRenderScene* __restrict__ scene, ShfTerrain T,
-                                                             const int16_t* __restrict__ hsamp, ShfCamera cam, int tiles_x,
-                                                             int tiles, const float* __restrict__ body_state,
-                                                             const float* __restrict__ cam_pose, const int32_t* __restrict__ seg_ids,
-                                                             const float* __restrict__ colors, float* __restrict__ depth,
-                                                             int32_t* __restrict__ seg_out, uint32_t* __restrict__ rgba) {
+// TW: the terrain is a warped trimesh (hsamp: samples followed by one byte per vertex).  The two forms are two kernels
+// (k_render_cameras, k_render_cameras_tw below); the host launches the TW one only when ShfTerrain.warped, so height fields
+// and planes keep their code and registers.
+template <bool TW>
+__device__ __forceinline__ void render_cameras(const ShfRenderScene* __restrict__ scene, const ShfTerrain& T,
+                                               const int16_t* __restrict__ hsamp, const ShfCamera& cam, int tiles_x, int tiles,
+                                               const float* __restrict__ body_state, const float* __restrict__ cam_pose,
+                                               const int32_t* __restrict__ seg_ids, const float* __restrict__ colors,
+                                               float* __restrict__ depth, int32_t* __restrict__ seg_out, uint32_t* __restrict__ rgba) {
   __shared__ float S[SHF_RENDER_MAX_SHAPES * RT_SW];
   __shared__ int SI[SHF_RENDER_MAX_SHAPES * 3];   // kind, poly, segmentation id
   const int env = blockIdx.x / tiles, tile = blockIdx.x - env * tiles;
@@ -328,7 +403,7 @@ __global__ void __launch_bounds__(RT_THREADS) k_render_cameras(const ShfRenderSc
         if (s >= nearp && s <= lim) { sg = s; nn[0] = 0.0f; nn[1] = 0.0f; nn[2] = 1.0f; }
       }
     } else {
-      sg = hit_heightfield(T, hsamp, scene->hf_zmin, scene->hf_zmax, o, d, nearp, lim, nn);
+      sg = hit_heightfield<TW>(T, hsamp, scene->hf_zmin, scene->hf_zmax, o, d, nearp, lim, nn);
     }
     if (sg < best) {
       best = sg;
@@ -365,6 +440,18 @@ __global__ void __launch_bounds__(RT_THREADS) k_render_cameras(const ShfRenderSc
   }
 }
 
+#define RT_KERNEL_ARGS                                                                                                          \
+  const ShfRenderScene *__restrict__ scene, ShfTerrain T, const int16_t *__restrict__ hsamp, ShfCamera cam, int tiles_x,        \
+      int tiles, const float *__restrict__ body_state, const float *__restrict__ cam_pose, const int32_t *__restrict__ seg_ids, \
+      const float *__restrict__ colors, float *__restrict__ depth, int32_t *__restrict__ seg_out, uint32_t *__restrict__ rgba
+
+__global__ void __launch_bounds__(RT_THREADS) k_render_cameras(RT_KERNEL_ARGS) {
+  render_cameras<false>(scene, T, hsamp, cam, tiles_x, tiles, body_state, cam_pose, seg_ids, colors, depth, seg_out, rgba);
+}
+__global__ void __launch_bounds__(RT_THREADS) k_render_cameras_tw(RT_KERNEL_ARGS) {
+  render_cameras<true>(scene, T, hsamp, cam, tiles_x, tiles, body_state, cam_pose, seg_ids, colors, depth, seg_out, rgba);
+}
+
 extern "C" int shf_render_cameras(const ShfRenderScene* scene_dev, const ShfTerrain* terrain, const int16_t* height_samples_dev,
                                   const ShfCamera* camera, int32_t num_envs, const float* body_state, const float* cam_pose,
                                   const int32_t* seg_ids, const float* colors, float* depth_or_null, int32_t* seg_or_null,
@@ -377,7 +464,8 @@ extern "C" int shf_render_cameras(const ShfRenderScene* scene_dev, const ShfTerr
     return shf_set_error("shf_render_cameras: horizontal_fov must be in (0, 180) degrees");
   if (!(c.near_plane > 0.0f && c.far_plane > c.near_plane))
     return shf_set_error("shf_render_cameras: need 0 < near_plane < far_plane");
-  if (terrain->warped) return shf_set_error("shf_render_cameras: a warped trimesh terrain cannot be rendered (height fields and planes only)");
+  if (terrain->warped && terrain->rows == 0)
+    return shf_set_error("shf_render_cameras: a warped (trimesh) terrain needs height samples");
   if (terrain->rows != 0 && (terrain->rows < 2 || terrain->cols < 2 || !height_samples_dev))
     return shf_set_error("shf_render_cameras: a height field needs at least 2 x 2 samples on the device");
   if (num_envs < 0) return shf_set_error("shf_render_cameras: num_envs < 0");
@@ -385,8 +473,8 @@ extern "C" int shf_render_cameras(const ShfRenderScene* scene_dev, const ShfTerr
   if (!body_state || !cam_pose || !seg_ids || !colors) return shf_set_error("shf_render_cameras: null input tensor");
   const int tiles_x = (c.width + RT_TILE - 1) / RT_TILE, tiles = tiles_x * ((c.height + RT_TILE - 1) / RT_TILE);
   if ((int64_t)tiles * num_envs > 0x7fffffffLL) return shf_set_error("shf_render_cameras: too many envs x tiles for one launch");
-  hipLaunchKernelGGL(k_render_cameras, dim3((unsigned)(tiles * num_envs)), dim3(RT_THREADS), 0, (hipStream_t)stream, scene_dev,
-                     *terrain, height_samples_dev, c, tiles_x, tiles, body_state, cam_pose, seg_ids, colors, depth_or_null,
-                     seg_or_null, reinterpret_cast<uint32_t*>(rgba_or_null));
+  hipLaunchKernelGGL(terrain->warped ? k_render_cameras_tw : k_render_cameras, dim3((unsigned)(tiles * num_envs)),
+                     dim3(RT_THREADS), 0, (hipStream_t)stream, scene_dev, *terrain, height_samples_dev, c, tiles_x, tiles, body_state,
+                     cam_pose, seg_ids, colors, depth_or_null, seg_or_null, reinterpret_cast<uint32_t*>(rgba_or_null));
   return hipGetLastError() == hipSuccess ? 0 : shf_set_error("shf_render_cameras: launch failed");
 }

@@ -25,6 +25,7 @@ from ..a1_task import MEASURED_POINTS_X, MEASURED_POINTS_Y, a1_task_params, heig
 from ..backend import A1Task, Sim, default_sim_params
 from ..model import asset_path, compile_urdf
 from ..utils.terrain import Terrain
+from .fused_camera import FusedCameraHost
 
 REWARD_NAMES = ["tracking_lin_vel", "tracking_ang_vel", "stabilizing_base", "smoothing_action", "leg_collision",
                 "torques_penalize"]  # build_reward_functions order, a1_conditional.py:152-160
@@ -57,8 +58,8 @@ def _philox_uniform(global_ids: np.ndarray, seed: int, stream: int) -> np.ndarra
     return out
 
 
-class FusedA1Env:
-    """rsl_rl.env.VecEnv duck type (SURVEY 8b 'upward contract')."""
+class FusedA1Env(FusedCameraHost):
+    """rsl_rl.env.VecEnv duck type (SURVEY 8b 'upward contract').  Cameras: add_camera (gym/fused_camera.py)."""
 
     def __init__(self, num_envs: int = 4096, device="cuda:0", terrain: str = "heightfield", seed: int = 42,
                  rank: int = 0, world_size: int = 1, terrain_cfg=None, sim_params: Optional[_abi.ShfSimParams] = None,
@@ -181,6 +182,7 @@ class FusedA1Env:
         self.reward_names = REWARD_NAMES
         self.extras = {}
         self.common_step_counter = 0
+        self._init_cameras()
         # actors are created at default_pos + env origin (units.py:57-70 with Q14 fixed), identity pose, at rest: the
         # first reset_idx(all) then sees distance 0 and zero commands, so no env changes its terrain level (Q13)
         spawn = torch.zeros(num_envs, 13, device=self.device)

@@ -9,11 +9,12 @@ import torch
 from .. import _abi
 from ..abb_task import ABB_BASE_POS, abb_boxes, abb_model, abb_task_params
 from ..backend import AbbTask, Sim, default_sim_params
+from .fused_camera import FusedCameraHost
 
 REWARD_NAMES = ["reward_reaching", "reward_success"]   # build_reward_functions order, a_prior_stage.py:115-119
 
 
-class FusedAbbEnv:
+class FusedAbbEnv(FusedCameraHost):
     def __init__(self, num_envs: int = 4096, device="cuda:0", seed: int = 42, rank: int = 0, world_size: int = 1,
                  group: int = None, dt: float = 0.02, decimation: int = 5, episode_length_s: float = 20.0,
                  extra_boxes=(), link_contacts: bool = None, mapping: str = None, solver: str = None,
@@ -109,6 +110,7 @@ class FusedAbbEnv:
         # SHF_MAX_LINK_CONTACTS); the live device tensor, (N,) int32
         self.extras = {"dropped_contacts": S[_abi.T_DROPPED]}
         self.reward_names = REWARD_NAMES
+        self._init_cameras([tuple(b.dim) for b in self.boxes])     # add_camera (gym/fused_camera.py)
         # spawn poses + the tensors Isaac Gym would show after create_actor/prepare_sim
         A = 1 + len(self.boxes)
         root = torch.zeros(num_envs * A, 13, device=self.device)

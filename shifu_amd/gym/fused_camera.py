@@ -1,0 +1,99 @@
+"""Camera sensors on the fused envs (FusedA1Env / FusedAbbEnv): the ray caster of shifu_amd/render.py on the body states
+the fused step kernels write (SHF_T_BODY_STATE), one launch per render and camera.
+
+The fused envs own their scene -- the articulation's render shapes (CompiledModel.render_shapes), the box actors after
+them in the body-state rows, and the terrain the env was built on, the warped trimesh included -- so cameras can be added
+at any time.  Nothing here is part of the simulation state: images are derived data (state_dict is unchanged)."""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from .. import _abi
+
+
+class FusedCamera:
+    """One camera per env, the same properties in every env.  Fixed: pose (position, quat) in the frame of root_state.
+    Attached: the pose is body pose o (position, quat) at every render (Isaac Gym's FOLLOW_TRANSFORM)."""
+
+    def __init__(self, env, width: int, height: int, horizontal_fov: float, near_plane: float, far_plane: float,
+                 position, quat, attach_body: Optional[int]):
+        from ..render import camera_struct
+        n, dev = env.num_envs, env.device
+        self.env = env
+        self.width, self.height = int(width), int(height)
+        self.horizontal_fov, self.near_plane, self.far_plane = float(horizontal_fov), float(near_plane), float(far_plane)
+        self.camera = camera_struct(width, height, horizontal_fov, near_plane, far_plane, depth_negative=True)
+        self.attach_body = None if attach_body is None else int(attach_body)
+        B = env.cam_seg.shape[1]
+        if self.attach_body is not None and not 0 <= self.attach_body < B:
+            raise ValueError(f"add_camera: attach_body {attach_body} outside the env's {B} body-state rows")
+        pose = torch.tensor(np.concatenate([np.asarray(position, float), np.asarray(quat, float)]), dtype=torch.float32)
+        # fixed: the (N, 7) world poses, writable; attached: the local transform and the body's rows
+        self.pose = pose.repeat(n, 1).to(dev).contiguous()
+        if self.attach_body is not None:
+            self._rows = torch.arange(n, device=dev, dtype=torch.long) * B + self.attach_body
+        self._images = dict(rgba=torch.zeros(n, self.height, self.width, 4, dtype=torch.uint8, device=dev),
+                            depth=torch.full((n, self.height, self.width), -float("inf"), dtype=torch.float32, device=dev),
+                            seg=torch.zeros(n, self.height, self.width, dtype=torch.int32, device=dev))
+
+    def world_pose(self) -> torch.Tensor:
+        """(N, 7) camera poses (pos, quat xyzw) on the env's current body states."""
+        if self.attach_body is None:
+            return self.pose
+        from ..isaacgym.torch_utils import quat_apply, quat_mul
+        bs = self.env.body_state.index_select(0, self._rows)
+        return torch.cat([bs[:, :3] + quat_apply(bs[:, 3:7], self.pose[:, :3]), quat_mul(bs[:, 3:7], self.pose[:, 3:7])],
+                         dim=1).contiguous()
+
+    def render(self):
+        """One launch for all envs on the body states of the last step / reset; no host sync."""
+        env, im = self.env, self._images
+        env._renderer.render(env.body_state, self.world_pose(), env.cam_seg, env.cam_color, self.camera, depth=im["depth"],
+                             seg_out=im["seg"], rgba=im["rgba"])
+        return im
+
+    def raw_images(self):
+        """{"rgba": (N, H, W, 4) u8, "depth": (N, H, W) f32, negative view depth, -inf where nothing is hit, "seg":
+        (N, H, W) i32} -- the tensors render() writes (CameraSensor.raw_images's conventions).  Views, not copies."""
+        return self._images
+
+
+class FusedCameraHost:
+    """What FusedA1Env and FusedAbbEnv share: the per-env segmentation / color tables and add_camera."""
+
+    def _init_cameras(self, box_dims: Sequence = ()):
+        """box_dims: full extents of the env's box actors, in body-state row order after the articulation's bodies."""
+        from ..render import DEFAULT_BODY_COLOR
+        self._cam_box_dims = [tuple(float(v) for v in d) for d in box_dims]
+        B = int(self.cm.blob.nb) + len(self._cam_box_dims)
+        # per env and body-state row, writable: segmentation id (0, the facade's default) and color in [0, 1]
+        self.cam_seg = torch.zeros(self.num_envs, B, dtype=torch.int32, device=self.device)
+        self.cam_color = torch.tensor(DEFAULT_BODY_COLOR, dtype=torch.float32, device=self.device).repeat(self.num_envs, B, 1)
+        self.cameras = []
+        self._renderer = None
+
+    def add_camera(self, width: int, height: int, horizontal_fov: float, near_plane: float, far_plane: float,
+                   position=(0.0, 0.0, 0.0), target=None, quat=None, attach_body: Optional[int] = None) -> FusedCamera:
+        """A camera in every env: looking from `position` at `target`, or with orientation `quat` (xyzw; local +x forward,
+        +z up), in the frame of root_state -- or, with attach_body (a row of the env's body states), in that body's frame."""
+        from ..render import Renderer, build_scene, lookat_quat
+        if target is not None and quat is not None:
+            raise ValueError("add_camera: give target or quat, not both")
+        if target is not None:
+            quat = lookat_quat(position, target)
+        elif quat is None:
+            quat = (0.0, 0.0, 0.0, 1.0)
+        quat = np.asarray(quat, float) / np.linalg.norm(quat)
+        if self._renderer is None:
+            t = self.sim.terrain
+            hs = self.sim.height_samples if t.rows > 0 else None
+            scene = build_scene(self.cm.render_shapes, int(self.cm.blob.nb), self._cam_box_dims, height_samples=hs,
+                                vscale=t.vscale)
+            # the sim's own terrain payload on the device (a warped terrain: samples followed by the vertex bytes)
+            self._renderer = Renderer(scene, t, self.sim._heights if t.rows > 0 else None, self.device)
+        cam = FusedCamera(self, width, height, horizontal_fov, near_plane, far_plane, position, quat, attach_body)
+        self.cameras.append(cam)
+        return cam

@@ -638,11 +638,18 @@ class Gym:
         return len(env.cameras) - 1
 
     @staticmethod
+    def _trimesh_cameras_enabled() -> bool:
+        """SHIFU_AMD_TRIMESH_CAMERAS=1: camera sensors on a warped trimesh terrain (the ray caster draws it, risers
+        included); refused without it, which is what callers of this facade have seen so far."""
+        return os.environ.get("SHIFU_AMD_TRIMESH_CAMERAS", "0") == "1"
+
+    @staticmethod
     def _check_renderable_terrain(sim):
         t = sim.terrain
-        if t is not None and t[0] == "heightfield" and len(t) > 6 and t[6] is not None:
+        if t is not None and t[0] == "heightfield" and len(t) > 6 and t[6] is not None and not Gym._trimesh_cameras_enabled():
             raise NotImplementedError("camera sensors cannot render a warped trimesh terrain (the triangle mesh "
-                                      "convert_heightfield_to_trimesh makes, ShfTerrain.warped): height fields and planes only")
+                                      "convert_heightfield_to_trimesh makes, ShfTerrain.warped) unless "
+                                      "SHIFU_AMD_TRIMESH_CAMERAS=1 is set: height fields and planes only by default")
 
     def set_camera_location(self, camera_handle, env: Env, position, target):
         from ..render import lookat_quat
@@ -688,9 +695,9 @@ class Gym:
         import torch
         from ..render import DEFAULT_BODY_COLOR, Renderer, build_scene, camera_struct
         be = sim.backend
-        if be.terrain.warped:
-            raise NotImplementedError("camera sensors cannot render a warped trimesh terrain (ShfTerrain.warped): height "
-                                      "fields and planes only")
+        if be.terrain.warped and not self._trimesh_cameras_enabled():
+            raise NotImplementedError("camera sensors cannot render a warped trimesh terrain (ShfTerrain.warped) unless "
+                                      "SHIFU_AMD_TRIMESH_CAMERAS=1 is set: height fields and planes only by default")
         env0 = sim.envs[0]
         model = env0.actors[0].asset.model
         boxes = [a.asset.box_dim for a in env0.actors[1:]]

@@ -258,8 +258,10 @@ class FusedRegressor:
     def from_camera(self, camera_sensor):
         """The same forward straight from a CameraSensor's image group (rgba u8 and depth, as rendered): equals
         __call__({'rgb': color_buf.permute(0, 3, 1, 2), 'depth': depth_buf.unsqueeze(1)}) of a sensor with
-        image_normalization bit for bit, without the normalise / negate copies."""
-        if not camera_sensor.cfg.image_normalization:
+        image_normalization bit for bit, without the normalise / negate copies.  A fused env's camera
+        (gym/fused_camera.py) has no converted buffers and no such setting: only its raw_images() are read."""
+        cfg = getattr(camera_sensor, "cfg", None)
+        if cfg is not None and not cfg.image_normalization:
             raise ValueError("from_camera reads colors as [0, 1] floats and depth as positive distance, which is what a "
                              "CameraSensor with image_normalization gives; this sensor has it off")
         im = camera_sensor.raw_images()

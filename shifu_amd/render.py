@@ -191,24 +191,39 @@ def camera_struct(width: int, height: int, horizontal_fov: float, near: float, f
 
 
 class Renderer:
-    """Device copies of one render scene (+ the terrain) and the launch of shf_render_cameras."""
+    """Device copies of one render scene (+ the terrain) and the launch of shf_render_cameras.
+
+    heights: the (rows, cols) int16 samples, host or device.  A warped terrain (ShfTerrain.warped, the triangle mesh
+    convert_heightfield_to_trimesh makes) takes the packed payload the sim holds -- samples followed by one byte per vertex
+    (terrain_utils.pack_trimesh_samples) -- either as that flat int16 array / device tensor, or as the samples plus `warp`,
+    the (rows, cols) uint8 bytes of terrain_utils.trimesh_warp_map, which are packed here."""
 
     def __init__(self, scene: "_abi.ShfRenderScene", terrain: Optional["_abi.ShfTerrain"] = None, heights=None,
-                 device="cuda:0"):
+                 device="cuda:0", warp=None):
         import torch
         from .backend import _struct_to_device
         self.device = torch.device(device)
         if terrain is None:
             terrain = _abi.ShfTerrain()
             terrain.hscale = terrain.vscale = 1.0
-        if terrain.warped:
-            raise NotImplementedError("camera sensors cannot render a warped trimesh terrain (ShfTerrain.warped); height "
-                                      "fields and the ground plane only")
+        if warp is not None and not terrain.warped:
+            raise ValueError("Renderer: warp bytes given for a terrain that is not warped")
         self.scene, self.terrain = scene, terrain
         self._scene_dev = _struct_to_device(scene, self.device)
         self._heights = None
         if terrain.rows > 0:
+            nv = int(terrain.rows) * int(terrain.cols)
+            if warp is not None:
+                from .isaacgym.terrain_utils import pack_trimesh_samples
+                hs = heights.cpu().numpy() if isinstance(heights, torch.Tensor) else np.asarray(heights)
+                if hs.size != nv or np.asarray(warp).size != nv:
+                    raise ValueError(f"Renderer: samples and warp bytes must hold rows x cols = {nv} values each")
+                heights = pack_trimesh_samples(hs, warp)
             h = heights if isinstance(heights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(heights, np.int16))
+            need = nv + (nv + 1) // 2 if terrain.warped else nv
+            if h.dtype != torch.int16 or h.numel() < need:
+                raise ValueError(f"Renderer: the terrain needs {need} int16 values (a warped terrain: samples followed by "
+                                 f"one byte per vertex), got {h.numel()} {h.dtype}")
             self._heights = h.to(self.device).contiguous()
 
     def render(self, body_state, cam_pose, seg, color, camera: "_abi.ShfCamera", depth=None, seg_out=None, rgba=None):

@@ -4,6 +4,12 @@ on the ABB push-box scene through the gym facade and CameraSensor.  Times the re
 over --renders renders after warm-up, and prints one JSON line.
 
     python tools/bench_camera.py --envs 1000
+
+--scene a1-heightfield / a1-trimesh: FusedA1Env on that terrain with a trunk-mounted 64 x 48 camera (depth, segmentation
+and color; fov 87, near 0.05, far 6, pitched 0.5 rad down) after a reset and a few random steps -- the walk over the height
+field against the walk over the warped trimesh on the same samples.
+
+    python tools/bench_camera.py --scene a1-trimesh --envs 4096
 """
 import argparse
 import json
@@ -58,12 +64,62 @@ def make_env(n):
     return env_class(cfg)
 
 
+def time_renders(render, warmup, renders):
+    """ms per call of render(), by device events."""
+    import torch
+    for _ in range(warmup):
+        render()
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(renders):
+        render()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) / renders
+
+
+def bench_a1(a):
+    import math
+    import torch
+    from shifu_amd.gym.a1_fused import FusedA1Env
+    terrain = a.scene[len("a1-"):]
+    env = FusedA1Env(num_envs=a.envs, terrain=terrain)
+    W, H = 64, 48
+    cam = env.add_camera(W, H, 87.0, 0.05, 6.0, position=(0.25, 0.0, 0.05), quat=(0.0, math.sin(0.25), 0.0, math.cos(0.25)),
+                         attach_body=0)
+    env.cam_seg.fill_(1)                        # the robot; the terrain is segmentation 0
+    env.reset()
+    g = torch.Generator().manual_seed(0)
+    for _ in range(3):
+        env.step((2 * torch.rand(env.num_envs, env.num_actions, generator=g) - 1).to(env.device))
+    # the attached pose is composed once: the timed call is the render launch alone, as in the default scene
+    pose, im = cam.world_pose(), cam.raw_images()
+    render = lambda: env._renderer.render(env.body_state, pose, env.cam_seg, env.cam_color, cam.camera, depth=im["depth"],
+                                          seg_out=im["seg"], rgba=im["rgba"])
+    ms = time_renders(render, a.warmup, a.renders)
+    rays = a.envs * W * H
+    hit = torch.isfinite(im["depth"])
+    out = dict(bench="camera_render", scene=a.scene, envs=a.envs, width=W, height=H,
+               image_types=["color", "depth", "segmentation"], renders=a.renders, ms_per_render=round(ms, 4),
+               rays_per_s=round(rays / (ms * 1e-3), 1), bytes_written=rays * 12,
+               write_gb_per_s=round(rays * 12 / (ms * 1e-3) / 1e9, 1),
+               pixels_on_terrain=round(float((hit & (im["seg"] == 0)).float().mean()), 4),
+               pixels_hit=round(float(hit.float().mean()), 4), warped=int(env.sim.terrain.warped),
+               device=torch.cuda.get_device_name(0))
+    print(json.dumps(out))
+    env.destroy()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1000)
     ap.add_argument("--renders", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--scene", choices=["abb", "a1-heightfield", "a1-trimesh"], default="abb")
     a = ap.parse_args()
+    if a.scene != "abb":
+        return bench_a1(a)
     import torch
     env = make_env(a.envs)
     env.reset()

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SHF_ABI_VERSION 20
+#define SHF_ABI_VERSION 21
 
 #define SHF_MAX_BODIES 32 /* reported rigid bodies per articulation        */
 #define SHF_MAX_DOFS 32
@@ -738,6 +738,33 @@ int shf_conv_pack_weights(const float* w, void* pack, int32_t cin, int32_t cout,
 int shf_conv3x3s2_forward(const void* x, int32_t src_kind, const int64_t* strides, const void* pack, const float* scale,
                           const float* shift, float* y, int32_t flatten, int32_t nimg, int32_t cin, int32_t h, int32_t w,
                           int32_t cout, void* stream);
+
+/* ------------------------------------------------------------------------
+ * LSTM cell step of the recurrent policy (ABI v21; csrc/shf_lstm.hip): rsl_rl's ActorCriticRecurrent [EXT], which
+ * PPOConfig.policy names (shifu/configs/policy_config.py:13-16).  torch.nn.LSTM's equations and gate order (i, f, g, o):
+ *   pre      = x w_ih^T + b_ih + (r h_prev) w_hh^T + b_hh            r[m] = reset[m] ? 0 : 1 (one byte per row; null: all 1)
+ *   c_out    = sigma(pre_f) (r c_prev) + sigma(pre_i) tanh(pre_g)      h_out = sigma(pre_o) tanh(c_out)
+ * as one GEMM over [x | h_prev] on the matrix cores (operand scheme and precision switch of the trainer kernels above,
+ * shf_mlp_set_precision) whose epilogue is the pointwise update; the pre-activations are never stored.
+ *   pack     w_ih[4H, I], w_hh[4H, H] (fp32, contiguous) laid out once in fragment order in a caller-owned device buffer
+ *            of shf_lstm_pack_bytes(I, H) bytes (16-byte aligned); repack whenever the weights change
+ *   x        fp32 rows of I values, row stride ldx >= I (elements); h_prev, c_prev, h_out, c_out fp32 [M, H] contiguous
+ *   gates    null, or fp32 [M, 4H]: the activated gates, kept for the backward pass
+ * h_out / c_out must not overlap h_prev / c_prev / x (other blocks still read the rows being replaced): overlapping
+ * ranges are refused.  A row depends on its own row of the inputs only; no atomics, no host synchronisation.
+ * backward_pointwise: dgates[M, 4H] = dL/dpre and dc_prev[M, H] = dL/dc_prev from dh = dL/dh_out, dc = dL/dc_out (null: 0),
+ * the kept gates and cell states; the three GEMMs of the backward pass are shf_mlp_linear_backward_input (dx with w_ih,
+ * dh_prev with w_hh, times r) and shf_mlp_linear_backward_weight (x and r h_prev) on dgates.
+ * Errors: shf_mlp_last_error.
+ * ---------------------------------------------------------------------- */
+int shf_lstm_pack_bytes(int32_t I, int32_t H, int64_t* bytes);
+int shf_lstm_pack_weights(const float* w_ih, const float* w_hh, void* pack, int32_t I, int32_t H, void* stream);
+int shf_lstm_cell_forward(const float* x, int32_t ldx, const float* h_prev, const float* c_prev, const unsigned char* reset_or_null,
+                          const void* pack, const float* b_ih, const float* b_hh, float* h_out, float* c_out,
+                          float* gates_or_null, int32_t M, int32_t I, int32_t H, void* stream);
+int shf_lstm_cell_backward_pointwise(const float* dh, const float* dc_or_null, const float* gates, const float* c_prev,
+                                     const unsigned char* reset_or_null, const float* c_out, float* dgates, float* dc_prev,
+                                     int32_t M, int32_t H, void* stream);
 
 /* PPO mini-batch loss with its gradient, one pass (rsl_rl's PPO.update loss block [EXT], which the reference's runner
  * drives: shifu/runner/policy_runner.py:52-73 with PPOConfig.algorithm, shifu/configs/policy_config.py:18-31):

@@ -1162,6 +1162,8 @@ extern "C" int shf_mlp_probe_read(long long* out, int n) {
 }
 #endif
 extern "C" const char* shf_mlp_last_error(void) { return g_mlp_err.c_str(); }
+// for the trainer kernels of other units (csrc/shf_lstm.hip), whose errors are read through shf_mlp_last_error too
+int shf_mlp_report_error(const char* message) { return mlp_fail(message ? message : ""); }
 extern "C" int shf_mlp_set_precision(int32_t mode) {
   if (mode != SHF_MLP_BF16 && mode != SHF_MLP_BF16X3 && mode != SHF_MLP_BF16X3_W1)
     return mlp_fail("shf_mlp_set_precision: mode must be SHF_MLP_BF16, SHF_MLP_BF16X3 or SHF_MLP_BF16X3_W1");

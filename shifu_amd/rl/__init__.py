@@ -15,6 +15,7 @@ estimate are averaged with one bucketed all-reduce per mini-batch (RCCL on MI355
 from .actor_critic import ActorCritic
 from .on_policy_runner import OnPolicyRunner
 from .ppo import PPO
+from .recurrent import ActorCriticRecurrent, Memory
 from .storage import RolloutStorage
 
-__all__ = ["ActorCritic", "OnPolicyRunner", "PPO", "RolloutStorage"]
+__all__ = ["ActorCritic", "ActorCriticRecurrent", "Memory", "OnPolicyRunner", "PPO", "RolloutStorage"]

@@ -325,21 +325,26 @@ class MfmaMLP(nn.Sequential):
         return _MfmaChainFn.apply(x, tuple(1 if m.elu else 0 for m in ls), *params)
 
 
+def _keeps_pack(m) -> bool:
+    # MfmaLinear, and the recurrent policy's Memory (rl/recurrent.py: the LSTM cell kernel's pack, same rules)
+    return isinstance(m, MfmaLinear) or getattr(m, "_keeps_pack", False)
+
+
 def refresh_packs(module: nn.Module) -> None:
-    """MfmaLinear.refresh_pack on every such layer of `module` (a no-op for other layers)."""
+    """refresh_pack on every layer of `module` that keeps a weight pack (a no-op for other layers)."""
     for m in module.modules():
-        if isinstance(m, MfmaLinear):
+        if _keeps_pack(m):
             m.refresh_pack()
 
 
 def invalidate_packs(module: nn.Module) -> None:
     for m in module.modules():
-        if isinstance(m, MfmaLinear):
+        if _keeps_pack(m):
             m.invalidate_pack()
 
 
 def mark_packs_valid(module: nn.Module) -> None:
     """After replaying a captured graph that contains the refresh: the pack kernels ran, only the Python flag is stale."""
     for m in module.modules():
-        if isinstance(m, MfmaLinear) and m._pack is not None:
+        if _keeps_pack(m) and m._pack is not None:
             m._pack_valid = True

@@ -13,6 +13,7 @@ import torch
 
 from ..parallel import broadcast_parameters, rank, world_size
 from .actor_critic import ActorCritic
+from .recurrent import ActorCriticRecurrent
 from .mfma_linear import invalidate_packs, mark_packs_valid, refresh_packs
 from .ppo import PPO
 
@@ -26,11 +27,12 @@ class OnPolicyRunner:
         self.env = env
         num_critic_obs = env.num_privileged_obs if env.num_privileged_obs is not None else env.num_obs
         name = self.cfg.get("policy_class_name", "ActorCritic")
-        if name != "ActorCritic":
-            raise NotImplementedError(f"policy_class_name '{name}': only the feed-forward ActorCritic is implemented")
+        classes = {"ActorCritic": ActorCritic, "ActorCriticRecurrent": ActorCriticRecurrent}
+        if name not in classes:
+            raise NotImplementedError(f"policy_class_name '{name}': one of {sorted(classes)}")
         if self.cfg.get("algorithm_class_name", "PPO") != "PPO":
             raise NotImplementedError("algorithm_class_name: only PPO is implemented")
-        actor_critic = ActorCritic(env.num_obs, num_critic_obs, env.num_actions, **self.policy_cfg).to(device)
+        actor_critic = classes[name](env.num_obs, num_critic_obs, env.num_actions, **self.policy_cfg).to(device)
         broadcast_parameters(actor_critic)
         self.alg = PPO(actor_critic, device=device, **self.alg_cfg)
         self.num_steps_per_env = self.cfg["num_steps_per_env"]

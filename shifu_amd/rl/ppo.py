@@ -68,6 +68,9 @@ class PPO:
 
     def act(self, obs, critic_obs):
         t = self.transition
+        if self.actor_critic.is_recurrent and self.storage.step == 0:
+            # the state the rollout starts from: what the update's sequences start from (copied: the buffers are advanced in place)
+            self.storage.save_hidden_states(self.actor_critic.init_hidden_states(obs.shape[0], obs.device, obs.dtype))
         t.actions = self.actor_critic.act(obs).detach()
         t.values = self.actor_critic.evaluate(critic_obs).detach()
         t.actions_log_prob = self.actor_critic.get_actions_log_prob(t.actions).detach()
@@ -89,11 +92,13 @@ class PPO:
         self.actor_critic.reset(dones)
 
     def compute_returns(self, last_critic_obs):
-        last_values = self.actor_critic.evaluate(last_critic_obs).detach()
+        ac = self.actor_critic
+        last_values = (ac.evaluate(last_critic_obs, advance=False) if ac.is_recurrent else ac.evaluate(last_critic_obs)).detach()
         self.storage.compute_returns(last_values, self.gamma, self.lam)
 
     def losses(self, obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma):
-        """Loss terms of one mini-batch under the current parameters (also what tests/test_rl.py checks)."""
+        """Loss terms of one mini-batch under the current parameters (also what tests/test_rl.py checks).  obs / cobs are the
+        inputs of the actor / critic MLP: observations, or a recurrent policy's memory outputs (_update_recurrent)."""
         ac = self.actor_critic
         if self.fused_loss:
             return self._fused_losses(obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma)
@@ -103,7 +108,7 @@ class PPO:
             cur = torch.cuda.current_stream(torch.device(self.device))
             self._side.wait_stream(cur)
             with torch.cuda.stream(self._side):
-                value = ac.evaluate(cobs)
+                value = ac.critic(cobs)
             value.record_stream(cur)             # consumed on the main stream after the join
             ac.update_distribution(obs)
             logp = ac.get_actions_log_prob(actions)
@@ -111,7 +116,7 @@ class PPO:
         else:
             ac.update_distribution(obs)
             logp = ac.get_actions_log_prob(actions)
-            value = ac.evaluate(cobs)
+            value = ac.critic(cobs)
         mu, sigma, entropy = ac.action_mean, ac.action_std, ac.entropy
         with torch.no_grad():
             # KL(old || new) of diagonal Gaussians, averaged over the mini-batch
@@ -140,12 +145,12 @@ class PPO:
             cur = torch.cuda.current_stream(torch.device(self.device))
             self._side.wait_stream(cur)
             with torch.cuda.stream(self._side):
-                value = ac.evaluate(cobs)
+                value = ac.critic(cobs)
             value.record_stream(cur)
             mu = ac.actor(obs)
             cur.wait_stream(self._side)
         else:
-            mu, value = ac.actor(obs), ac.evaluate(cobs)
+            mu, value = ac.actor(obs), ac.critic(cobs)
         loss, stats = ppo_loss(mu, ac.std, value, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma,
                                self.clip_param, self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss)
         return {"surrogate": stats[0], "value": stats[1], "entropy": stats[2], "kl": stats[3], "loss": loss}
@@ -231,7 +236,28 @@ class PPO:
             self._minibatch_step(self.storage.mini_batch(self._upd_idx), self._upd_sums)
         self._upd_graph = g
 
+    def _update_recurrent(self):
+        """update() for a recurrent policy: whole (T, mb) sequences per mini-batch from the rollout's initial hidden state,
+        resets inside the cell (rl/recurrent.py); the loss block is the feed-forward one on the flattened memory outputs."""
+        st, ac = self.storage, self.actor_critic
+        if self.graph_update and not getattr(self, "_said_eager", False):
+            print("PPO: graph_update is not implemented for recurrent policies; the update runs eagerly")
+            self._said_eager = True
+        sums = torch.zeros(2, device=self.device)
+        for _ in range(self.num_learning_epochs):
+            for obs, cobs, dones, hidden, flat in st.recurrent_mini_batches(self.num_mini_batches):
+                self.optimizer.zero_grad(set_to_none=True)
+                feat_a, feat_c = ac.sequence_features(obs, cobs, dones, hidden)
+                self._minibatch_step((feat_a, feat_c) + flat, sums)
+        n = self.num_learning_epochs * self.num_mini_batches
+        st.clear()
+        self._updates_done += 1
+        mean_value_loss, mean_surrogate_loss = (sums / n).tolist()
+        return mean_value_loss, mean_surrogate_loss
+
     def update(self):
+        if self.actor_critic.is_recurrent:
+            return self._update_recurrent()
         st = self.storage
         B = st.num_envs * st.num_transitions_per_env
         mb = B // self.num_mini_batches

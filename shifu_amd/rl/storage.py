@@ -23,6 +23,20 @@ class RolloutStorage:
         self.dones = torch.zeros(T, N, 1, device=device, dtype=torch.uint8)
         self.mu, self.sigma = z(*actions_shape), z(*actions_shape)
         self.step = 0
+        # recurrent policies: the actor's and the critic's hidden state as it was before the rollout's first act
+        # (tuples of (num_layers, N, H) tensors; (h, c) for LSTM, (h,) for GRU), kept at fixed addresses
+        self.saved_hidden_states_a = self.saved_hidden_states_c = None
+
+    def save_hidden_states(self, hidden_states):
+        """hidden_states = (actor's, critic's) as ActorCriticRecurrent.get_hidden_states() returns them."""
+        norm = lambda h: tuple(h) if isinstance(h, (tuple, list)) else (h,)
+        ha, hc = norm(hidden_states[0]), norm(hidden_states[1])
+        if self.saved_hidden_states_a is None or any(d.shape != s.shape for d, s in zip(self.saved_hidden_states_a + self.saved_hidden_states_c, ha + hc)):
+            self.saved_hidden_states_a = tuple(h.detach().clone() for h in ha)
+            self.saved_hidden_states_c = tuple(h.detach().clone() for h in hc)
+        else:
+            for d, s in zip(self.saved_hidden_states_a + self.saved_hidden_states_c, ha + hc):
+                d.copy_(s.detach())
 
     def add_transitions(self, t: "RolloutStorage.Transition"):
         if self.step >= self.num_transitions_per_env:
@@ -113,6 +127,25 @@ class RolloutStorage:
         obs, actions, values, adv, ret, logp, mu, sigma = out[:8]
         cobs = out[8] if self.privileged_observations is not None else obs
         return (obs, cobs, actions, values, adv, ret, logp, mu, sigma)
+
+    def recurrent_mini_batches(self, num_mini_batches):
+        """Mini-batches of a recurrent policy: contiguous env slices [:, i * mb : (i + 1) * mb] with whole time (rsl_rl's
+        choice; no shuffling of time).  Yields (obs (T, mb, D), critic_obs, dones (T, mb), (actor's, critic's initial hidden
+        state), (actions, values, advantages, returns, log_prob, mu, sigma) flattened to (T * mb, ...), row t * mb + j)."""
+        mb = self.num_envs // num_mini_batches
+        if mb < 1:
+            raise ValueError(f"recurrent mini-batches: {num_mini_batches} mini-batches for {self.num_envs} envs")
+        if self.saved_hidden_states_a is None:
+            raise RuntimeError("recurrent mini-batches: no hidden state was saved for this rollout (save_hidden_states)")
+        unpack = lambda hs: hs if len(hs) > 1 else hs[0]
+        for i in range(num_mini_batches):
+            sl = slice(i * mb, (i + 1) * mb)
+            obs = self.observations[:, sl]
+            cobs = self.privileged_observations[:, sl] if self.privileged_observations is not None else obs
+            flat = tuple(t[:, sl].flatten(0, 1) for t in (self.actions, self.values, self.advantages, self.returns,
+                                                           self.actions_log_prob, self.mu, self.sigma))
+            hid = (unpack(tuple(h[:, sl] for h in self.saved_hidden_states_a)), unpack(tuple(h[:, sl] for h in self.saved_hidden_states_c)))
+            yield obs, cobs, self.dones[:, sl, 0], hid, flat
 
     def _gather_rows(self, srcs, idx):
         import ctypes as C

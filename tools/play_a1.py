@@ -23,6 +23,9 @@ def main():
     ap.add_argument("--traj", default=None)
     ap.add_argument("--self-collision", action="store_true", help="collide the robot's own links, as in training with the same flag")
     ap.add_argument("--solver", choices=["pgs", "tgs", "compliant"], default=None, help="contact solver (FusedA1Env(solver=...)); default: the env's")
+    ap.add_argument("--policy", choices=["mlp", "recurrent"], default="mlp", help="the policy class the checkpoint was trained with (tools/train_a1.py --policy)")
+    ap.add_argument("--rnn-hidden", type=int, default=512)
+    ap.add_argument("--rnn-layers", type=int, default=1)
     ap.add_argument("--max-contacts", type=int, default=None, help="ShfSimParams.max_contacts (pgs): 8 (default) .. 16")
     args = ap.parse_args()
     from examples.a1_conditional.task_config import A1PPOConfig
@@ -33,7 +36,11 @@ def main():
     env = FusedA1Env(num_envs=args.envs, terrain=args.terrain, seed=7, self_collision=args.self_collision,
                      **({} if args.solver is None else {"solver": args.solver}),
                      **({} if args.max_contacts is None else {"solver_kw": {"max_contacts": args.max_contacts}}))
-    runner = OnPolicyRunner(env, class_to_dict(A1PPOConfig()), log_dir=None, device="cuda:0")
+    cfg = class_to_dict(A1PPOConfig())
+    if args.policy == "recurrent":
+        cfg["runner"]["policy_class_name"] = "ActorCriticRecurrent"
+        cfg["policy"].update({"rnn_type": "lstm", "rnn_hidden_size": args.rnn_hidden, "rnn_num_layers": args.rnn_layers})
+    runner = OnPolicyRunner(env, cfg, log_dir=None, device="cuda:0")
     infos = runner.load(args.checkpoint, load_optimizer=False)
     trained = (infos or {}).get("contact_solver") if isinstance(infos, dict) else None
     if trained is None:
@@ -51,6 +58,7 @@ def main():
     with torch.no_grad():
         for _ in range(args.steps):
             obs, _, rew, done, extras = env.step(policy(obs.clone()))
+            runner.alg.actor_critic.reset(done)                  # (a recurrent policy forgets a finished episode; a no-op otherwise)
             bv = env.task.tensors[_abi.A1_BASE_VEL]               # base-frame lin (0:3) / ang (3:6) velocity
             cmd = env.command_buf
             c = cmd[:, :2]

@@ -27,6 +27,10 @@ def main():
     ap.add_argument("--graph", action="store_true", help="capture the rollout in one hipGraph (runner.graph_rollout)")
     ap.add_argument("--mlp", choices=["torch", "mfma"], default=None,
                     help="ActorCritic layers: stock fp32 library GEMMs, or the hand-written MFMA kernels (csrc/shf_mlp.hip)")
+    ap.add_argument("--policy", choices=["mlp", "recurrent"], default="mlp",
+                    help="mlp: the feed-forward ActorCritic; recurrent: ActorCriticRecurrent (an LSTM in front of each MLP, rl/recurrent.py)")
+    ap.add_argument("--rnn-hidden", type=int, default=512, help="--policy recurrent: rnn_hidden_size")
+    ap.add_argument("--rnn-layers", type=int, default=1, help="--policy recurrent: rnn_num_layers")
     ap.add_argument("--eager-update", action="store_true", help="with --graph: capture the rollout only, launch the PPO update eagerly")
     ap.add_argument("--graph-update", action="store_true", help="capture the PPO update only (debugging)")
     ap.add_argument("--fused-loss", action="store_true", help="(the default since round 5; accepted for old command lines)")
@@ -61,6 +65,9 @@ def main():
     cfg["algorithm"]["fused_loss"] = not args.torch_loss
     if args.mlp:
         cfg["policy"]["mlp_backend"] = args.mlp
+    if args.policy == "recurrent":
+        cfg["runner"]["policy_class_name"] = "ActorCriticRecurrent"
+        cfg["policy"].update({"rnn_type": "lstm", "rnn_hidden_size": args.rnn_hidden, "rnn_num_layers": args.rnn_layers})
     set_seed((A1PPOConfig.seed if args.seed is None else args.seed) + rank)
     if args.hook:
         from examples.a1_conditional.a1_conditional import A1Conditional
@@ -96,7 +103,7 @@ def main():
     if rank == 0:
         H = runner.history
         pick = sorted(set([0, len(H) // 8, len(H) // 4, len(H) // 2, 3 * len(H) // 4, len(H) - 1]))
-        out = {"env": "A1Conditional (hook path)" if args.hook else "FusedA1Env", "envs_per_gpu": args.envs, "n_gpus": world,
+        out = {"env": "A1Conditional (hook path)" if args.hook else "FusedA1Env", "policy": cfg["runner"]["policy_class_name"], "envs_per_gpu": args.envs, "n_gpus": world,
                "mlp_backend": runner.alg.actor_critic.mlp_backend, "ranks_in_sync": in_sync, "param_checksum": checksum.tolist(),
                "iterations": args.iters, "steps_per_env_per_iter": cfg["runner"]["num_steps_per_env"],
                "samples_per_s": args.iters * cfg["runner"]["num_steps_per_env"] * args.envs * world / el, "seconds": el,

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SHF_ABI_VERSION 21
+#define SHF_ABI_VERSION 22
 
 #define SHF_MAX_BODIES 32 /* reported rigid bodies per articulation        */
 #define SHF_MAX_DOFS 32
@@ -765,6 +765,37 @@ int shf_lstm_cell_forward(const float* x, int32_t ldx, const float* h_prev, cons
 int shf_lstm_cell_backward_pointwise(const float* dh, const float* dc_or_null, const float* gates, const float* c_prev,
                                      const unsigned char* reset_or_null, const float* c_out, float* dgates, float* dc_prev,
                                      int32_t M, int32_t H, void* stream);
+
+/* ------------------------------------------------------------------------
+ * GRU cell step of the recurrent policy (ABI v22; csrc/shf_gru.hip): ActorCriticRecurrent's other rnn_type.
+ * torch.nn.GRU's equations and gate order (r, z, n), rho[m] = reset[m] ? 0 : 1 (one byte per row; null: all 1):
+ *   r     = sigma(x w_ir^T + (rho h_prev) w_hr^T + b_ir + b_hr)        z = sigma(x w_iz^T + (rho h_prev) w_hz^T + b_iz + b_hz)
+ *   hn    = (rho h_prev) w_hn^T + b_hn                                 n = tanh(x w_in^T + b_in + r hn)
+ *   h_out = (1 - z) n + z (rho h_prev)
+ * as one GEMM over [x | h_prev] on the matrix cores (operand scheme and precision switch of the trainer kernels above,
+ * shf_mlp_set_precision) whose epilogue is the pointwise update; the n gate's x half and h half are accumulated apart,
+ * the pre-activations are never stored.
+ *   pack     w_ih[3H, I], w_hh[3H, H] (fp32, contiguous) laid out once in fragment order in a caller-owned device buffer
+ *            of shf_gru_pack_bytes(I, H) bytes (16-byte aligned); repack whenever the weights change
+ *   x        fp32 rows of I values, row stride ldx >= I (elements); h_prev, h_out fp32 [M, H] contiguous
+ *   b_ih, b_hh  fp32 [3H] (null: zero)
+ *   gates    null, or fp32 [M, 4H]: (r, z, n, hn), kept for the backward pass
+ * h_out must not overlap h_prev / x (other blocks still read the rows being replaced) and gates must overlap nothing:
+ * overlapping ranges are refused.  A row depends on its own row of the inputs only; no atomics, no host synchronisation.
+ * backward_pointwise: from dh = dL/dh_out, the kept gates and he = rho h_prev
+ *   dn = dh (1 - z)(1 - n^2)     dz = dh (he - n) z (1 - z)     dr = dn hn r (1 - r)
+ *   dgx[M, 3H] = (dr, dz, dn)    dgh[M, 3H] = (dr, dz, dn r)    dh_direct[M, H] = dh z rho
+ * the GEMMs of the backward pass are shf_mlp_linear_backward_input (dx from dgx with w_ih; dh_prev = (dgh w_hh) rho +
+ * dh_direct) and shf_mlp_linear_backward_weight (dgx with x, dgh with he), N = 3H.
+ * Errors: shf_mlp_last_error.
+ * ---------------------------------------------------------------------- */
+int shf_gru_pack_bytes(int32_t I, int32_t H, int64_t* bytes);
+int shf_gru_pack_weights(const float* w_ih, const float* w_hh, void* pack, int32_t I, int32_t H, void* stream);
+int shf_gru_cell_forward(const float* x, int32_t ldx, const float* h_prev, const unsigned char* reset_or_null, const void* pack,
+                         const float* b_ih, const float* b_hh, float* h_out, float* gates_or_null, int32_t M, int32_t I, int32_t H,
+                         void* stream);
+int shf_gru_cell_backward_pointwise(const float* dh, const float* gates, const float* h_prev, const unsigned char* reset_or_null,
+                                    float* dgx, float* dgh, float* dh_direct, int32_t M, int32_t H, void* stream);
 
 /* PPO mini-batch loss with its gradient, one pass (rsl_rl's PPO.update loss block [EXT], which the reference's runner
  * drives: shifu/runner/policy_runner.py:52-73 with PPOConfig.algorithm, shifu/configs/policy_config.py:18-31):

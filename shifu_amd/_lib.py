@@ -100,6 +100,11 @@ _SIGS = {
     "shf_lstm_pack_weights": ([vp, vp, vp, i32, i32, vp], i32),
     "shf_lstm_cell_forward": ([vp, i32] + [vp] * 9 + [i32, i32, i32, vp], i32),
     "shf_lstm_cell_backward_pointwise": ([vp] * 8 + [i32, i32, vp], i32),
+    # GRU cell step of the recurrent policy (csrc/shf_gru.hip)
+    "shf_gru_pack_bytes": ([i32, i32, C.POINTER(i64)], i32),
+    "shf_gru_pack_weights": ([vp, vp, vp, i32, i32, vp], i32),
+    "shf_gru_cell_forward": ([vp, i32] + [vp] * 7 + [i32, i32, i32, vp], i32),
+    "shf_gru_cell_backward_pointwise": ([vp] * 7 + [i32, i32, vp], i32),
 }
 EXPORTS = sorted(list(_SIGS) + ["shf_last_error", "shf_mlp_last_error", "shf_conv_last_error"])
 

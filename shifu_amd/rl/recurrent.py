@@ -7,11 +7,11 @@ mini-batch from the hidden state the rollout began with, and multiplies h and c 
 step t >= 1.  That is exact: rsl_rl zeroes the hidden state of finished envs after every step, so the state a trajectory
 starts from is either zero or the carried state at t = 0 (tests/test_rl_recurrent.py against split-and-pad).
 
-`Memory` holds a stock nn.LSTM / nn.GRU named `rnn` (rsl_rl's state_dict keys: memory_a.rnn.weight_ih_l0, ...).  LSTM on
-CUDA fp32 tensors can run on the fused cell kernel of csrc/shf_lstm.hip (`fused=True`): one launch per layer and time
-step, the pointwise update in the GEMM's epilogue, one autograd node per cell step.  Everything else -- CPU tensors, GRU,
-other dtypes -- steps the stock module one time step at a time with the same reset multiplication: same maths, no native
-calls."""
+`Memory` holds a stock nn.LSTM / nn.GRU named `rnn` (rsl_rl's state_dict keys: memory_a.rnn.weight_ih_l0, ...).  On CUDA
+fp32 tensors both can run on a fused cell kernel (`fused=True`) -- csrc/shf_lstm.hip for the LSTM, csrc/shf_gru.hip for
+the GRU: one launch per layer and time step, the pointwise update in the GEMM's epilogue, one autograd node per cell
+step.  Everything else -- CPU tensors, other dtypes, bias=False -- steps the stock module one time step at a time with
+the same reset multiplication: same maths, no native calls."""
 import ctypes as C
 
 import torch
@@ -103,6 +103,89 @@ def lstm_cell(x, h_prev, c_prev, reset, w_ih, w_hh, b_ih, b_hh, pack=None):
     return _LstmCellFn.apply(x, h_prev, c_prev, reset, w_ih, w_hh, b_ih, b_hh, pack)
 
 
+class _GruCellFn(torch.autograd.Function):
+    """One GRU cell step on shf_gru_cell_forward; backward = the pointwise kernel + the MLP layers' gradient GEMMs on the
+    raw weights (N = 3H).  `reset`: uint8 (M,), nonzero rows take h_prev = 0 (or None)."""
+
+    @staticmethod
+    def forward(ctx, x, h_prev, reset, w_ih, w_hh, b_ih, b_hh, pack):
+        L = ml.lib()
+        x, h_prev = x.contiguous(), h_prev.contiguous()
+        M, I = x.shape
+        H = h_prev.shape[1]
+        need = any(ctx.needs_input_grad)
+        with torch.cuda.device(x.device):
+            if pack is None:
+                pack = pack_gru_weights(w_ih, w_hh)
+            h = torch.empty_like(h_prev)
+            gates = torch.empty(M, 4 * H, device=x.device, dtype=torch.float32) if need else None      # r, z, n, hn
+            ml._check(L.shf_gru_cell_forward(ml._ptr(x), I, ml._ptr(h_prev), None if reset is None else ml._ptr(reset), ml._ptr(pack),
+                                             ml._ptr(b_ih), ml._ptr(b_hh), ml._ptr(h), None if gates is None else ml._ptr(gates),
+                                             M, I, H, ml._stream(x)))
+        if need:
+            ctx.save_for_backward(x, h_prev, reset, w_ih, w_hh, gates)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        L = ml.lib()
+        x, h_prev, reset, w_ih, w_hh, gates = ctx.saved_tensors
+        M, I = x.shape
+        H = h_prev.shape[1]
+        dh = dh.contiguous()
+        dgx = torch.empty(M, 3 * H, device=x.device, dtype=torch.float32)
+        dgh = torch.empty_like(dgx)
+        dh_direct = torch.empty_like(h_prev)
+        rp = None if reset is None else ml._ptr(reset)
+        keep = None if reset is None else (1.0 - reset.to(torch.float32)).unsqueeze(1)
+        dx = dh_prev = dw_ih = dw_hh = db_ih = db_hh = None
+        with torch.cuda.device(x.device):
+            st = ml._stream(x)
+            ml._check(L.shf_gru_cell_backward_pointwise(ml._ptr(dh), ml._ptr(gates), ml._ptr(h_prev), rp, ml._ptr(dgx), ml._ptr(dgh),
+                                                        ml._ptr(dh_direct), M, H, st))
+            if ctx.needs_input_grad[0]:
+                dx = torch.empty_like(x)
+                ml._check(L.shf_mlp_linear_backward_input(ml._ptr(dgx), None, ml._ptr(w_ih), ml._ptr(dx), M, I, 3 * H, st))
+            if ctx.needs_input_grad[1]:
+                dh_prev = torch.empty_like(h_prev)
+                ml._check(L.shf_mlp_linear_backward_input(ml._ptr(dgh), None, ml._ptr(w_hh), ml._ptr(dh_prev), M, H, 3 * H, st))
+                if keep is not None:
+                    dh_prev = dh_prev * keep
+                dh_prev = dh_prev + dh_direct
+            if any(ctx.needs_input_grad[3:7]):
+                def workspace(K):
+                    n = C.c_int64()
+                    ml._check(L.shf_mlp_backward_weight_workspace(M, K, 3 * H, C.byref(n)))
+                    return torch.empty(n.value, device=x.device, dtype=torch.float32)
+                dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
+                db_ih = torch.empty(3 * H, device=x.device, dtype=torch.float32)
+                db_hh = torch.empty_like(db_ih)
+                ml._check(L.shf_mlp_linear_backward_weight(ml._ptr(dgx), None, ml._ptr(x), ml._ptr(dw_ih), ml._ptr(db_ih), ml._ptr(workspace(I)),
+                                                           M, I, 3 * H, st))
+                h_eff = h_prev if keep is None else h_prev * keep
+                ml._check(L.shf_mlp_linear_backward_weight(ml._ptr(dgh), None, ml._ptr(h_eff), ml._ptr(dw_hh), ml._ptr(db_hh), ml._ptr(workspace(H)),
+                                                           M, H, 3 * H, st))
+        return dx, dh_prev, None, dw_ih, dw_hh, db_ih, db_hh, None
+
+
+def pack_gru_weights(w_ih, w_hh, out=None):
+    """[W_ih | W_hh] in the GRU cell kernel's fragment order (shf_gru_pack_weights); `out`: a kept buffer to refill."""
+    H, I = w_hh.shape[1], w_ih.shape[1]
+    with torch.cuda.device(w_ih.device):
+        if out is None:
+            n = C.c_int64()
+            ml._check(ml.lib().shf_gru_pack_bytes(I, H, C.byref(n)))
+            out = torch.empty(n.value, device=w_ih.device, dtype=torch.uint8)
+        ml._check(ml.lib().shf_gru_pack_weights(ml._ptr(w_ih), ml._ptr(w_hh), ml._ptr(out), I, H, ml._stream(w_ih)))
+    return out
+
+
+def gru_cell(x, h_prev, reset, w_ih, w_hh, b_ih, b_hh, pack=None):
+    """h of one fused GRU cell step (CUDA fp32; `reset` uint8 (M,) or None; `pack` from pack_gru_weights or None)."""
+    ml._apply_env_precision()
+    return _GruCellFn.apply(x, h_prev, reset, w_ih, w_hh, b_ih, b_hh, pack)
+
+
 class Memory(nn.Module):
     """The RNN in front of an MLP.  Step mode (`forward(x)`, x (N, D)) advances the module's own hidden state, kept in
     fixed buffers (state, next state, copy back) so that addresses are stable under graph capture; sequence mode
@@ -117,7 +200,7 @@ class Memory(nn.Module):
         kind = type.lower()
         if kind not in ("lstm", "gru"):
             raise ValueError(f"rnn_type '{type}': 'lstm' or 'gru'")
-        self.kind, self.fused = kind, bool(fused) and kind == "lstm"
+        self.kind, self.fused = kind, bool(fused)
         self.rnn = (nn.LSTM if kind == "lstm" else nn.GRU)(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers)
         self.hidden_states = None          # tuple of (num_layers, N, H) tensors: (h, c) for LSTM, (h,) for GRU
         self._next = None
@@ -132,8 +215,9 @@ class Memory(nn.Module):
         with torch.no_grad():
             if self._pack is None or self._pack[0].device != w.device:
                 self._pack = [None] * self.rnn.num_layers
+            pack_weights = pack_lstm_weights if self.kind == "lstm" else pack_gru_weights
             for l in range(self.rnn.num_layers):
-                self._pack[l] = pack_lstm_weights(getattr(self.rnn, f"weight_ih_l{l}"), getattr(self.rnn, f"weight_hh_l{l}"), self._pack[l])
+                self._pack[l] = pack_weights(getattr(self.rnn, f"weight_ih_l{l}"), getattr(self.rnn, f"weight_hh_l{l}"), self._pack[l])
         self._pack_valid = True
 
     def invalidate_pack(self):
@@ -194,10 +278,15 @@ class Memory(nn.Module):
             inp = x
             packs = self._pack if (self._pack_valid and not torch.is_grad_enabled()) else None
             for l in range(self.rnn.num_layers):
-                h, c = lstm_cell(inp, state[0][l], state[1][l], None, *self._layer_params(l), None if packs is None else packs[l])
+                pack = None if packs is None else packs[l]
+                if self.kind == "lstm":
+                    h, c = lstm_cell(inp, state[0][l], state[1][l], None, *self._layer_params(l), pack)
+                else:
+                    h, c = gru_cell(inp, state[0][l], None, *self._layer_params(l), pack), None
                 with torch.no_grad():
                     nxt[0][l].copy_(h)
-                    nxt[1][l].copy_(c)
+                    if c is not None:
+                        nxt[1][l].copy_(c)
                 inp = h
             out = inp
         else:
@@ -223,12 +312,15 @@ class Memory(nn.Module):
         if self._use_kernel(obs):
             rb = dones.to(torch.uint8)
             h = [init[0][l] for l in range(self.rnn.num_layers)]
-            c = [init[1][l] for l in range(self.rnn.num_layers)]
+            c = [init[1][l] for l in range(self.rnn.num_layers)] if self.kind == "lstm" else None
             for t in range(T):
                 reset = None if t == 0 else rb[t - 1].contiguous()
                 inp = obs[t]
                 for l in range(self.rnn.num_layers):
-                    h[l], c[l] = lstm_cell(inp, h[l], c[l], reset, *self._layer_params(l))
+                    if self.kind == "lstm":
+                        h[l], c[l] = lstm_cell(inp, h[l], c[l], reset, *self._layer_params(l))
+                    else:
+                        h[l] = gru_cell(inp, h[l], reset, *self._layer_params(l))
                     inp = h[l]
                 outs.append(inp)
             return torch.cat(outs, dim=0)
@@ -256,9 +348,10 @@ class ActorCriticRecurrent(ActorCritic):
         super().__init__(rnn_hidden_size, rnn_hidden_size, num_actions, actor_hidden_dims=actor_hidden_dims,
                          critic_hidden_dims=critic_hidden_dims, activation=activation, init_noise_std=init_noise_std,
                          mlp_backend=mlp_backend)
-        # the fused cell goes with the MFMA layers: its step is 3.3 x the stock one's at the A1 widths;
-        # rnn_fused=False keeps the stock LSTM next to them (tools/bench_recurrent.py's comparison)
-        fused = self.mlp_backend == "mfma" if rnn_fused is None else bool(rnn_fused)
+        # the fused LSTM cell goes with the MFMA layers: its step is 3.3 x the stock one's at the A1 widths;
+        # rnn_fused=False keeps the stock LSTM next to them (tools/bench_recurrent.py's comparison).  The fused GRU cell
+        # (csrc/shf_gru.hip) is chosen with rnn_fused=True only: None keeps the stock nn.GRU
+        fused = (self.mlp_backend == "mfma" and rnn_type.lower() == "lstm") if rnn_fused is None else bool(rnn_fused)
         self.memory_a = Memory(num_actor_obs, type=rnn_type, num_layers=rnn_num_layers, hidden_size=rnn_hidden_size, fused=fused)
         self.memory_c = Memory(num_critic_obs, type=rnn_type, num_layers=rnn_num_layers, hidden_size=rnn_hidden_size, fused=fused)
 

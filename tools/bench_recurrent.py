@@ -1,5 +1,6 @@
 """Recurrent-policy benchmark: the fused LSTM cell step (csrc/shf_lstm.hip) against the stock torch.nn.LSTM in the same
-process, at the A1 widths (259 -> 512, one layer).  Times, per call:
+process, at the A1 widths (259 -> 512, one layer); --rnn gru: the fused GRU cell step (csrc/shf_gru.hip) against the
+stock torch.nn.GRU, same rows.  Times, per call:
 
     fused_cell / stock_cell      one cell step under no_grad at --rows rows: the kernel with the kept pack / nn.LSTM on a
                                  one-step sequence (no state copy-back in either)
@@ -10,7 +11,7 @@ process, at the A1 widths (259 -> 512, one layer).  Times, per call:
 Each figure is the median over --blocks blocks of --reps calls between device events, the candidates' blocks interleaved,
 with the min .. max of the blocks as spread.  One JSON line.
 
-    python tools/bench_recurrent.py
+    python tools/bench_recurrent.py [--rnn gru]
 """
 import argparse
 import json
@@ -42,12 +43,12 @@ def timed(calls, blocks, reps, warmup):
     return {k: dict(ms=round(statistics.median(v), 4), min=round(min(v), 4), max=round(max(v), 4)) for k, v in times.items()}
 
 
-def make_update(fused, T, mb, nmb, I, H, dev):
+def make_update(fused, T, mb, nmb, I, H, dev, rnn="lstm"):
     import torch
     from shifu_amd.rl import PPO, ActorCriticRecurrent
     torch.manual_seed(0)
     ac = ActorCriticRecurrent(I, I, 12, actor_hidden_dims=[512, 256, 128], critic_hidden_dims=[512, 256, 128], rnn_hidden_size=H,
-                              mlp_backend="mfma", rnn_fused=fused)
+                              mlp_backend="mfma", rnn_fused=fused, rnn_type=rnn)
     alg = PPO(ac, num_learning_epochs=1, num_mini_batches=nmb, device=dev, learning_rate=1e-4, schedule="fixed")
     N = mb * nmb
     alg.init_storage(N, T, [I], [None], [12])
@@ -73,37 +74,46 @@ def main():
     ap.add_argument("--blocks", type=int, default=15)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--rnn", choices=["lstm", "gru"], default="lstm")
     a = ap.parse_args()
     import torch
     from shifu_amd.rl import Memory
-    from shifu_amd.rl.recurrent import lstm_cell
+    from shifu_amd.rl.recurrent import gru_cell, lstm_cell
     dev = "cuda:0"
     torch.manual_seed(0)
     M, I, H = a.rows, a.inputs, a.hidden
-    fused = Memory(I, hidden_size=H, fused=True).to(dev)
-    stock = Memory(I, hidden_size=H, fused=False).to(dev)
+    fused = Memory(I, type=a.rnn, hidden_size=H, fused=True).to(dev)
+    stock = Memory(I, type=a.rnn, hidden_size=H, fused=False).to(dev)
     stock.load_state_dict(fused.state_dict())
     x = torch.randn(M, I, device=dev)
     h0, c0 = torch.randn(1, M, H, device=dev) * 0.5, torch.rand(1, M, H, device=dev) * 2 - 1
     fused.refresh_pack()
     params = fused._layer_params(0)
+    if a.rnn == "lstm":
+        fused_cell = lambda: lstm_cell(x, h0[0], c0[0], None, *params, fused._pack[0])
+        stock_cell = lambda: stock.rnn(x.unsqueeze(0), (h0, c0))
+    else:
+        fused_cell = lambda: gru_cell(x, h0[0], None, *params, fused._pack[0])
+        stock_cell = lambda: stock.rnn(x.unsqueeze(0), h0)
     with torch.no_grad():
-        hf, cf = lstm_cell(x, h0[0], c0[0], None, *params, fused._pack[0])
-        out, (hs, cs) = stock.rnn(x.unsqueeze(0), (h0, c0))
-        diff = max(float((hf - hs[0]).abs().max()), float((cf - cs[0]).abs().max()))
+        if a.rnn == "lstm":
+            hf, cf = fused_cell()
+            out, (hs, cs) = stock_cell()
+            diff = max(float((hf - hs[0]).abs().max()), float((cf - cs[0]).abs().max()))
+        else:
+            diff = float((fused_cell() - stock_cell()[1][0]).abs().max())
 
         def no_grad(fn):
             def run():
                 with torch.no_grad():
                     return fn()
             return run
-        cell = timed({"fused_cell": no_grad(lambda: lstm_cell(x, h0[0], c0[0], None, *params, fused._pack[0])),
-                      "stock_cell": no_grad(lambda: stock.rnn(x.unsqueeze(0), (h0, c0))),
+        cell = timed({"fused_cell": no_grad(fused_cell), "stock_cell": no_grad(stock_cell),
                       "fused_step": no_grad(lambda: fused(x)), "stock_step": no_grad(lambda: stock(x))}, a.blocks, a.reps, a.warmup)
-    upd = {k: make_update(k == "fused_update", a.steps, a.mb_envs, a.minibatches, I, H, dev) for k in ("fused_update", "stock_update")}
+    upd = {k: make_update(k == "fused_update", a.steps, a.mb_envs, a.minibatches, I, H, dev, a.rnn) for k in ("fused_update", "stock_update")}
     update = timed({k: alg.update for k, alg in upd.items()}, max(3, a.blocks // 3), 2, 2)
-    flop = 2.0 * M * (I + H) * 4 * H
-    print(json.dumps(dict(bench="recurrent", rows=M, inputs=I, hidden=H, blocks=a.blocks, reps=a.reps, ms_per_call=cell,
+    flop = 2.0 * M * (I + H) * (4 if a.rnn == "lstm" else 3) * H
+    print(json.dumps(dict(bench="recurrent", **({} if a.rnn == "lstm" else {"rnn": a.rnn}), rows=M, inputs=I, hidden=H, blocks=a.blocks, reps=a.reps, ms_per_call=cell,
                           speedup_fused_vs_stock_cell=round(cell["stock_cell"]["ms"] / cell["fused_cell"]["ms"], 2),
                           fused_cell_tflops=round(flop / (cell["fused_cell"]["ms"] * 1e-3) / 1e12, 1),
                           fused_vs_stock_max_abs_diff=float(f"{diff:.3g}"),

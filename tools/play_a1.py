@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--policy", choices=["mlp", "recurrent"], default="mlp", help="the policy class the checkpoint was trained with (tools/train_a1.py --policy)")
     ap.add_argument("--rnn-hidden", type=int, default=512)
     ap.add_argument("--rnn-layers", type=int, default=1)
+    ap.add_argument("--rnn-type", choices=["lstm", "gru"], default="lstm", help="--policy recurrent: the checkpoint's rnn_type")
     ap.add_argument("--max-contacts", type=int, default=None, help="ShfSimParams.max_contacts (pgs): 8 (default) .. 16")
     args = ap.parse_args()
     from examples.a1_conditional.task_config import A1PPOConfig
@@ -39,7 +40,7 @@ def main():
     cfg = class_to_dict(A1PPOConfig())
     if args.policy == "recurrent":
         cfg["runner"]["policy_class_name"] = "ActorCriticRecurrent"
-        cfg["policy"].update({"rnn_type": "lstm", "rnn_hidden_size": args.rnn_hidden, "rnn_num_layers": args.rnn_layers})
+        cfg["policy"].update({"rnn_type": args.rnn_type, "rnn_hidden_size": args.rnn_hidden, "rnn_num_layers": args.rnn_layers})
     runner = OnPolicyRunner(env, cfg, log_dir=None, device="cuda:0")
     infos = runner.load(args.checkpoint, load_optimizer=False)
     trained = (infos or {}).get("contact_solver") if isinstance(infos, dict) else None

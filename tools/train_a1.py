@@ -28,7 +28,10 @@ def main():
     ap.add_argument("--mlp", choices=["torch", "mfma"], default=None,
                     help="ActorCritic layers: stock fp32 library GEMMs, or the hand-written MFMA kernels (csrc/shf_mlp.hip)")
     ap.add_argument("--policy", choices=["mlp", "recurrent"], default="mlp",
-                    help="mlp: the feed-forward ActorCritic; recurrent: ActorCriticRecurrent (an LSTM in front of each MLP, rl/recurrent.py)")
+                    help="mlp: the feed-forward ActorCritic; recurrent: ActorCriticRecurrent (an LSTM or GRU in front of each MLP, rl/recurrent.py)")
+    ap.add_argument("--rnn-type", choices=["lstm", "gru"], default="lstm", help="--policy recurrent: rnn_type")
+    ap.add_argument("--rnn-fused", action="store_true",
+                    help="--policy recurrent: rnn_fused=True, the fused cell kernel (the LSTM's default under --mlp mfma; the GRU's only with this flag)")
     ap.add_argument("--rnn-hidden", type=int, default=512, help="--policy recurrent: rnn_hidden_size")
     ap.add_argument("--rnn-layers", type=int, default=1, help="--policy recurrent: rnn_num_layers")
     ap.add_argument("--eager-update", action="store_true", help="with --graph: capture the rollout only, launch the PPO update eagerly")
@@ -67,7 +70,9 @@ def main():
         cfg["policy"]["mlp_backend"] = args.mlp
     if args.policy == "recurrent":
         cfg["runner"]["policy_class_name"] = "ActorCriticRecurrent"
-        cfg["policy"].update({"rnn_type": "lstm", "rnn_hidden_size": args.rnn_hidden, "rnn_num_layers": args.rnn_layers})
+        cfg["policy"].update({"rnn_type": args.rnn_type, "rnn_hidden_size": args.rnn_hidden, "rnn_num_layers": args.rnn_layers})
+        if args.rnn_fused:
+            cfg["policy"]["rnn_fused"] = True
     set_seed((A1PPOConfig.seed if args.seed is None else args.seed) + rank)
     if args.hook:
         from examples.a1_conditional.a1_conditional import A1Conditional

@@ -968,6 +968,24 @@ int shf_render_cameras(const ShfRenderScene* scene_dev, const ShfTerrain* terrai
                        const int32_t* seg_ids, const float* colors, float* depth_or_null, int32_t* seg_or_null,
                        uint8_t* rgba_or_null, void* stream);
 
+/* Optical flow from the same cast (csrc/shf_render.hip, header comment).  A purely additive entry: it was
+ * added without a new SHF_ABI_VERSION, no struct layout changed, and shf_render_cameras is as it was.  Every argument of
+ * shf_render_cameras in its place, then: prev_body_pose (num_envs * num_bodies, 7) and prev_cam_pose (num_envs, 7), the
+ * body and camera poses (pos + quat xyzw) of this camera's previous flow render; prev_valid (num_envs) int32, 0 = the env
+ * has no usable previous frame and its flow is zero; flow (num_envs, H, W, 2) f32, (u, v) in pixels, u to the right, v
+ * downwards: where the surface point is now minus where it was at the previous render (backward-looking); flow_i16
+ * (num_envs, H, W, 2) int16, Isaac Gym's encoding q_u = sat16(rint(u 32768 / W)), q_v = sat16(rint(v 32768 / H)), u first.
+ * Flow is exactly +0.0 where nothing is hit, where the point was behind the previous camera or a term is not finite, where
+ * prev_valid is 0, and where neither the hit body's pose nor the camera's changed bits (the terrain never moves).  Isaac
+ * Gym's own sign and direction conventions are not known (a closed binary): no parity with them is claimed.  depth / seg /
+ * rgba are written as shf_render_cameras writes them, bit for bit.  With both flow outputs NULL the call is
+ * shf_render_cameras.  flow must be 8-byte and flow_i16 4-byte aligned.  No atomics, no host sync: capturable. */
+int shf_render_cameras_flow(const ShfRenderScene* scene_dev, const ShfTerrain* terrain, const int16_t* height_samples_dev,
+                            const ShfCamera* camera, int32_t num_envs, const float* body_state, const float* cam_pose,
+                            const int32_t* seg_ids, const float* colors, float* depth_or_null, int32_t* seg_or_null,
+                            uint8_t* rgba_or_null, const float* prev_body_pose, const float* prev_cam_pose,
+                            const int32_t* prev_valid, float* flow_or_null, int16_t* flow_i16_or_null, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,8 @@ _SIGS = {
     "shf_ppo_loss": ([vp] * 10 + [i64, i32, C.c_float, C.c_float, C.c_float, i32] + [vp] * 6, i32),
     # camera sensors (csrc/shf_render.hip)
     "shf_render_cameras": ([vp, C.POINTER(_abi.ShfTerrain), vp, C.POINTER(_abi.ShfCamera), i32] + [vp] * 7 + [vp], i32),
+    # ... with optical flow: the same arguments, then prev_body_pose, prev_cam_pose, prev_valid, flow, flow_i16, stream
+    "shf_render_cameras_flow": ([vp, C.POINTER(_abi.ShfTerrain), vp, C.POINTER(_abi.ShfCamera), i32] + [vp] * 7 + [vp] * 5 + [vp], i32),
     # conv-encoder inference (csrc/shf_conv.hip)
     "shf_conv_pack_bytes": ([i32, i32, C.POINTER(i64)], i32),
     "shf_conv_pack_weights": ([vp, vp, i32, i32, vp], i32),

@@ -88,6 +88,10 @@ BUDGETS = [("_Z16k_a1_step_a1_g32", 256, 0),          # default: A1, two envs pe
            # its warped-trimesh form (a kernel of its own name: the height-field form stays the one k_render_cameras): the walk plus
            # the cell search with its per-cell vertex arrays unrolled into registers
            ("_Z19k_render_cameras_tw", 128, 0),
+           # their optical-flow forms (kernels of their own names again; the two above keep their code): 70 and 85 registers in
+           # the first clean build (the motion table sits in LDS; the previous camera's basis and the projection live only
+           # after the nearest hit is chosen) plus a margin of 10 -- 7 and 5 waves per SIMD; nothing on the stack
+           ("_Z21k_render_cameras_flow", 80, 0), ("_Z24k_render_cameras_tw_flow", 95, 0),
            # the conv-encoder layer (csrc/shf_conv.hip), every instantiation: 214 registers at most in the first clean build (64
            # accumulators, a chunk's weight fragments, the gathered rows in flight) plus a margin of 10 for compiler drift -- still
            # two waves per SIMD; nothing on the stack

@@ -11,6 +11,24 @@
 // world poses are built once per workgroup into LDS (one thread per shape); each wave then culls the shapes' bounding
 // spheres against the cone of its strip's rays (one lane per shape, a ballot), so the loop over candidate shapes is
 // wave-uniform and its LDS reads are broadcasts.  Stores are one dword per lane per image, 64 consecutive bytes per row.
+//
+// Optical flow (FLOW form, kernels k_render_cameras_flow / k_render_cameras_tw_flow behind shf_render_cameras_flow): the
+// caster knows the surface point X = o + s d and the body b behind every pixel, so ground-truth flow is one rigid transform
+// and one projection per pixel.  The point as it was at the previous flow render is X' = p_b' + R_b' R_b^T (X - p_b) (primed:
+// the previous render's body pose; the terrain is static, X' = X); projected into the previous camera pose (o', q') with the
+// pixel-ray convention above: z' = fwd'.(X' - o'), x' = right'.(X' - o') / (z' t), y' = up'.(X' - o') / (z' t H/W),
+// c' = (x' + 1) W/2 - 1/2, r' = (1 - y') H/2 - 1/2, and flow = (c - c', r - r') in pixels, u to the right, v downwards --
+// the backward-looking motion vector, where the point is now minus where it was.  Flow is exactly +0.0 where nothing is
+// hit, where z' <= 0 or a term is not finite, where prev_valid[env] == 0, and where neither the hit body's pose (7 floats,
+// compared as bits) nor the camera's changed bits since the previous render (a static scene is exactly zero, not float32
+// noise).  The integer image is Isaac Gym's encoding, q_u = sat16(rint(u 32768 / W)), q_v = sat16(rint(v 32768 / H)), u in
+// the low half of the pixel's dword.  Isaac Gym's own sign and direction conventions are a closed binary: no parity with
+// it is claimed.  The staging phase also builds, per shape, the body's motion transform Rm = R_b' R_b^T and tm (12 floats in
+// a second LDS table, 3 KB) RELATIVE TO THE CAMERA ORIGIN o -- X' - o = Rm (X - o) + tm, tm = (p_b' - o) - Rm (p_b - o) --
+// because envs sit tens of metres out on the terrain and X' - X is a small difference; and a per-shape `moved` flag.  The
+// per-pixel flow work comes after the nearest hit is chosen (one 3 x 3 transform, three dot products), not in the candidate
+// loop; depth / segmentation / color come from the same cast and are bit-equal to the plain kernels'.  The checker is
+// tests/flow_ref.py.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -24,6 +42,7 @@ int shf_set_error(const std::string& msg);   // shf_api.hip
 #define RT_TILE 16
 #define RT_THREADS 256
 #define RT_SW 20   // floats per shape in LDS: c[3] R[9] param[3] radius col[3] pad
+#define RT_MW 12   // FLOW: floats per shape in the motion table: Rm[9] tm[3]
 
 namespace {
 
@@ -261,15 +280,24 @@ __device__ __forceinline__ uint32_t shade_u8(float c, float lam) {
 
 // TW: the terrain is a warped trimesh (hsamp: samples followed by one byte per vertex).  The two forms are two kernels
 // (k_render_cameras, k_render_cameras_tw below); the host launches the TW one only when ShfTerrain.warped, so height fields
-// and planes keep their code and registers.
-template <bool TW>
+// and planes keep their code and registers.  FLOW: the optical-flow form (header comment), again kernels of their own names
+// (k_render_cameras_flow, k_render_cameras_tw_flow): everything it adds sits behind if constexpr, so the plain kernels keep
+// their code.
+template <bool TW, bool FLOW>
 __device__ __forceinline__ void render_cameras(const ShfRenderScene* __restrict__ scene, const ShfTerrain& T,
                                                const int16_t* __restrict__ hsamp, const ShfCamera& cam, int tiles_x, int tiles,
                                                const float* __restrict__ body_state, const float* __restrict__ cam_pose,
                                                const int32_t* __restrict__ seg_ids, const float* __restrict__ colors,
-                                               float* __restrict__ depth, int32_t* __restrict__ seg_out, uint32_t* __restrict__ rgba) {
+                                               float* __restrict__ depth, int32_t* __restrict__ seg_out, uint32_t* __restrict__ rgba,
+                                               const float* __restrict__ prev_body_pose = nullptr,
+                                               const float* __restrict__ prev_cam_pose = nullptr,
+                                               const int32_t* __restrict__ prev_valid = nullptr, float2* __restrict__ flow = nullptr,
+                                               uint32_t* __restrict__ flow_i16 = nullptr) {
   __shared__ float S[SHF_RENDER_MAX_SHAPES * RT_SW];
   __shared__ int SI[SHF_RENDER_MAX_SHAPES * 3];   // kind, poly, segmentation id
+  // FLOW: per shape, the body's motion since the previous render about the camera origin, and whether its pose changed bits
+  __shared__ float SM[FLOW ? SHF_RENDER_MAX_SHAPES * RT_MW : 1];
+  __shared__ int SMV[FLOW ? SHF_RENDER_MAX_SHAPES : 1];
   const int env = blockIdx.x / tiles, tile = blockIdx.x - env * tiles;
   const int tx = tile % tiles_x, ty = tile / tiles_x;
   const int lid = threadIdx.x, wave = lid >> 6, lane = lid & 63;
@@ -310,6 +338,27 @@ __device__ __forceinline__ void render_cameras(const ShfRenderScene* __restrict_
     SI[lid * 3] = sh.kind;
     SI[lid * 3 + 1] = sh.poly;
     SI[lid * 3 + 2] = seg_ids[row];
+    if constexpr (FLOW) {
+      const float* pb = prev_body_pose + row * 7;
+      bool mv = false;
+      for (int k = 0; k < 7; k++) mv = mv || __float_as_uint(pb[k]) != __float_as_uint(bsr[k]);
+      float* m = SM + lid * RT_MW;
+      if (mv) {
+        float Rp[9];
+        {
+          const float q[4] = {pb[3], pb[4], pb[5], pb[6]};
+          quat_mat(q, Rp);
+        }
+        const float rel[3] = {bsr[0] - o[0], bsr[1] - o[1], bsr[2] - o[2]};
+        for (int r = 0; r < 3; r++) {
+          for (int c = 0; c < 3; c++) m[3 * r + c] = Rp[3 * r] * Rb[3 * c] + Rp[3 * r + 1] * Rb[3 * c + 1] + Rp[3 * r + 2] * Rb[3 * c + 2];
+          m[9 + r] = (pb[r] - o[r]) - (m[3 * r] * rel[0] + m[3 * r + 1] * rel[1] + m[3 * r + 2] * rel[2]);
+        }
+      } else {
+        for (int k = 0; k < RT_MW; k++) m[k] = (k == 0 || k == 4 || k == 8) ? 1.0f : 0.0f;
+      }
+      SMV[lid] = mv ? 1 : 0;
+    }
   }
   __syncthreads();
 
@@ -438,6 +487,44 @@ __device__ __forceinline__ void render_cameras(const ShfRenderScene* __restrict_
     }
     rgba[px_i] = pix;
   }
+  if constexpr (FLOW) {
+    float fu = 0.0f, fv = 0.0f;
+    if (any && prev_valid[env] != 0) {
+      // the previous camera: its basis as the current one's above, its origin relative to the current one's
+      const float* pc = prev_cam_pose + (size_t)env * 7;
+      bool moved = false;
+      for (int k = 0; k < 7; k++) moved = moved || __float_as_uint(pc[k]) != __float_as_uint(cp[k]);
+      // X' - o: the hit point about the camera origin, carried by its body's motion (the terrain: as it is)
+      float v[3] = {best * d[0], best * d[1], best * d[2]};
+      if (!ground_hit && best_i >= 0) {
+        const float* m = SM + best_i * RT_MW;
+        moved = moved || SMV[best_i] != 0;
+        const float x[3] = {v[0], v[1], v[2]};
+        for (int k = 0; k < 3; k++) v[k] = (m[3 * k] * x[0] + m[3 * k + 1] * x[1] + m[3 * k + 2] * x[2]) + m[9 + k];
+      }
+      if (moved) {
+        float Rp[9];
+        {
+          const float q[4] = {pc[3], pc[4], pc[5], pc[6]};
+          quat_mat(q, Rp);
+        }
+        for (int k = 0; k < 3; k++) v[k] -= pc[k] - o[k];
+        const float fwdp[3] = {Rp[0], Rp[3], Rp[6]}, rightp[3] = {-Rp[1], -Rp[4], -Rp[7]}, upp[3] = {Rp[2], Rp[5], Rp[8]};
+        const float zp = dot3(fwdp, v);
+        const float xp = dot3(rightp, v) / (zp * t), yp = dot3(upp, v) / (zp * ty_scale);
+        const float cpx = (xp + 1.0f) * (0.5f * (float)W) - 0.5f, rpx = (1.0f - yp) * (0.5f * (float)Hh) - 0.5f;
+        const float u = (float)col - cpx, w = (float)rowp - rpx;
+        if (zp > 0.0f && isfinite(u) && isfinite(w)) { fu = u; fv = w; }
+      }
+    }
+    if (flow) flow[px_i] = make_float2(fu, fv);
+    if (flow_i16) {
+      // Isaac Gym's encoding: u x 32768 is exact, one correctly rounded division, round half to even, saturate
+      const float qu = fminf(fmaxf(rintf((fu * 32768.0f) / (float)W), -32768.0f), 32767.0f);
+      const float qv = fminf(fmaxf(rintf((fv * 32768.0f) / (float)Hh), -32768.0f), 32767.0f);
+      flow_i16[px_i] = ((uint32_t)(int)qu & 0xffffu) | ((uint32_t)(int)qv << 16);
+    }
+  }
 }
 
 #define RT_KERNEL_ARGS                                                                                                          \
@@ -446,35 +533,83 @@ __device__ __forceinline__ void render_cameras(const ShfRenderScene* __restrict_
       const float *__restrict__ colors, float *__restrict__ depth, int32_t *__restrict__ seg_out, uint32_t *__restrict__ rgba
 
 __global__ void __launch_bounds__(RT_THREADS) k_render_cameras(RT_KERNEL_ARGS) {
-  render_cameras<false>(scene, T, hsamp, cam, tiles_x, tiles, body_state, cam_pose, seg_ids, colors, depth, seg_out, rgba);
+  render_cameras<false, false>(scene, T, hsamp, cam, tiles_x, tiles, body_state, cam_pose, seg_ids, colors, depth, seg_out, rgba);
 }
 __global__ void __launch_bounds__(RT_THREADS) k_render_cameras_tw(RT_KERNEL_ARGS) {
-  render_cameras<true>(scene, T, hsamp, cam, tiles_x, tiles, body_state, cam_pose, seg_ids, colors, depth, seg_out, rgba);
+  render_cameras<true, false>(scene, T, hsamp, cam, tiles_x, tiles, body_state, cam_pose, seg_ids, colors, depth, seg_out, rgba);
+}
+
+#define RT_FLOW_KERNEL_ARGS                                                                                          \
+  RT_KERNEL_ARGS, const float *__restrict__ prev_body_pose, const float *__restrict__ prev_cam_pose,                 \
+      const int32_t *__restrict__ prev_valid, float2 *__restrict__ flow, uint32_t *__restrict__ flow_i16
+
+__global__ void __launch_bounds__(RT_THREADS) k_render_cameras_flow(RT_FLOW_KERNEL_ARGS) {
+  render_cameras<false, true>(scene, T, hsamp, cam, tiles_x, tiles, body_state, cam_pose, seg_ids, colors, depth, seg_out, rgba,
+                              prev_body_pose, prev_cam_pose, prev_valid, flow, flow_i16);
+}
+__global__ void __launch_bounds__(RT_THREADS) k_render_cameras_tw_flow(RT_FLOW_KERNEL_ARGS) {
+  render_cameras<true, true>(scene, T, hsamp, cam, tiles_x, tiles, body_state, cam_pose, seg_ids, colors, depth, seg_out, rgba,
+                             prev_body_pose, prev_cam_pose, prev_valid, flow, flow_i16);
+}
+
+// The argument checks both entries share (fn: the entry's name, the prefix of its error strings).  Returns 0 with *tiles_x /
+// *tiles set, or the error code.
+static int render_check(const char* fn, const ShfRenderScene* scene_dev, const ShfTerrain* terrain, const int16_t* height_samples_dev,
+                        const ShfCamera* camera, int32_t num_envs, int* tiles_x, int* tiles) {
+  const std::string f(fn);
+  if (!scene_dev || !terrain || !camera) return shf_set_error(f + ": null scene, terrain or camera");
+  const ShfCamera& c = *camera;
+  if (c.width <= 0 || c.height <= 0 || c.width > 16384 || c.height > 16384)
+    return shf_set_error(f + ": width and height must be in 1..16384");
+  if (!(c.horizontal_fov > 0.0f && c.horizontal_fov < 180.0f))
+    return shf_set_error(f + ": horizontal_fov must be in (0, 180) degrees");
+  if (!(c.near_plane > 0.0f && c.far_plane > c.near_plane)) return shf_set_error(f + ": need 0 < near_plane < far_plane");
+  if (terrain->warped && terrain->rows == 0) return shf_set_error(f + ": a warped (trimesh) terrain needs height samples");
+  if (terrain->rows != 0 && (terrain->rows < 2 || terrain->cols < 2 || !height_samples_dev))
+    return shf_set_error(f + ": a height field needs at least 2 x 2 samples on the device");
+  if (num_envs < 0) return shf_set_error(f + ": num_envs < 0");
+  *tiles_x = (c.width + RT_TILE - 1) / RT_TILE;
+  *tiles = *tiles_x * ((c.height + RT_TILE - 1) / RT_TILE);
+  return 0;
 }
 
 extern "C" int shf_render_cameras(const ShfRenderScene* scene_dev, const ShfTerrain* terrain, const int16_t* height_samples_dev,
                                   const ShfCamera* camera, int32_t num_envs, const float* body_state, const float* cam_pose,
                                   const int32_t* seg_ids, const float* colors, float* depth_or_null, int32_t* seg_or_null,
                                   uint8_t* rgba_or_null, void* stream) {
-  if (!scene_dev || !terrain || !camera) return shf_set_error("shf_render_cameras: null scene, terrain or camera");
-  const ShfCamera c = *camera;
-  if (c.width <= 0 || c.height <= 0 || c.width > 16384 || c.height > 16384)
-    return shf_set_error("shf_render_cameras: width and height must be in 1..16384");
-  if (!(c.horizontal_fov > 0.0f && c.horizontal_fov < 180.0f))
-    return shf_set_error("shf_render_cameras: horizontal_fov must be in (0, 180) degrees");
-  if (!(c.near_plane > 0.0f && c.far_plane > c.near_plane))
-    return shf_set_error("shf_render_cameras: need 0 < near_plane < far_plane");
-  if (terrain->warped && terrain->rows == 0)
-    return shf_set_error("shf_render_cameras: a warped (trimesh) terrain needs height samples");
-  if (terrain->rows != 0 && (terrain->rows < 2 || terrain->cols < 2 || !height_samples_dev))
-    return shf_set_error("shf_render_cameras: a height field needs at least 2 x 2 samples on the device");
-  if (num_envs < 0) return shf_set_error("shf_render_cameras: num_envs < 0");
+  int tiles_x, tiles;
+  if (const int rc = render_check("shf_render_cameras", scene_dev, terrain, height_samples_dev, camera, num_envs, &tiles_x, &tiles)) return rc;
   if (num_envs == 0 || (!depth_or_null && !seg_or_null && !rgba_or_null)) return 0;
   if (!body_state || !cam_pose || !seg_ids || !colors) return shf_set_error("shf_render_cameras: null input tensor");
-  const int tiles_x = (c.width + RT_TILE - 1) / RT_TILE, tiles = tiles_x * ((c.height + RT_TILE - 1) / RT_TILE);
   if ((int64_t)tiles * num_envs > 0x7fffffffLL) return shf_set_error("shf_render_cameras: too many envs x tiles for one launch");
   hipLaunchKernelGGL(terrain->warped ? k_render_cameras_tw : k_render_cameras, dim3((unsigned)(tiles * num_envs)),
-                     dim3(RT_THREADS), 0, (hipStream_t)stream, scene_dev, *terrain, height_samples_dev, c, tiles_x, tiles, body_state,
-                     cam_pose, seg_ids, colors, depth_or_null, seg_or_null, reinterpret_cast<uint32_t*>(rgba_or_null));
+                     dim3(RT_THREADS), 0, (hipStream_t)stream, scene_dev, *terrain, height_samples_dev, *camera, tiles_x, tiles,
+                     body_state, cam_pose, seg_ids, colors, depth_or_null, seg_or_null, reinterpret_cast<uint32_t*>(rgba_or_null));
   return hipGetLastError() == hipSuccess ? 0 : shf_set_error("shf_render_cameras: launch failed");
+}
+
+// The flow form: shf_render_cameras' arguments in their places, then the previous render's poses and the flow images.
+extern "C" int shf_render_cameras_flow(const ShfRenderScene* scene_dev, const ShfTerrain* terrain, const int16_t* height_samples_dev,
+                                       const ShfCamera* camera, int32_t num_envs, const float* body_state, const float* cam_pose,
+                                       const int32_t* seg_ids, const float* colors, float* depth_or_null, int32_t* seg_or_null,
+                                       uint8_t* rgba_or_null, const float* prev_body_pose, const float* prev_cam_pose,
+                                       const int32_t* prev_valid, float* flow_or_null, int16_t* flow_i16_or_null, void* stream) {
+  if (!flow_or_null && !flow_i16_or_null)
+    return shf_render_cameras(scene_dev, terrain, height_samples_dev, camera, num_envs, body_state, cam_pose, seg_ids, colors,
+                              depth_or_null, seg_or_null, rgba_or_null, stream);
+  int tiles_x, tiles;
+  if (const int rc = render_check("shf_render_cameras_flow", scene_dev, terrain, height_samples_dev, camera, num_envs, &tiles_x, &tiles)) return rc;
+  if (num_envs == 0) return 0;
+  if (!body_state || !cam_pose || !seg_ids || !colors) return shf_set_error("shf_render_cameras_flow: null input tensor");
+  if (!prev_body_pose || !prev_cam_pose || !prev_valid)
+    return shf_set_error("shf_render_cameras_flow: null prev_body_pose, prev_cam_pose or prev_valid");
+  if (((uintptr_t)flow_or_null & 7u) != 0 || ((uintptr_t)flow_i16_or_null & 3u) != 0)
+    return shf_set_error("shf_render_cameras_flow: flow must be 8-byte aligned and flow_i16 4-byte aligned");
+  if ((int64_t)tiles * num_envs > 0x7fffffffLL) return shf_set_error("shf_render_cameras_flow: too many envs x tiles for one launch");
+  hipLaunchKernelGGL(terrain->warped ? k_render_cameras_tw_flow : k_render_cameras_flow, dim3((unsigned)(tiles * num_envs)),
+                     dim3(RT_THREADS), 0, (hipStream_t)stream, scene_dev, *terrain, height_samples_dev, *camera, tiles_x, tiles,
+                     body_state, cam_pose, seg_ids, colors, depth_or_null, seg_or_null, reinterpret_cast<uint32_t*>(rgba_or_null),
+                     prev_body_pose, prev_cam_pose, prev_valid, reinterpret_cast<float2*>(flow_or_null),
+                     reinterpret_cast<uint32_t*>(flow_i16_or_null));
+  return hipGetLastError() == hipSuccess ? 0 : shf_set_error("shf_render_cameras_flow: launch failed");
 }

@@ -182,7 +182,7 @@ class FusedA1Env(FusedCameraHost):
         self.reward_names = REWARD_NAMES
         self.extras = {}
         self.common_step_counter = 0
-        self._init_cameras()
+        self._init_cameras(reset_count=T[_abi.A1_RESET_COUNT])
         # actors are created at default_pos + env origin (units.py:57-70 with Q14 fixed), identity pose, at rest: the
         # first reset_idx(all) then sees distance 0 and zero commands, so no env changes its terrain level (Q13)
         spawn = torch.zeros(num_envs, 13, device=self.device)
@@ -220,6 +220,7 @@ class FusedA1Env(FusedCameraHost):
 
     def reset(self):
         self.task.reset_all()
+        self._invalidate_camera_flow()            # flow cameras: no previous frame across a reset
         obs, priv, _, _, _ = self.step(torch.zeros(self.num_envs, self.num_actions, device=self.device))
         return obs, priv
 
@@ -237,6 +238,7 @@ class FusedA1Env(FusedCameraHost):
     def load_state_dict(self, sd):
         from ..checkpoint import load_env_state_dict
         load_env_state_dict(self, sd)
+        self._invalidate_camera_flow()
 
     def destroy(self):
         self.task.destroy()

@@ -110,7 +110,7 @@ class FusedAbbEnv(FusedCameraHost):
         # SHF_MAX_LINK_CONTACTS); the live device tensor, (N,) int32
         self.extras = {"dropped_contacts": S[_abi.T_DROPPED]}
         self.reward_names = REWARD_NAMES
-        self._init_cameras([tuple(b.dim) for b in self.boxes])     # add_camera (gym/fused_camera.py)
+        self._init_cameras([tuple(b.dim) for b in self.boxes], reset_count=T[_abi.ABB_RESET_COUNT])     # add_camera (gym/fused_camera.py)
         # spawn poses + the tensors Isaac Gym would show after create_actor/prepare_sim
         A = 1 + len(self.boxes)
         root = torch.zeros(num_envs * A, 13, device=self.device)
@@ -142,6 +142,7 @@ class FusedAbbEnv(FusedCameraHost):
 
     def reset(self):
         self.task.reset_all()
+        self._invalidate_camera_flow()            # flow cameras: no previous frame across a reset
         obs, priv, _, _, _ = self.step(torch.zeros(self.num_envs, 3, device=self.device))
         return obs, priv
 
@@ -159,6 +160,7 @@ class FusedAbbEnv(FusedCameraHost):
     def load_state_dict(self, sd):
         from ..checkpoint import load_env_state_dict
         load_env_state_dict(self, sd)
+        self._invalidate_camera_flow()
 
     def destroy(self):
         self.task.destroy()

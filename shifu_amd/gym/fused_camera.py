@@ -3,7 +3,13 @@ the fused step kernels write (SHF_T_BODY_STATE), one launch per render and camer
 
 The fused envs own their scene -- the articulation's render shapes (CompiledModel.render_shapes), the box actors after
 them in the body-state rows, and the terrain the env was built on, the warped trimesh included -- so cameras can be added
-at any time.  Nothing here is part of the simulation state: images are derived data (state_dict is unchanged)."""
+at any time.  Nothing here is part of the simulation state: images are derived data (state_dict is unchanged).
+
+Optical flow (add_camera(..., flow=True)): the camera keeps the body and camera poses of its previous render
+(render.FlowHistory) and renders with shf_render_cameras_flow.  The fused step kernels reset envs inside the launch, so
+whether an env's previous frame is usable is worked out on the device: an env is valid iff its reset counter
+(A1_RESET_COUNT / ABB_RESET_COUNT) still equals the value snapshotted at the previous flow render; env.reset()
+invalidates every env."""
 from __future__ import annotations
 
 from typing import Optional, Sequence
@@ -19,8 +25,8 @@ class FusedCamera:
     Attached: the pose is body pose o (position, quat) at every render (Isaac Gym's FOLLOW_TRANSFORM)."""
 
     def __init__(self, env, width: int, height: int, horizontal_fov: float, near_plane: float, far_plane: float,
-                 position, quat, attach_body: Optional[int]):
-        from ..render import camera_struct
+                 position, quat, attach_body: Optional[int], flow: bool = False):
+        from ..render import FlowHistory, camera_struct
         n, dev = env.num_envs, env.device
         self.env = env
         self.width, self.height = int(width), int(height)
@@ -38,6 +44,15 @@ class FusedCamera:
         self._images = dict(rgba=torch.zeros(n, self.height, self.width, 4, dtype=torch.uint8, device=dev),
                             depth=torch.full((n, self.height, self.width), -float("inf"), dtype=torch.float32, device=dev),
                             seg=torch.zeros(n, self.height, self.width, dtype=torch.int32, device=dev))
+        self.flow = bool(flow)
+        if self.flow:
+            self._images["flow"] = torch.zeros(n, self.height, self.width, 2, dtype=torch.float32, device=dev)
+            self._images["flow_i16"] = torch.zeros(n, self.height, self.width, 2, dtype=torch.int16, device=dev)
+            self.history = FlowHistory(n, B, dev)
+            self._count = env._cam_reset_count                   # (N,) int32, bumped by the step kernel's resets
+            self._count_seen = self._count.clone()
+            self._same = torch.zeros(n, dtype=torch.bool, device=dev)
+            self._valid = torch.zeros(n, dtype=torch.int32, device=dev)
 
     def world_pose(self) -> torch.Tensor:
         """(N, 7) camera poses (pos, quat xyzw) on the env's current body states."""
@@ -51,21 +66,44 @@ class FusedCamera:
     def render(self):
         """One launch for all envs on the body states of the last step / reset; no host sync."""
         env, im = self.env, self._images
+        if self.flow:
+            return self._render_flow()
         env._renderer.render(env.body_state, self.world_pose(), env.cam_seg, env.cam_color, self.camera, depth=im["depth"],
                              seg_out=im["seg"], rgba=im["rgba"])
         return im
 
+    def _render_flow(self):
+        """The flow launch, then this render becomes the previous one: preallocated tensors only, no host sync."""
+        env, im, h = self.env, self._images, self.history
+        pose = self.world_pose()
+        torch.eq(self._count, self._count_seen, out=self._same)       # no reset inside a step since the previous render
+        self._valid.copy_(self._same)
+        self._valid.mul_(h.prev_valid)
+        env._renderer.render(env.body_state, pose, env.cam_seg, env.cam_color, self.camera, depth=im["depth"], seg_out=im["seg"],
+                             rgba=im["rgba"], flow=im["flow"], flow_i16=im["flow_i16"], prev_body_pose=h.prev_body_pose,
+                             prev_cam_pose=h.prev_cam_pose, prev_valid=self._valid)
+        h.update(env.body_state, pose)
+        self._count_seen.copy_(self._count)
+        return im
+
+    def invalidate_flow(self, env_ids=None):
+        """The next render's flow is zero in env_ids (all by default); nothing to do on a camera without flow."""
+        if self.flow:
+            self.history.invalidate(env_ids)
+
     def raw_images(self):
         """{"rgba": (N, H, W, 4) u8, "depth": (N, H, W) f32, negative view depth, -inf where nothing is hit, "seg":
-        (N, H, W) i32} -- the tensors render() writes (CameraSensor.raw_images's conventions).  Views, not copies."""
+        (N, H, W) i32} -- the tensors render() writes (CameraSensor.raw_images's conventions).  Views, not copies.  A camera
+        added with flow=True also has "flow": (N, H, W, 2) f32, (u, v) in pixels, and "flow_i16": (N, H, W, 2) int16."""
         return self._images
 
 
 class FusedCameraHost:
     """What FusedA1Env and FusedAbbEnv share: the per-env segmentation / color tables and add_camera."""
 
-    def _init_cameras(self, box_dims: Sequence = ()):
-        """box_dims: full extents of the env's box actors, in body-state row order after the articulation's bodies."""
+    def _init_cameras(self, box_dims: Sequence = (), reset_count=None):
+        """box_dims: full extents of the env's box actors, in body-state row order after the articulation's bodies;
+        reset_count: the task's (N,) int32 per-env reset counter (what flow cameras check their previous frame against)."""
         from ..render import DEFAULT_BODY_COLOR
         self._cam_box_dims = [tuple(float(v) for v in d) for d in box_dims]
         B = int(self.cm.blob.nb) + len(self._cam_box_dims)
@@ -74,11 +112,19 @@ class FusedCameraHost:
         self.cam_color = torch.tensor(DEFAULT_BODY_COLOR, dtype=torch.float32, device=self.device).repeat(self.num_envs, B, 1)
         self.cameras = []
         self._renderer = None
+        self._cam_reset_count = reset_count
+
+    def _invalidate_camera_flow(self, env_ids=None):
+        for cam in self.cameras:
+            cam.invalidate_flow(env_ids)
 
     def add_camera(self, width: int, height: int, horizontal_fov: float, near_plane: float, far_plane: float,
-                   position=(0.0, 0.0, 0.0), target=None, quat=None, attach_body: Optional[int] = None) -> FusedCamera:
+                   position=(0.0, 0.0, 0.0), target=None, quat=None, attach_body: Optional[int] = None,
+                   flow: bool = False) -> FusedCamera:
         """A camera in every env: looking from `position` at `target`, or with orientation `quat` (xyzw; local +x forward,
-        +z up), in the frame of root_state -- or, with attach_body (a row of the env's body states), in that body's frame."""
+        +z up), in the frame of root_state -- or, with attach_body (a row of the env's body states), in that body's frame.
+        flow=True: render() also writes optical flow ("flow", "flow_i16"; module docstring); the default leaves the images and
+        the launch as they are."""
         from ..render import Renderer, build_scene, lookat_quat
         if target is not None and quat is not None:
             raise ValueError("add_camera: give target or quat, not both")
@@ -94,6 +140,8 @@ class FusedCameraHost:
                                 vscale=t.vscale)
             # the sim's own terrain payload on the device (a warped terrain: samples followed by the vertex bytes)
             self._renderer = Renderer(scene, t, self.sim._heights if t.rows > 0 else None, self.device)
-        cam = FusedCamera(self, width, height, horizontal_fov, near_plane, far_plane, position, quat, attach_body)
+        if flow and self._cam_reset_count is None:
+            raise ValueError("add_camera: flow=True needs the env's reset counter (_init_cameras(reset_count=...))")
+        cam = FusedCamera(self, width, height, horizontal_fov, near_plane, far_plane, position, quat, attach_body, flow=flow)
         self.cameras.append(cam)
         return cam

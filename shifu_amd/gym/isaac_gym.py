@@ -155,6 +155,10 @@ class IsaacGymEnv:
         rows = (rows[0] if len(rows) == 1 else torch.cat(rows)).to(dtype=torch.int32)
         self.gym.set_actor_root_state_tensor_indexed(self.sim, gymtorch.unwrap_tensor(self.root_state),
                                                      gymtorch.unwrap_tensor(rows), len(rows))
+        # camera sensors with optical flow: a reset is a teleport, these envs' previous frame is void (no-op otherwise)
+        for sensor in getattr(self, "sensors", ()):
+            if isinstance(sensor, CameraSensor):
+                sensor.reset_idx(env_ids)
 
     # -- viewer: nothing to draw on this backend ---------------------------------
     def render(self, sync_frame_time=True):

@@ -644,6 +644,12 @@ class Gym:
         return os.environ.get("SHIFU_AMD_TRIMESH_CAMERAS", "0") == "1"
 
     @staticmethod
+    def _optical_flow_enabled() -> bool:
+        """SHIFU_AMD_OPTICAL_FLOW=1: camera groups also render IMAGE_OPTICAL_FLOW (shf_render_cameras_flow; DESIGN.md
+        8e).  Off by default: the facade then refuses the image type as before."""
+        return os.environ.get("SHIFU_AMD_OPTICAL_FLOW", "0") == "1"
+
+    @staticmethod
     def _check_renderable_terrain(sim):
         t = sim.terrain
         if t is not None and t[0] == "heightfield" and len(t) > 6 and t[6] is not None and not Gym._trimesh_cameras_enabled():
@@ -736,6 +742,10 @@ class Gym:
                 g["attach"] = (torch.tensor([e * B + c.attach[0] for e, c in enumerate(cams)], dtype=torch.long, device=be.device),
                                torch.tensor(np.array([c.attach[1] for c in cams]), dtype=torch.float32, device=be.device),
                                torch.tensor(np.array([c.attach[2] for c in cams]), dtype=torch.float32, device=be.device))
+            if self._optical_flow_enabled():
+                from ..render import FlowHistory
+                g["flow_i16"] = torch.zeros(n, p.height, p.width, 2, dtype=torch.int16, device=be.device)
+                g["history"] = FlowHistory(n, B, be.device)
             sim.camera_groups.append(g)
 
     def _group_of(self, sim, camera_handle):
@@ -776,8 +786,27 @@ class Gym:
             self.refresh_rigid_body_state_tensor(sim)
         g = sim.camera_groups[camera_handle]
         pose = g["pose"] if g["attach"] is None else self._attached_poses(sim, g).contiguous()
-        sim.renderer.render(sim.backend.tensors[_abi.T_BODY_STATE], pose, sim.cam_seg, sim.cam_color, g["camera"],
+        bs = sim.backend.tensors[_abi.T_BODY_STATE]
+        h = g.get("history")
+        if h is not None:
+            # with optical flow (SHIFU_AMD_OPTICAL_FLOW=1): against the poses of this group's previous render, which this
+            # one then replaces -- preallocated tensors, no host sync
+            sim.renderer.render(bs, pose, sim.cam_seg, sim.cam_color, g["camera"], depth=g["depth"], seg_out=g["seg"],
+                                rgba=g["rgba"], flow_i16=g["flow_i16"], **h.tensors())
+            h.update(bs, pose)
+            return
+        sim.renderer.render(bs, pose, sim.cam_seg, sim.cam_color, g["camera"],
                             depth=g["depth"], seg_out=g["seg"], rgba=g["rgba"])
+
+    def invalidate_camera_flow(self, sim, camera_handle, env_ids=None):
+        """Not an Isaac Gym call: the group's next render shows zero optical flow in env_ids (all envs by default) -- after a
+        reset or any teleport, when the previous render's poses say nothing about motion.  Nothing to do without
+        SHIFU_AMD_OPTICAL_FLOW=1."""
+        if not sim.camera_groups:
+            return
+        h = sim.camera_groups[camera_handle].get("history")
+        if h is not None:
+            h.invalidate(env_ids)
 
     def render_all_camera_sensors(self, sim):
         """One launch per camera group, on the state of the last simulate (the rigid-body states are refreshed first when
@@ -787,21 +816,29 @@ class Gym:
 
     def get_camera_image_gpu_tensor(self, sim, env: Env, camera_handle, image_type):
         """Zero-copy view of row env of the group's image: IMAGE_COLOR (H, W, 4) u8 RGBA, IMAGE_DEPTH (H, W) f32 (minus the
-        view-space depth, -inf where nothing is hit), IMAGE_SEGMENTATION (H, W) int32."""
-        if image_type == IMAGE_OPTICAL_FLOW:
-            raise NotImplementedError("IMAGE_OPTICAL_FLOW is not rendered by this backend (depth, segmentation and color are)")
+        view-space depth, -inf where nothing is hit), IMAGE_SEGMENTATION (H, W) int32.  IMAGE_OPTICAL_FLOW, under
+        SHIFU_AMD_OPTICAL_FLOW=1 only: (H, W, 2) int16, (u, v) x 32768 / (W, H) (render.flow_from_i16 gives pixels)."""
+        if image_type == IMAGE_OPTICAL_FLOW and not (self._optical_flow_enabled() and (
+                not sim.camera_groups or "flow_i16" in sim.camera_groups[camera_handle])):
+            # (also a sim prepared without the variable: its groups hold no flow image)
+            raise NotImplementedError("IMAGE_OPTICAL_FLOW is not rendered by this backend (depth, segmentation and color are) "
+                                      "unless SHIFU_AMD_OPTICAL_FLOW=1 is set")
         if not sim.camera_groups:
             raise RuntimeError("get_camera_image_gpu_tensor: no camera sensors (create them before prepare_sim)")
         g = sim.camera_groups[camera_handle]
-        key = {IMAGE_COLOR: "rgba", IMAGE_DEPTH: "depth", IMAGE_SEGMENTATION: "seg"}.get(image_type)
+        key = {IMAGE_COLOR: "rgba", IMAGE_DEPTH: "depth", IMAGE_SEGMENTATION: "seg", IMAGE_OPTICAL_FLOW: "flow_i16"}.get(image_type)
         if key is None:
             raise ValueError(f"get_camera_image_gpu_tensor: unknown image type {image_type}")
         return _TensorHandle(g[key][env.index])
 
     def camera_group_tensors(self, sim, camera_handle):
-        """Not an Isaac Gym call: the group's (N, H, W[, 4]) images -- dict(rgba=, depth=, seg=) -- for all envs at once."""
+        """Not an Isaac Gym call: the group's (N, H, W[, 4]) images -- dict(rgba=, depth=, seg=) -- for all envs at once; under
+        SHIFU_AMD_OPTICAL_FLOW=1 also flow=, the (N, H, W, 2) int16 optical flow."""
         g = sim.camera_groups[camera_handle]
-        return dict(rgba=g["rgba"], depth=g["depth"], seg=g["seg"])
+        out = dict(rgba=g["rgba"], depth=g["depth"], seg=g["seg"])
+        if "flow_i16" in g:
+            out["flow"] = g["flow_i16"]
+        return out
 
     # ---- graphics: accepted and ignored (no viewer on this path) ----------------
     def create_viewer(self, *a, **k): return None

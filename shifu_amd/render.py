@@ -9,7 +9,13 @@ owns the conventions the kernel mirrors (DESIGN.md "Camera sensors"):
     x = 2 (c + 1/2) / W - 1,  y = 1 - 2 (r + 1/2) / H  -- so the ray parameter is the view-space depth;
   * view / projection matrices are row-vector 4 x 4 (p_clip = [p, 1] @ view @ proj, the form of the reference's
     shifu/utils/camera.py), proj[0, 0] = 1 / t, proj[1, 1] = proj[0, 0] W / H;
-  * color = body color x (AMBIENT + DIFFUSE max(0, n . LIGHT)) rounded to u8, alpha 255; background BACKGROUND.
+  * color = body color x (AMBIENT + DIFFUSE max(0, n . LIGHT)) rounded to u8, alpha 255; background BACKGROUND;
+  * optical flow (shf_render_cameras_flow): for the surface point X a pixel (r, c) shows on body b, X' = p_b' + R_b' R_b^T
+    (X - p_b) is where it was at the previous flow render (primed: that render's body pose; the terrain does not move);
+    projected into the previous camera pose with the pixel-ray convention it lands at (r', c'), and flow = (c - c', r - r')
+    in pixels, u to the right, v downwards -- backward-looking.  Exactly +0.0 where nothing is hit, where the point was
+    behind the previous camera, where the env's previous frame is marked invalid (FlowHistory) and where neither the
+    body's pose nor the camera's changed bits.  flow_to_i16 / flow_from_i16: Isaac Gym's int16 encoding.
 """
 from __future__ import annotations
 
@@ -226,18 +232,28 @@ class Renderer:
                                  f"one byte per vertex), got {h.numel()} {h.dtype}")
             self._heights = h.to(self.device).contiguous()
 
-    def render(self, body_state, cam_pose, seg, color, camera: "_abi.ShfCamera", depth=None, seg_out=None, rgba=None):
+    def render(self, body_state, cam_pose, seg, color, camera: "_abi.ShfCamera", depth=None, seg_out=None, rgba=None,
+               flow=None, flow_i16=None, prev_body_pose=None, prev_cam_pose=None, prev_valid=None):
         """One launch for all envs: body_state (N * num_bodies, 13), cam_pose (N, 7), seg (N, num_bodies) int32, color
-        (N, num_bodies, 3) f32; writes depth (N, H, W) f32, seg_out (N, H, W) int32 and rgba (N, H, W, 4) u8, each optional."""
+        (N, num_bodies, 3) f32; writes depth (N, H, W) f32, seg_out (N, H, W) int32 and rgba (N, H, W, 4) u8, each optional.
+
+        Optical flow (module docstring): with flow (N, H, W, 2) f32 pixels and / or flow_i16 (N, H, W, 2) int16 given, the
+        launch is shf_render_cameras_flow and needs the previous flow render's prev_body_pose (N * num_bodies, 7),
+        prev_cam_pose (N, 7) and prev_valid (N,) int32 (0: that env's flow is zero) -- a FlowHistory holds them."""
         import torch
         from ._lib import check, lib
         from .backend import _stream_ptr
         n = int(cam_pose.shape[0])
         B, H, W = self.scene.num_bodies, camera.height, camera.width
+        with_flow = flow is not None or flow_i16 is not None
+        if with_flow and (prev_body_pose is None or prev_cam_pose is None or prev_valid is None):
+            raise ValueError("render: a flow output needs prev_body_pose, prev_cam_pose and prev_valid (render.FlowHistory)")
         for t, shape, dt in ((body_state, (n * B, 13), torch.float32), (cam_pose, (n, 7), torch.float32),
                              (seg, (n, B), torch.int32), (color, (n, B, 3), torch.float32),
                              (depth, (n, H, W), torch.float32), (seg_out, (n, H, W), torch.int32),
-                             (rgba, (n, H, W, 4), torch.uint8)):
+                             (rgba, (n, H, W, 4), torch.uint8), (flow, (n, H, W, 2), torch.float32),
+                             (flow_i16, (n, H, W, 2), torch.int16), (prev_body_pose, (n * B, 7), torch.float32),
+                             (prev_cam_pose, (n, 7), torch.float32), (prev_valid, (n,), torch.int32)):
             if t is None:
                 continue
             if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
@@ -245,6 +261,76 @@ class Renderer:
                                  f"{tuple(t.shape)} {t.dtype} on {t.device}")
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         with torch.cuda.device(self.device):
+            if with_flow:
+                check(lib().shf_render_cameras_flow(ptr(self._scene_dev), C.byref(self.terrain), ptr(self._heights),
+                                                    C.byref(camera), n, ptr(body_state), ptr(cam_pose), ptr(seg), ptr(color),
+                                                    ptr(depth), ptr(seg_out), ptr(rgba), ptr(prev_body_pose), ptr(prev_cam_pose),
+                                                    ptr(prev_valid), ptr(flow), ptr(flow_i16), _stream_ptr(self.device)))
+                return
             check(lib().shf_render_cameras(ptr(self._scene_dev), C.byref(self.terrain), ptr(self._heights), C.byref(camera), n,
                                            ptr(body_state), ptr(cam_pose), ptr(seg), ptr(color), ptr(depth), ptr(seg_out),
                                            ptr(rgba), _stream_ptr(self.device)))
+
+
+# -- optical flow -------------------------------------------------------------------------------------------------------
+def flow_to_i16(flow, W: int, H: int):
+    """Isaac Gym's integer encoding of a (..., 2) pixel flow (u, v): q_u = sat16(rint(u 32768 / W)), q_v = sat16(rint(v
+    32768 / H)) as (..., 2) int16 -- float32 arithmetic as the kernel's (u x 32768 is exact, one correctly rounded division,
+    round half to even, saturation to [-32768, 32767]).  torch tensor or numpy array in, the same kind out."""
+    try:
+        import torch
+        is_torch = isinstance(flow, torch.Tensor)
+    except ImportError:
+        is_torch = False
+    if is_torch:
+        f = flow.to(torch.float32)
+        scale = torch.tensor([float(W), float(H)], dtype=torch.float32, device=f.device)
+        return torch.clamp(torch.round(f * 32768.0 / scale), -32768.0, 32767.0).to(torch.int16)
+    f = np.asarray(flow, np.float32)
+    q = np.rint((f * np.float32(32768.0)) / np.array([W, H], np.float32))
+    return np.clip(q, -32768.0, 32767.0).astype(np.int16)
+
+
+def flow_from_i16(q, W: int, H: int):
+    """The pixel flow (..., 2) float32 of flow_to_i16's integers: u = q_u W / 32768, v = q_v H / 32768 (what the
+    reference's normalize_optical_flow means to compute)."""
+    try:
+        import torch
+        is_torch = isinstance(q, torch.Tensor)
+    except ImportError:
+        is_torch = False
+    if is_torch:
+        scale = torch.tensor([float(W), float(H)], dtype=torch.float32, device=q.device)
+        return q.to(torch.float32) * scale / 32768.0
+    return np.asarray(q).astype(np.float32) * np.array([W, H], np.float32) / np.float32(32768.0)
+
+
+class FlowHistory:
+    """What a camera (or camera group) keeps between two flow renders: the body poses and camera poses of the previous
+    one and, per env, whether they are usable.  Everything is allocated here; update() is two strided copies and a fill on
+    the current stream -- no allocation, no host sync, capturable.  Born invalid: the first render's flow is zero."""
+
+    def __init__(self, num_envs: int, num_bodies: int, device):
+        import torch
+        self.num_envs, self.num_bodies = int(num_envs), int(num_bodies)
+        self.prev_body_pose = torch.zeros(self.num_envs * self.num_bodies, 7, dtype=torch.float32, device=device)
+        self.prev_cam_pose = torch.zeros(self.num_envs, 7, dtype=torch.float32, device=device)
+        self.prev_valid = torch.zeros(self.num_envs, dtype=torch.int32, device=device)
+
+    def update(self, body_state, cam_pose):
+        """After a flow render on (body_state, cam_pose): they become the previous frame, valid in every env."""
+        self.prev_body_pose.copy_(body_state[:, :7])
+        self.prev_cam_pose.copy_(cam_pose)
+        self.prev_valid.fill_(1)
+
+    def invalidate(self, env_ids=None):
+        """The next flow render is zero in env_ids (all envs by default): after a reset or a teleport."""
+        if env_ids is None:
+            self.prev_valid.zero_()
+        else:
+            import torch
+            ids = torch.as_tensor(env_ids, device=self.prev_valid.device).long()
+            self.prev_valid.index_fill_(0, ids, 0)
+
+    def tensors(self) -> dict:
+        return dict(prev_body_pose=self.prev_body_pose, prev_cam_pose=self.prev_cam_pose, prev_valid=self.prev_valid)

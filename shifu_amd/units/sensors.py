@@ -5,7 +5,15 @@ init_buffers, refresh, set_camera_location, set_camera_transform, the local_look
 image_normalization.  refresh() fills every env at once from the camera group's image tensors (the reference loops over
 envs, one get_camera_image_gpu_tensor per env and image type); IsaacGymEnv.refresh_sensors renders first.  The images
 are drawn from the collision geometry by a ray caster, not by Isaac Gym's renderer (DESIGN.md "Camera sensors").
-IMAGE_OPTICAL_FLOW is not rendered, and the cv2 viewer `render()` is not provided."""
+The cv2 viewer `render()` is not provided.
+
+IMAGE_OPTICAL_FLOW is rendered under SHIFU_AMD_OPTICAL_FLOW=1 only (read when the sensor and the sim are built; without
+it the type is refused as before, so the default config's image_types still raise): ground-truth flow from the same cast,
+flow = where a pixel's surface point is now minus where it was at this sensor's previous render, in Isaac Gym's int16
+encoding (DESIGN.md "Camera sensors"; no parity with Isaac Gym's own sign conventions is claimed).  optical_flow_buf is
+(N, H, W, 2) int16, u first -- the reference allocates (N, H, W) and its own comment doubts that shape (sensors.py:88-94);
+a flow image has two channels.  normalize_optical_flow(optical_flow, width, height) returns pixels.  reset_idx(env_ids)
+marks those envs' previous frame unusable: their next flow image is zero."""
 import enum
 
 import numpy as np
@@ -19,6 +27,17 @@ IMAGE_TYPE_COLOR = gymapi.IMAGE_COLOR
 IMAGE_TYPE_DEPTH = gymapi.IMAGE_DEPTH
 IMAGE_TYPE_SEGMENTATION = gymapi.IMAGE_SEGMENTATION
 IMAGE_TYPE_OPTICAL_FLOW = gymapi.IMAGE_OPTICAL_FLOW
+
+
+def optical_flow_enabled() -> bool:
+    return gymapi.Gym._optical_flow_enabled()
+
+
+def normalize_optical_flow(optical_flow, width, height):
+    """Pixels (..., 2) float32 of an int16 flow image: u = q_u width / 32768, v = q_v height / 32768 -- a working form of the
+    reference's helper (sensors.py:31-36)."""
+    from shifu_amd.render import flow_from_i16
+    return flow_from_i16(optical_flow, width, height)
 
 
 class CameraPose(enum.Enum):
@@ -51,12 +70,14 @@ class CameraSensor(Sensor):
             raise NotImplementedError('Currently not support')      # as the reference (sensors.py:117-119)
         else:
             raise NotImplementedError('choose one of method from local_lookat_positions and transform')
-        if IMAGE_TYPE_OPTICAL_FLOW in self.cfg.image_types:
+        if IMAGE_TYPE_OPTICAL_FLOW in self.cfg.image_types and not optical_flow_enabled():
             raise NotImplementedError("CameraSensor: IMAGE_OPTICAL_FLOW is not rendered by this backend (depth, "
                                       "segmentation and color are)")
 
     def reset_idx(self, env_ids):
-        pass
+        # optical flow: the poses of the previous render say nothing about motion across a reset
+        if IMAGE_TYPE_OPTICAL_FLOW in self.cfg.image_types and getattr(self, "camera_handle", None) is not None:
+            self.gym.invalidate_camera_flow(self.sim, self.camera_handle, env_ids)
 
     def load_to(self, env_id, env_handle, seg_id):
         camera_handle = self.gym.create_camera_sensor(env_handle, self.cfg.camera_props)
@@ -84,6 +105,9 @@ class CameraSensor(Sensor):
                 self.depth_buf = torch.zeros(n, self.height, self.width, dtype=torch.float, device=self.device)
             elif img_type == IMAGE_TYPE_SEGMENTATION:
                 self.segmentation_buf = torch.zeros(n, self.height, self.width, dtype=torch.int32, device=self.device)
+            elif img_type == IMAGE_TYPE_OPTICAL_FLOW and optical_flow_enabled():
+                # (u, v) x 32768 / (W, H), int16 (module docstring: the reference's (N, H, W) has no room for two channels)
+                self.optical_flow_buf = torch.zeros(n, self.height, self.width, 2, dtype=torch.int16, device=self.device)
             else:
                 raise NotImplementedError
         self._images = self.gym.camera_group_tensors(self.sim, self.camera_handle)
@@ -109,7 +133,8 @@ class CameraSensor(Sensor):
 
     def raw_images(self):
         """The camera group's own image tensors as rendered, before refresh() converts them: {"rgba": (N, H, W, 4) u8,
-        "depth": (N, H, W) f32, negative view depth, "seg": (N, H, W) i32}.  Views, not copies."""
+        "depth": (N, H, W) f32, negative view depth, "seg": (N, H, W) i32} and, under SHIFU_AMD_OPTICAL_FLOW=1, "flow": (N, H, W, 2)
+        int16.  Views, not copies."""
         return self._images
 
     def refresh(self):
@@ -127,3 +152,5 @@ class CameraSensor(Sensor):
             torch.neg(im["depth"], out=self.depth_buf)                       # Isaac gives negative depth (sensors.py:174-178)
         if IMAGE_TYPE_SEGMENTATION in types:
             self.segmentation_buf.copy_(im["seg"])
+        if IMAGE_TYPE_OPTICAL_FLOW in types:
+            self.optical_flow_buf.copy_(im["flow"])

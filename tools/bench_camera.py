@@ -10,6 +10,12 @@ and color; fov 87, near 0.05, far 6, pitched 0.5 rad down) after a reset and a f
 field against the walk over the warped trimesh on the same samples.
 
     python tools/bench_camera.py --scene a1-trimesh --envs 4096
+
+--flow: the same launch with and without optical flow (shf_render_cameras_flow writing the int16 flow image on top of the
+three others, against a previous frame one env step older, valid in every env), alternating --repeats times in one session;
+reports both medians and their ratio.
+
+    python tools/bench_camera.py --envs 1000 --flow
 """
 import argparse
 import json
@@ -79,6 +85,19 @@ def time_renders(render, warmup, renders):
     return t0.elapsed_time(t1) / renders
 
 
+def flow_on_off(render_off, render_on, a):
+    """{"ms_flow_off": median, "ms_flow_on": median, ...}: the two launches timed alternately, a.repeats times each."""
+    import statistics
+    off, on = [], []
+    for _ in range(a.repeats):
+        off.append(time_renders(render_off, a.warmup, a.renders))
+        on.append(time_renders(render_on, a.warmup, a.renders))
+    m_off, m_on = statistics.median(off), statistics.median(on)
+    return dict(flow=True, repeats=a.repeats, ms_flow_off=round(m_off, 4), ms_flow_on=round(m_on, 4),
+                flow_on_over_off=round(m_on / m_off, 4), ms_flow_off_runs=[round(v, 4) for v in off],
+                ms_flow_on_runs=[round(v, 4) for v in on], flow_bytes_written_extra_per_ray=4)
+
+
 def bench_a1(a):
     import math
     import torch
@@ -91,12 +110,23 @@ def bench_a1(a):
     env.cam_seg.fill_(1)                        # the robot; the terrain is segmentation 0
     env.reset()
     g = torch.Generator().manual_seed(0)
-    for _ in range(3):
+    from shifu_amd.render import FlowHistory
+    hist = FlowHistory(env.num_envs, env.cam_seg.shape[1], env.device)
+    for k in range(3):
+        if k == 2:
+            hist.update(env.body_state, cam.world_pose())          # --flow: the previous frame, one step older
         env.step((2 * torch.rand(env.num_envs, env.num_actions, generator=g) - 1).to(env.device))
     # the attached pose is composed once: the timed call is the render launch alone, as in the default scene
     pose, im = cam.world_pose(), cam.raw_images()
     render = lambda: env._renderer.render(env.body_state, pose, env.cam_seg, env.cam_color, cam.camera, depth=im["depth"],
                                           seg_out=im["seg"], rgba=im["rgba"])
+    flow_out = {}
+    if a.flow:
+        q = torch.zeros(env.num_envs, H, W, 2, dtype=torch.int16, device=env.device)
+        render_on = lambda: env._renderer.render(env.body_state, pose, env.cam_seg, env.cam_color, cam.camera, depth=im["depth"],
+                                                 seg_out=im["seg"], rgba=im["rgba"], flow_i16=q, **hist.tensors())
+        flow_out = flow_on_off(render, render_on, a)
+        flow_out["pixels_with_flow"] = round(float(q.ne(0).any(-1).float().mean()), 4)
     ms = time_renders(render, a.warmup, a.renders)
     rays = a.envs * W * H
     hit = torch.isfinite(im["depth"])
@@ -107,6 +137,7 @@ def bench_a1(a):
                pixels_on_terrain=round(float((hit & (im["seg"] == 0)).float().mean()), 4),
                pixels_hit=round(float(hit.float().mean()), 4), warped=int(env.sim.terrain.warped),
                device=torch.cuda.get_device_name(0))
+    out.update(flow_out)
     print(json.dumps(out))
     env.destroy()
 
@@ -117,6 +148,8 @@ def main():
     ap.add_argument("--renders", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--scene", choices=["abb", "a1-heightfield", "a1-trimesh"], default="abb")
+    ap.add_argument("--flow", action="store_true", help="also time the launch with optical flow, alternating with the one without")
+    ap.add_argument("--repeats", type=int, default=3, help="--flow: timed runs of each form")
     a = ap.parse_args()
     if a.scene != "abb":
         return bench_a1(a)
@@ -124,9 +157,26 @@ def main():
     env = make_env(a.envs)
     env.reset()
     g = torch.Generator().manual_seed(0)
-    for _ in range(3):
-        env.step((2 * torch.rand(env.num_envs, env.num_actions, generator=g) - 1).to(env.device))
     gym, sim, cam = env.isg_env.gym, env.isg_env.sim, env.camera
+    from shifu_amd import _abi
+    from shifu_amd.render import FlowHistory
+    grp = sim.camera_groups[cam.camera_handle]
+    bs = sim.backend.tensors[_abi.T_BODY_STATE]
+    hist = FlowHistory(a.envs, sim.cam_seg.shape[1], bs.device)
+    for k in range(3):
+        if k == 2:
+            hist.update(bs, grp["pose"])                            # --flow: the previous frame, one step older
+        env.step((2 * torch.rand(env.num_envs, env.num_actions, generator=g) - 1).to(env.device))
+    flow_out = {}
+    if a.flow:
+        q = torch.zeros(a.envs, cam.height, cam.width, 2, dtype=torch.int16, device=bs.device)
+        gym.refresh_rigid_body_state_tensor(sim)
+        render_off = lambda: sim.renderer.render(bs, grp["pose"], sim.cam_seg, sim.cam_color, grp["camera"], depth=grp["depth"],
+                                                 seg_out=grp["seg"], rgba=grp["rgba"])
+        render_on = lambda: sim.renderer.render(bs, grp["pose"], sim.cam_seg, sim.cam_color, grp["camera"], depth=grp["depth"],
+                                                seg_out=grp["seg"], rgba=grp["rgba"], flow_i16=q, **hist.tensors())
+        flow_out = flow_on_off(render_off, render_on, a)
+        flow_out["pixels_with_flow"] = round(float(q.ne(0).any(-1).float().mean()), 4)
     for _ in range(a.warmup):
         gym.render_camera_group(sim, cam.camera_handle)
     torch.cuda.synchronize()
@@ -149,6 +199,7 @@ def main():
                device=torch.cuda.get_device_name(0))
     if a.envs == 1000:
         out["meets_target"] = bool(ms <= TARGET_MS)
+    out.update(flow_out)
     print(json.dumps(out))
     env.destroy()
 

@@ -986,6 +986,31 @@ int shf_render_cameras_flow(const ShfRenderScene* scene_dev, const ShfTerrain* t
                             uint8_t* rgba_or_null, const float* prev_body_pose, const float* prev_cam_pose,
                             const int32_t* prev_valid, float* flow_or_null, int16_t* flow_i16_or_null, void* stream);
 
+/* World view (the headless viewer, shifu_amd/viewer.py): num_views cameras that each see MANY envs, where
+ * shf_render_cameras gives every env a camera that sees that env alone.  Another additive entry: no new SHF_ABI_VERSION,
+ * no struct layout changed.  view_pose (num_views, 7) pos + quat xyzw.  body_state / seg_ids / colors: the per-env tables
+ * of shf_render_cameras with num_envs rows.  The envs drawn are env_ids[0 .. num_drawn) (NULL: 0 .. num_drawn - 1; every
+ * value is clamped into [0, num_envs) on the device), and the shapes of the env at list position j are displaced by
+ * env_offset[j] ((num_drawn, 3), by LIST POSITION; NULL: zeros) -- the push-box envs, which all sit at the origin, laid out
+ * on a grid.  The terrain or ground is cast once and not displaced.  Pixel rays, near / far, depth_negative, shading,
+ * background and segmentation are shf_render_cameras'; a pixel shows the nearest hit among the terrain and every shape of
+ * every drawn env; among shapes at equal depth the earlier (list position, shape index) wins, and the terrain wins over a
+ * shape only where it is strictly nearer (as in shf_render_cameras).  env_out (num_views, H, W) int32: the env id (the
+ * clamped env_ids value) of the shape a pixel shows, -1 for the terrain, the ground or nothing.  Each output is optional.
+ * env_radius > 0: an env whose sphere of that radius about body 0's position + offset misses a tile's cone is skipped as
+ * a whole for that tile; the images are the same provided the sphere really bounds the env's shapes.  <= 0: no such cull.
+ * Refused: num_views, num_envs or num_drawn < 1, more than 2^31 - 1 workgroups, null inputs.  No atomics (the order of the
+ * candidate list is the tie rule), no host sync, no allocation: stream-ordered and capturable.
+ * SHF_RENDER_WORLD_LIST: candidate shapes a workgroup keeps in LDS before its waves cast them; SHF_RENDER_WORLD_CHUNK:
+ * (env, shape) pairs examined per pass, so a pass takes CHUNK / nshapes envs.  Mirrored in shifu_amd/_abi.py. */
+#define SHF_RENDER_WORLD_LIST 512
+#define SHF_RENDER_WORLD_CHUNK 256
+int shf_render_world(const ShfRenderScene* scene_dev, const ShfTerrain* terrain, const int16_t* height_samples_dev,
+                     const ShfCamera* camera, int32_t num_views, const float* view_pose, int32_t num_envs, int32_t num_drawn,
+                     const int32_t* env_ids_or_null, const float* env_offset_or_null, float env_radius, const float* body_state,
+                     const int32_t* seg_ids, const float* colors, float* depth_or_null, int32_t* seg_or_null,
+                     uint8_t* rgba_or_null, int32_t* env_or_null, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

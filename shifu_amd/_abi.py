@@ -96,6 +96,8 @@ RENDER_BOX, RENDER_SPHERE, RENDER_CAPSULE, RENDER_POLY = 0, 1, 2, 3
 RENDER_AMBIENT, RENDER_DIFFUSE = 0.35, 0.65
 RENDER_LIGHT = (0.40824829, 0.40824829, 0.81649658)
 RENDER_BG = (140, 170, 200)
+# world view (shf_render_world): candidate records a workgroup lists before a flush; (env, shape) pairs examined per pass
+RENDER_WORLD_LIST, RENDER_WORLD_CHUNK = 512, 256
 
 
 class ShfRenderShape(C.Structure):

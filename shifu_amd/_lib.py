@@ -93,6 +93,10 @@ _SIGS = {
     "shf_render_cameras": ([vp, C.POINTER(_abi.ShfTerrain), vp, C.POINTER(_abi.ShfCamera), i32] + [vp] * 7 + [vp], i32),
     # ... with optical flow: the same arguments, then prev_body_pose, prev_cam_pose, prev_valid, flow, flow_i16, stream
     "shf_render_cameras_flow": ([vp, C.POINTER(_abi.ShfTerrain), vp, C.POINTER(_abi.ShfCamera), i32] + [vp] * 7 + [vp] * 5 + [vp], i32),
+    # world view: scene, terrain, heights, camera, num_views, view_pose, num_envs, num_drawn, env_ids, env_offset, env_radius,
+    # body_state, seg_ids, colors, depth, seg, rgba, env, stream
+    "shf_render_world": ([vp, C.POINTER(_abi.ShfTerrain), vp, C.POINTER(_abi.ShfCamera), i32, vp, i32, i32, vp, vp, C.c_float]
+                         + [vp] * 3 + [vp] * 4 + [vp], i32),
     # conv-encoder inference (csrc/shf_conv.hip)
     "shf_conv_pack_bytes": ([i32, i32, C.POINTER(i64)], i32),
     "shf_conv_pack_weights": ([vp, vp, i32, i32, vp], i32),

@@ -92,6 +92,10 @@ BUDGETS = [("_Z16k_a1_step_a1_g32", 256, 0),          # default: A1, two envs pe
            # the first clean build (the motion table sits in LDS; the previous camera's basis and the projection live only
            # after the nearest hit is chosen) plus a margin of 10 -- 7 and 5 waves per SIMD; nothing on the stack
            ("_Z21k_render_cameras_flow", 80, 0), ("_Z24k_render_cameras_tw_flow", 95, 0),
+           # the world view (k_render_world / k_render_world_tw behind shf_render_world): 124 registers each in the first clean
+           # build (the per-pixel hit record, two cones, a pass's shape pose before it is listed) plus a margin of 10; the 52 KB
+           # candidate list in LDS holds them to three waves per SIMD either way; nothing on the stack
+           ("_Z14k_render_world", 134, 0), ("_Z17k_render_world_tw", 134, 0),
            # the conv-encoder layer (csrc/shf_conv.hip), every instantiation: 214 registers at most in the first clean build (64
            # accumulators, a chunk's weight fragments, the gathered rows in flight) plus a margin of 10 for compiler drift -- still
            # two waves per SIMD; nothing on the stack

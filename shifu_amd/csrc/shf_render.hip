@@ -29,6 +29,9 @@
 // per-pixel flow work comes after the nearest hit is chosen (one 3 x 3 transform, three dot products), not in the candidate
 // loop; depth / segmentation / color come from the same cast and are bit-equal to the plain kernels'.  The checker is
 // tests/flow_ref.py.
+//
+// World view (kernels k_render_world / k_render_world_tw behind shf_render_world, at the end of this file): one camera that
+// sees many envs, each displaced by an offset -- the headless viewer.  Same rays, intersections, walk and shading.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -612,4 +615,331 @@ extern "C" int shf_render_cameras_flow(const ShfRenderScene* scene_dev, const Sh
                      prev_body_pose, prev_cam_pose, prev_valid, reinterpret_cast<float2*>(flow_or_null),
                      reinterpret_cast<uint32_t*>(flow_i16_or_null));
   return hipGetLastError() == hipSuccess ? 0 : shf_set_error("shf_render_cameras_flow: launch failed");
+}
+
+// ---- world view (shf_render_world; the headless viewer of shifu_amd/viewer.py) -------------------------------------------
+// One camera that sees many envs.  One 256-thread workgroup per (view, 16 x 16 tile), a wave per 16 x 4 strip, as above; the
+// drawn envs are walked in passes of RW_CHUNK / nshapes envs, one thread per (env of the pass, shape): the thread builds its
+// shape's world centre (body pose, then the env's offset) and tests the bounding sphere against the TILE's cone and
+// [near, far].  The survivors are compacted IN ORDER -- a ballot, a popcount prefix, the four wave totals through LDS; no
+// atomics, which would make the order depend on timing -- into a candidate list in LDS (RW_LIST records: the 20 floats of the
+// per-env kernels' table, then kind, poly, segmentation id and env id).  When the next pass could overflow the list, and
+// after the last pass, it is flushed: every wave casts its pixels against the list (64 records at a time through its own strip cull, then the
+// wave-uniform candidate loop of the per-env kernels) and keeps the nearest hit under a strict <, and the list restarts.
+// Records are cast in (list position, shape) order whatever the flushes, so on equal depth the earlier one wins and the
+// images do not depend on where the flushes fall.  The terrain is cast last, up to the nearest shape, and wins only where
+// it is strictly nearer: k_render_cameras' rule.  env_radius > 0 adds a pass in front: one thread per env tests the env's
+// sphere against the tile's cone, and only the surviving envs (compacted in order into EL) reach the shape passes.
+#define RW_LIST SHF_RENDER_WORLD_LIST
+#define RW_CHUNK SHF_RENDER_WORLD_CHUNK
+#define RW_REC 24     // dwords per record: RT_SW floats, then kind, poly, segmentation id, env id
+static_assert(RW_CHUNK == RT_THREADS, "one thread per (env, shape) pair of a pass");
+static_assert(RW_LIST >= RW_CHUNK, "a pass must fit the empty list");
+
+namespace {
+
+// the cone about the central ray of pixel columns [ca, cb) x rows [ra, rb) that holds their four corner rays
+__device__ __forceinline__ void rw_cone(const float* fwd, const float* right, const float* up, float xa, float xb, float ya,
+                                        float yb, float t, float ty_scale, float* ax, float* half) {
+  for (int k = 0; k < 3; k++) ax[k] = fwd[k] + right[k] * (0.5f * (xa + xb) * t) + up[k] * (0.5f * (ya + yb) * ty_scale);
+  const float ian = 1.0f / sqrtf(dot3(ax, ax));
+  for (int k = 0; k < 3; k++) ax[k] *= ian;
+  float cmin = 1.0f;
+  for (int e = 0; e < 4; e++) {
+    const float xx = (e & 1) ? xb : xa, yy = (e & 2) ? yb : ya;
+    float dd[3];
+    for (int k = 0; k < 3; k++) dd[k] = fwd[k] + right[k] * (xx * t) + up[k] * (yy * ty_scale);
+    cmin = fminf(cmin, dot3(dd, ax) / sqrtf(dot3(dd, dd)));
+  }
+  *half = acosf(fminf(fmaxf(cmin, -1.0f), 1.0f));
+}
+
+// does the sphere of radius r about v (relative to the camera origin) reach into the cone and the depth range?
+__device__ __forceinline__ bool rw_sphere_in_cone(const float* v, float r, const float* ax, float half, const float* fwd,
+                                                  float nearp, float farp) {
+  const float dist2 = dot3(v, v), dv = dot3(v, fwd);
+  if (!(dv - r <= farp && dv + r >= nearp)) return false;
+  if (dist2 <= r * r) return true;
+  const float dist = sqrtf(dist2);
+  const float ang = acosf(fminf(fmaxf(dot3(v, ax) / dist, -1.0f), 1.0f));
+  return ang <= half + asinf(fminf(r / dist, 1.0f)) + 1e-3f;
+}
+
+struct RwHit {
+  float best, nw[3], col[3];
+  int sid, env;
+};
+
+// a flush: this wave's pixels against records [0, count) of the list, in order
+__device__ __forceinline__ void rw_cast(const float* L, int count, const ShfRenderScene* __restrict__ scene, const float* o,
+                                        const float* d, const float* fwd, const float* sax, float shalf, float nearp, float farp,
+                                        int lane, RwHit& h) {
+  for (int b0 = 0; b0 < count; b0 += 64) {
+    bool in = false;
+    if (b0 + lane < count) {
+      const float* s = L + (b0 + lane) * RW_REC;
+      const float v[3] = {s[0] - o[0], s[1] - o[1], s[2] - o[2]};
+      in = rw_sphere_in_cone(v, s[15], sax, shalf, fwd, nearp, farp);
+    }
+    uint64_t cand = __ballot(in);
+    while (cand) {
+      const int i = b0 + __builtin_amdgcn_readfirstlane(__builtin_ctzll(cand));
+      cand &= cand - 1;
+      const float* s = L + i * RW_REC;
+      const float rel[3] = {o[0] - s[0], o[1] - s[1], o[2] - s[2]};
+      float ol[3], dl[3];
+      for (int k = 0; k < 3; k++) {     // into the shape frame: R^T (.)
+        ol[k] = s[3 + k] * rel[0] + s[6 + k] * rel[1] + s[9 + k] * rel[2];
+        dl[k] = s[3 + k] * d[0] + s[6 + k] * d[1] + s[9 + k] * d[2];
+      }
+      const int kind = __float_as_int(s[20]);
+      float nl[3] = {0.0f, 0.0f, 1.0f}, sh;
+      if (kind == SHF_RENDER_BOX) {
+        const float hh[3] = {s[12], s[13], s[14]};
+        sh = hit_box(ol, dl, hh, nl);
+      } else if (kind == SHF_RENDER_SPHERE) {
+        sh = hit_sphere(ol, dl, s[12], nl);
+      } else if (kind == SHF_RENDER_CAPSULE) {
+        sh = hit_capsule(ol, dl, s[12], s[13], nl);
+      } else {
+        const int p = __builtin_amdgcn_readfirstlane(min(max(__float_as_int(s[21]), 0), SHF_RENDER_MAX_POLYS - 1));
+        sh = hit_poly(&scene->poly[p], ol, dl, nl);
+      }
+      if (sh >= nearp && sh <= farp && sh < h.best) {
+        h.best = sh;
+        for (int k = 0; k < 3; k++) h.nw[k] = s[3 + 3 * k] * nl[0] + s[4 + 3 * k] * nl[1] + s[5 + 3 * k] * nl[2];
+        h.col[0] = s[16]; h.col[1] = s[17]; h.col[2] = s[18];
+        h.sid = __float_as_int(s[22]);
+        h.env = __float_as_int(s[23]);
+      }
+    }
+  }
+}
+
+// exclusive prefix of `keep` over the workgroup in thread order, and the total: a ballot and a popcount per wave, the wave
+// totals through WT (the caller alternates between two WT rows, so one barrier per call is enough)
+__device__ __forceinline__ int rw_prefix(bool keep, int* WT, int wave, int lane, int* total) {
+  const uint64_t m = __ballot(keep);
+  if (lane == 0) WT[wave] = __popcll(m);
+  __syncthreads();
+  int pre = __popcll(m & ((1ull << lane) - 1ull)), tot = 0;
+  for (int w = 0; w < RT_THREADS / 64; w++) {
+    const int c = WT[w];
+    if (w < wave) pre += c;
+    tot += c;
+  }
+  *total = tot;
+  return pre;
+}
+
+}  // namespace
+
+template <bool TW>
+__device__ __forceinline__ void render_world(const ShfRenderScene* __restrict__ scene, const ShfTerrain& T,
+                                             const int16_t* __restrict__ hsamp, const ShfCamera& cam, int tiles_x, int tiles,
+                                             const float* __restrict__ view_pose, int num_envs, int num_drawn,
+                                             const int32_t* __restrict__ env_ids, const float* __restrict__ env_offset,
+                                             float env_radius, const float* __restrict__ body_state,
+                                             const int32_t* __restrict__ seg_ids, const float* __restrict__ colors,
+                                             float* __restrict__ depth, int32_t* __restrict__ seg_out, uint32_t* __restrict__ rgba,
+                                             int32_t* __restrict__ env_out) {
+  __shared__ float L[RW_LIST * RW_REC];
+  __shared__ int EL[RT_THREADS];                  // env pre-cull: the surviving list positions of a block of RT_THREADS
+  __shared__ int WT[2][RT_THREADS / 64];
+  const int view = blockIdx.x / tiles, tile = blockIdx.x - view * tiles;
+  const int tx = tile % tiles_x, ty = tile / tiles_x;
+  const int lid = threadIdx.x, wave = lid >> 6, lane = lid & 63;
+  const int W = cam.width, Hh = cam.height;
+  // (device data, not trusted: the counts are clamped, and so is every env id below)
+  const int ns = min(max(scene->nshapes, 0), SHF_RENDER_MAX_SHAPES), B = max(scene->num_bodies, 1);
+
+  const float* cp = view_pose + (size_t)view * 7;
+  float Rc[9];
+  {
+    const float q[4] = {cp[3], cp[4], cp[5], cp[6]};
+    quat_mat(q, Rc);
+  }
+  const float o[3] = {cp[0], cp[1], cp[2]};
+  const float fwd[3] = {Rc[0], Rc[3], Rc[6]}, right[3] = {-Rc[1], -Rc[4], -Rc[7]}, up[3] = {Rc[2], Rc[5], Rc[8]};
+  const float t = tanf(0.5f * cam.horizontal_fov * 0.017453292519943295f);
+  const float ty_scale = t * (float)Hh / (float)W;
+  const float nearp = cam.near_plane, farp = cam.far_plane;
+
+  const int c0 = tx * RT_TILE, r0 = ty * RT_TILE + wave * 4;
+  const int col = c0 + (lane & 15), rowp = r0 + (lane >> 4);
+  const float iW = 1.0f / (float)W, iH = 1.0f / (float)Hh;
+  const float xa = 2.0f * (float)c0 * iW - 1.0f, xb = 2.0f * (float)(c0 + RT_TILE) * iW - 1.0f;
+  float tax[3], thalf, sax[3], shalf;     // the tile's cone (what enters the list) and this wave's strip's (its own cull)
+  rw_cone(fwd, right, up, xa, xb, 1.0f - 2.0f * (float)(ty * RT_TILE) * iH, 1.0f - 2.0f * (float)(ty * RT_TILE + RT_TILE) * iH, t,
+          ty_scale, tax, &thalf);
+  rw_cone(fwd, right, up, xa, xb, 1.0f - 2.0f * (float)r0 * iH, 1.0f - 2.0f * (float)(r0 + 4) * iH, t, ty_scale, sax, &shalf);
+
+  const float px = 2.0f * ((float)col + 0.5f) * iW - 1.0f, py = 1.0f - 2.0f * ((float)rowp + 0.5f) * iH;
+  float d[3];
+  for (int k = 0; k < 3; k++) d[k] = fwd[k] + right[k] * (px * t) + up[k] * (py * ty_scale);
+
+  RwHit h;
+  h.best = INFINITY;
+  h.nw[0] = 0.0f; h.nw[1] = 0.0f; h.nw[2] = 1.0f;
+  h.col[0] = h.col[1] = h.col[2] = 0.0f;
+  h.sid = 0;
+  h.env = -1;
+
+  if (ns > 0) {
+    const int ec = RW_CHUNK / ns;                   // envs per pass (>= 4: ns <= 64)
+    const int je = lid / ns, si = lid - je * ns;    // this thread's env of the pass and its shape
+    const bool cull = env_radius > 0.0f;
+    int count = 0, par = 0;
+    for (int base = 0; base < num_drawn; base += RT_THREADS) {
+      int nel = min(RT_THREADS, num_drawn - base);
+      if (cull) {
+        bool keep = false;
+        if (lid < nel) {
+          const int j = base + lid;
+          const int env = min(max(env_ids ? env_ids[j] : j, 0), num_envs - 1);
+          const float* bsr = body_state + (size_t)env * B * 13;
+          float v[3];
+          for (int k = 0; k < 3; k++) v[k] = (bsr[k] + (env_offset ? env_offset[(size_t)j * 3 + k] : 0.0f)) - o[k];
+          keep = rw_sphere_in_cone(v, env_radius, tax, thalf, fwd, nearp, farp);
+        }
+        const int pre = rw_prefix(keep, WT[par], wave, lane, &nel);
+        par ^= 1;
+        if (keep) EL[pre] = base + lid;
+        __syncthreads();
+      }
+      // (at least one pass per block, possibly an empty one: the flush below is the only one, and the last pass takes it)
+      int e0 = 0;
+      do {
+        const int ne = max(min(ec, nel - e0), 0);
+        bool keep = false;
+        int env = 0;
+        size_t row = 0;
+        float c[3] = {0.0f, 0.0f, 0.0f}, Rb[9];
+        if (je < ne) {
+          const int j = cull ? EL[e0 + je] : base + e0 + je;
+          env = min(max(env_ids ? env_ids[j] : j, 0), num_envs - 1);
+          const ShfRenderShape& sh = scene->shape[si];
+          row = (size_t)env * B + min(max(sh.body, 0), B - 1);
+          const float* bsr = body_state + row * 13;
+          {
+            const float q[4] = {bsr[3], bsr[4], bsr[5], bsr[6]};
+            quat_mat(q, Rb);
+          }
+          for (int r = 0; r < 3; r++)
+            c[r] = (bsr[r] + Rb[3 * r] * sh.pos[0] + Rb[3 * r + 1] * sh.pos[1] + Rb[3 * r + 2] * sh.pos[2]) +
+                   (env_offset ? env_offset[(size_t)j * 3 + r] : 0.0f);
+          const float v[3] = {c[0] - o[0], c[1] - o[1], c[2] - o[2]};
+          keep = rw_sphere_in_cone(v, sh.radius, tax, thalf, fwd, nearp, farp);
+        }
+        int total;
+        const int pre = rw_prefix(keep, WT[par], wave, lane, &total);
+        par ^= 1;
+        if (keep) {
+          const ShfRenderShape& sh = scene->shape[si];
+          float* s = L + (count + pre) * RW_REC;
+          for (int r = 0; r < 3; r++) {
+            s[r] = c[r];
+            for (int cc = 0; cc < 3; cc++)
+              s[3 + 3 * r + cc] = Rb[3 * r] * sh.rot[cc] + Rb[3 * r + 1] * sh.rot[3 + cc] + Rb[3 * r + 2] * sh.rot[6 + cc];
+            s[12 + r] = sh.param[r];
+            s[16 + r] = colors[row * 3 + r];
+          }
+          s[15] = sh.radius;
+          s[19] = 0.0f;
+          s[20] = __int_as_float(sh.kind);
+          s[21] = __int_as_float(sh.poly);
+          s[22] = __int_as_float(seg_ids[row]);
+          s[23] = __int_as_float(env);
+        }
+        count += total;
+        e0 += ec;
+        // flush: after the last pass, and when the next pass could overflow the list
+        if ((e0 >= nel && base + RT_THREADS >= num_drawn) || count + ec * ns > RW_LIST) {
+          __syncthreads();
+          rw_cast(L, count, scene, o, d, fwd, sax, shalf, nearp, farp, lane, h);
+          __syncthreads();
+          count = 0;
+        }
+      } while (e0 < nel);
+    }
+  }
+
+  float best = h.best;
+  bool ground_hit = false;
+  if (scene->ground) {
+    const float lim = fminf(best, farp);
+    float nn[3], sg = INFINITY;
+    if (T.rows == 0) {
+      if (d[2] < 0.0f) {
+        const float s = -o[2] / d[2];
+        if (s >= nearp && s <= lim) { sg = s; nn[0] = 0.0f; nn[1] = 0.0f; nn[2] = 1.0f; }
+      }
+    } else {
+      sg = hit_heightfield<TW>(T, hsamp, scene->hf_zmin, scene->hf_zmax, o, d, nearp, lim, nn);
+    }
+    if (sg < best) {
+      best = sg;
+      ground_hit = true;
+      h.nw[0] = nn[0]; h.nw[1] = nn[1]; h.nw[2] = nn[2];
+      h.col[0] = scene->ground_color[0]; h.col[1] = scene->ground_color[1]; h.col[2] = scene->ground_color[2];
+    }
+  }
+
+  if (col >= W || rowp >= Hh) return;
+  const size_t px_i = ((size_t)view * Hh + rowp) * W + col;
+  const bool any = best < INFINITY;
+  if (depth) {
+    const float dv = any ? best : INFINITY;
+    depth[px_i] = cam.depth_negative ? -dv : dv;
+  }
+  if (seg_out) seg_out[px_i] = ground_hit ? 0 : h.sid;
+  if (env_out) env_out[px_i] = ground_hit ? -1 : h.env;
+  if (rgba) {
+    uint32_t pix;
+    if (any) {
+      const float il = 1.0f / sqrtf(dot3(h.nw, h.nw));
+      const float nl = (h.nw[0] * SHF_RENDER_LIGHT_X + h.nw[1] * SHF_RENDER_LIGHT_Y + h.nw[2] * SHF_RENDER_LIGHT_Z) * il;
+      const float lam = SHF_RENDER_AMBIENT + SHF_RENDER_DIFFUSE * fmaxf(nl, 0.0f);
+      pix = shade_u8(h.col[0], lam) | (shade_u8(h.col[1], lam) << 8) | (shade_u8(h.col[2], lam) << 16) | (255u << 24);
+    } else {
+      pix = (uint32_t)SHF_RENDER_BG_R | ((uint32_t)SHF_RENDER_BG_G << 8) | ((uint32_t)SHF_RENDER_BG_B << 16) | (255u << 24);
+    }
+    rgba[px_i] = pix;
+  }
+}
+
+#define RW_KERNEL_ARGS                                                                                                       \
+  const ShfRenderScene *__restrict__ scene, ShfTerrain T, const int16_t *__restrict__ hsamp, ShfCamera cam, int tiles_x,     \
+      int tiles, const float *__restrict__ view_pose, int num_envs, int num_drawn, const int32_t *__restrict__ env_ids,      \
+      const float *__restrict__ env_offset, float env_radius, const float *__restrict__ body_state,                         \
+      const int32_t *__restrict__ seg_ids, const float *__restrict__ colors, float *__restrict__ depth,                      \
+      int32_t *__restrict__ seg_out, uint32_t *__restrict__ rgba, int32_t *__restrict__ env_out
+
+__global__ void __launch_bounds__(RT_THREADS) k_render_world(RW_KERNEL_ARGS) {
+  render_world<false>(scene, T, hsamp, cam, tiles_x, tiles, view_pose, num_envs, num_drawn, env_ids, env_offset, env_radius,
+                      body_state, seg_ids, colors, depth, seg_out, rgba, env_out);
+}
+__global__ void __launch_bounds__(RT_THREADS) k_render_world_tw(RW_KERNEL_ARGS) {
+  render_world<true>(scene, T, hsamp, cam, tiles_x, tiles, view_pose, num_envs, num_drawn, env_ids, env_offset, env_radius,
+                     body_state, seg_ids, colors, depth, seg_out, rgba, env_out);
+}
+
+extern "C" int shf_render_world(const ShfRenderScene* scene_dev, const ShfTerrain* terrain, const int16_t* height_samples_dev,
+                                const ShfCamera* camera, int32_t num_views, const float* view_pose, int32_t num_envs,
+                                int32_t num_drawn, const int32_t* env_ids_or_null, const float* env_offset_or_null, float env_radius,
+                                const float* body_state, const int32_t* seg_ids, const float* colors, float* depth_or_null,
+                                int32_t* seg_or_null, uint8_t* rgba_or_null, int32_t* env_or_null, void* stream) {
+  int tiles_x, tiles;
+  if (const int rc = render_check("shf_render_world", scene_dev, terrain, height_samples_dev, camera, num_envs, &tiles_x, &tiles)) return rc;
+  if (num_views < 1 || num_envs < 1 || num_drawn < 1)
+    return shf_set_error("shf_render_world: num_views, num_envs and num_drawn must be at least 1");
+  if (!body_state || !view_pose || !seg_ids || !colors) return shf_set_error("shf_render_world: null input tensor");
+  if (((uintptr_t)rgba_or_null & 3u) != 0) return shf_set_error("shf_render_world: rgba must be 4-byte aligned");
+  if ((int64_t)tiles * num_views > 0x7fffffffLL) return shf_set_error("shf_render_world: too many views x tiles for one launch");
+  if (!depth_or_null && !seg_or_null && !rgba_or_null && !env_or_null) return 0;
+  hipLaunchKernelGGL(terrain->warped ? k_render_world_tw : k_render_world, dim3((unsigned)(tiles * num_views)), dim3(RT_THREADS),
+                     0, (hipStream_t)stream, scene_dev, *terrain, height_samples_dev, *camera, tiles_x, tiles, view_pose, num_envs,
+                     num_drawn, env_ids_or_null, env_offset_or_null, env_radius, body_state, seg_ids, colors, depth_or_null,
+                     seg_or_null, reinterpret_cast<uint32_t*>(rgba_or_null), env_or_null);
+  return hipGetLastError() == hipSuccess ? 0 : shf_set_error("shf_render_world: launch failed");
 }

@@ -59,7 +59,13 @@ def _philox_uniform(global_ids: np.ndarray, seed: int, stream: int) -> np.ndarra
 
 
 class FusedA1Env(FusedCameraHost):
-    """rsl_rl.env.VecEnv duck type (SURVEY 8b 'upward contract').  Cameras: add_camera (gym/fused_camera.py)."""
+    """rsl_rl.env.VecEnv duck type (SURVEY 8b 'upward contract').  Cameras: add_camera, the headless viewer: add_viewer
+    (gym/fused_camera.py)."""
+
+    def _viewer_env_radius(self) -> float:
+        # from the model: the longest chain of joint offsets plus the largest shape reach (viewer.model_env_radius)
+        from ..viewer import model_env_radius
+        return model_env_radius(self.cm)
 
     def __init__(self, num_envs: int = 4096, device="cuda:0", terrain: str = "heightfield", seed: int = 42,
                  rank: int = 0, world_size: int = 1, terrain_cfg=None, sim_params: Optional[_abi.ShfSimParams] = None,

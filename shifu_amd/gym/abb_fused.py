@@ -15,6 +15,8 @@ REWARD_NAMES = ["reward_reaching", "reward_success"]   # build_reward_functions 
 
 
 class FusedAbbEnv(FusedCameraHost):
+    _viewer_layout = "grid"      # add_viewer: the envs all sit at the origin, so the viewer lays them out
+
     def __init__(self, num_envs: int = 4096, device="cuda:0", seed: int = 42, rank: int = 0, world_size: int = 1,
                  group: int = None, dt: float = 0.02, decimation: int = 5, episode_length_s: float = 20.0,
                  extra_boxes=(), link_contacts: bool = None, mapping: str = None, solver: str = None,

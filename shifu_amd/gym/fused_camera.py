@@ -111,6 +111,7 @@ class FusedCameraHost:
         self.cam_seg = torch.zeros(self.num_envs, B, dtype=torch.int32, device=self.device)
         self.cam_color = torch.tensor(DEFAULT_BODY_COLOR, dtype=torch.float32, device=self.device).repeat(self.num_envs, B, 1)
         self.cameras = []
+        self.viewers = []
         self._renderer = None
         self._cam_reset_count = reset_count
 
@@ -125,7 +126,7 @@ class FusedCameraHost:
         +z up), in the frame of root_state -- or, with attach_body (a row of the env's body states), in that body's frame.
         flow=True: render() also writes optical flow ("flow", "flow_i16"; module docstring); the default leaves the images and
         the launch as they are."""
-        from ..render import Renderer, build_scene, lookat_quat
+        from ..render import lookat_quat
         if target is not None and quat is not None:
             raise ValueError("add_camera: give target or quat, not both")
         if target is not None:
@@ -133,6 +134,15 @@ class FusedCameraHost:
         elif quat is None:
             quat = (0.0, 0.0, 0.0, 1.0)
         quat = np.asarray(quat, float) / np.linalg.norm(quat)
+        self._ensure_renderer()
+        if flow and self._cam_reset_count is None:
+            raise ValueError("add_camera: flow=True needs the env's reset counter (_init_cameras(reset_count=...))")
+        cam = FusedCamera(self, width, height, horizontal_fov, near_plane, far_plane, position, quat, attach_body, flow=flow)
+        self.cameras.append(cam)
+        return cam
+
+    def _ensure_renderer(self):
+        from ..render import Renderer, build_scene
         if self._renderer is None:
             t = self.sim.terrain
             hs = self.sim.height_samples if t.rows > 0 else None
@@ -140,8 +150,25 @@ class FusedCameraHost:
                                 vscale=t.vscale)
             # the sim's own terrain payload on the device (a warped terrain: samples followed by the vertex bytes)
             self._renderer = Renderer(scene, t, self.sim._heights if t.rows > 0 else None, self.device)
-        if flow and self._cam_reset_count is None:
-            raise ValueError("add_camera: flow=True needs the env's reset counter (_init_cameras(reset_count=...))")
-        cam = FusedCamera(self, width, height, horizontal_fov, near_plane, far_plane, position, quat, attach_body, flow=flow)
-        self.cameras.append(cam)
-        return cam
+        return self._renderer
+
+    # what add_viewer takes when the caller names none: FusedA1Env's envs really are apart on the terrain ("world", and a
+    # radius about the trunk that holds the whole robot, for the env-level cull); FusedAbbEnv's all sit at the origin
+    # ("grid"), and its box roams free of the arm's base, so no radius bounds the env (0: no env-level cull)
+    _viewer_layout = "world"
+
+    def _viewer_env_radius(self) -> float:
+        return 0.0
+
+    def add_viewer(self, width: int, height: int, horizontal_fov: float = 90.0, near_plane: float = 0.05,
+                   far_plane: float = 100.0, env_ids=None, layout: Optional[str] = None, spacing=2.0,
+                   per_row: Optional[int] = None):
+        """A viewer.Viewer over env_ids (default: every env) on the body states the step kernels write: one camera that sees
+        them all (shf_render_world), with the cameras' segmentation / color tables.  Derived data, like the cameras."""
+        from ..viewer import Viewer
+        layout = self._viewer_layout if layout is None else layout
+        v = Viewer(self._ensure_renderer(), self.num_envs, self.body_state, self.cam_seg, self.cam_color, width, height,
+                   horizontal_fov, near_plane, far_plane, env_ids=env_ids, layout=layout, spacing=spacing, per_row=per_row,
+                   env_radius=self._viewer_env_radius())
+        self.viewers.append(v)
+        return v

@@ -5,8 +5,11 @@ reference (that order is what produces quirks Q1, Q2, Q4):
     step(a):  render -> robot.step(a) -> refresh_state() [one MORE simulate] -> post_physics_step
 
 All `self.gym.*` calls land on shifu_amd.isaacgym.gymapi.Gym, i.e. on the HIP kernels
-behind include/shifu_amd.h.  Viewer / lighting code paths are accepted no-ops.
+behind include/shifu_amd.h.  Viewer / lighting code paths are accepted no-ops, unless
+SHIFU_AMD_VIEWER=<directory> opts into the headless viewer (shifu_amd/viewer.py): render() then
+writes numbered PNG frames there.
 """
+import os
 from typing import List, Union
 
 import numpy as np
@@ -77,7 +80,16 @@ class IsaacGymEnv:
             self.env_handles.append(handle)
         self.gym.prepare_sim(self.sim)
         self._init_buffers()
+        if not self.headless and os.environ.get("SHIFU_AMD_VIEWER"):
+            self._set_camera(getattr(self.cfg.debug, "camera_pos", [1., -1., 1.]), getattr(self.cfg.debug, "camera_lookat", [0, 0, 0]))
         self.init_done = True
+
+    def _set_camera(self, position, lookat):
+        """The reference's _set_camera (shifu/gym/isaac_gym.py:223-232), for the headless viewer: only reached with
+        SHIFU_AMD_VIEWER=<directory> set, where create_viewer returns a viewer.Viewer."""
+        self.viewer = self.gym.create_viewer(self.sim, gymapi.CameraProperties())
+        self._viewer_frame = 0
+        self.gym.viewer_camera_look_at(self.viewer, None, gymapi.Vec3(*position), gymapi.Vec3(*lookat))
 
     def _init_buffers(self):
         g, s = self.gym, self.sim
@@ -160,9 +172,18 @@ class IsaacGymEnv:
             if isinstance(sensor, CameraSensor):
                 sensor.reset_idx(env_ids)
 
-    # -- viewer: nothing to draw on this backend ---------------------------------
+    # -- viewer: nothing to draw on this backend, unless the headless viewer is opted into ----------------------------
     def render(self, sync_frame_time=True):
-        return
+        if self.viewer is None:
+            return
+        # SHIFU_AMD_VIEWER=<directory>: draw, and write the next numbered frame there (a host copy per frame)
+        directory = os.environ.get("SHIFU_AMD_VIEWER")
+        if not directory:
+            return
+        os.makedirs(directory, exist_ok=True)
+        self.gym.draw_viewer(self.viewer, self.sim, True)
+        self.gym.write_viewer_image_to_file(self.viewer, os.path.join(directory, "frame_%06d.png" % self._viewer_frame))
+        self._viewer_frame += 1
 
     def change_light(self, *args, **kwargs):
         return

@@ -253,6 +253,7 @@ class SimHandle:
         self.camera_groups: List[dict] = []   # after prepare_sim: one per camera handle (one camera per env each)
         self.renderer = None
         self.body_fresh = False               # body_state refreshed since the last simulate (render_all_camera_sensors)
+        self.env_grid = (0.0, 0.0, 1)         # create_env's (pitch x, pitch y, envs per row): the viewer's layout
 
 
 class Gym:
@@ -360,6 +361,10 @@ class Gym:
 
     def create_env(self, sim: SimHandle, lower, upper, num_per_row):
         env = Env(sim, len(sim.envs))
+        if not sim.envs:
+            # the grid Isaac Gym would place the envs on (pitch = the env box's extent, num_per_row per row).  The sim does
+            # not use it -- every env sits at the origin of the state tensors -- but the viewer lays the envs out on it
+            sim.env_grid = (float(upper.x) - float(lower.x), float(upper.y) - float(lower.y), max(int(num_per_row), 1))
         sim.envs.append(env)
         return env
 
@@ -699,29 +704,12 @@ class Gym:
 
     def _prepare_cameras(self, sim):
         import torch
-        from ..render import DEFAULT_BODY_COLOR, Renderer, build_scene, camera_struct
+        from ..render import camera_struct
+        self._prepare_render_scene(sim)
         be = sim.backend
-        if be.terrain.warped and not self._trimesh_cameras_enabled():
-            raise NotImplementedError("camera sensors cannot render a warped trimesh terrain (ShfTerrain.warped) unless "
-                                      "SHIFU_AMD_TRIMESH_CAMERAS=1 is set: height fields and planes only by default")
-        env0 = sim.envs[0]
-        model = env0.actors[0].asset.model
-        boxes = [a.asset.box_dim for a in env0.actors[1:]]
-        nb = model.blob.nb
-        B = nb + len(boxes)
-        hs = getattr(be, "height_samples", None) if be.terrain.rows > 0 else None
-        scene = build_scene(model.render_shapes, nb, boxes, height_samples=hs, vscale=be.terrain.vscale)
-        sim.renderer = Renderer(scene, be.terrain, be._heights if be.terrain.rows > 0 else None, be.device)
         n = len(sim.envs)
-        row = lambda a, b: b if a == 0 else nb + a - 1
-        seg = torch.zeros(n, B, dtype=torch.int32)
-        col = torch.tensor(DEFAULT_BODY_COLOR, dtype=torch.float32).repeat(n, B, 1)
-        for e, env in enumerate(sim.envs):
-            for (a, b), v in env.seg_ids.items():
-                seg[e, row(a, b)] = v
-            for (a, b), v in env.colors.items():
-                col[e, row(a, b)] = torch.tensor(v)
-        sim.cam_seg, sim.cam_color = seg.to(be.device), col.to(be.device)
+        env0 = sim.envs[0]
+        B = sim.cam_seg.shape[1]
         ncam = len(env0.cameras)
         sim.camera_groups = []
         for k in range(ncam):
@@ -747,6 +735,36 @@ class Gym:
                 g["flow_i16"] = torch.zeros(n, p.height, p.width, 2, dtype=torch.int16, device=be.device)
                 g["history"] = FlowHistory(n, B, be.device)
             sim.camera_groups.append(g)
+
+    def _prepare_render_scene(self, sim):
+        """The render scene of a prepared sim and the per-env segmentation / color tables (sim.renderer, sim.cam_seg,
+        sim.cam_color): what camera groups and the viewer draw from.  Built once."""
+        if sim.renderer is not None:
+            return
+        import torch
+        from ..render import DEFAULT_BODY_COLOR, Renderer, build_scene
+        be = sim.backend
+        if be.terrain.warped and not self._trimesh_cameras_enabled():
+            raise NotImplementedError("camera sensors cannot render a warped trimesh terrain (ShfTerrain.warped) unless "
+                                      "SHIFU_AMD_TRIMESH_CAMERAS=1 is set: height fields and planes only by default")
+        env0 = sim.envs[0]
+        model = env0.actors[0].asset.model
+        boxes = [a.asset.box_dim for a in env0.actors[1:]]
+        nb = model.blob.nb
+        B = nb + len(boxes)
+        hs = getattr(be, "height_samples", None) if be.terrain.rows > 0 else None
+        scene = build_scene(model.render_shapes, nb, boxes, height_samples=hs, vscale=be.terrain.vscale)
+        sim.renderer = Renderer(scene, be.terrain, be._heights if be.terrain.rows > 0 else None, be.device)
+        n = len(sim.envs)
+        row = lambda a, b: b if a == 0 else nb + a - 1
+        seg = torch.zeros(n, B, dtype=torch.int32)
+        col = torch.tensor(DEFAULT_BODY_COLOR, dtype=torch.float32).repeat(n, B, 1)
+        for e, env in enumerate(sim.envs):
+            for (a, b), v in env.seg_ids.items():
+                seg[e, row(a, b)] = v
+            for (a, b), v in env.colors.items():
+                col[e, row(a, b)] = torch.tensor(v)
+        sim.cam_seg, sim.cam_color = seg.to(be.device), col.to(be.device)
 
     def _group_of(self, sim, camera_handle):
         return sim.camera_groups[camera_handle]
@@ -840,14 +858,68 @@ class Gym:
             out["flow"] = g["flow_i16"]
         return out
 
-    # ---- graphics: accepted and ignored (no viewer on this path) ----------------
-    def create_viewer(self, *a, **k): return None
+    # ---- graphics: accepted and ignored by default (no window on this path).  SHIFU_AMD_VIEWER=<directory> opts into the
+    # headless viewer (shifu_amd/viewer.py): create_viewer then returns a Viewer -- one camera over all envs, laid out on
+    # create_env's grid --, draw_viewer renders it and write_viewer_image_to_file writes a PNG; IsaacGymEnv.render() numbers
+    # its frames into that directory.  Unset, every call below is the no-op it has always been.
+    @staticmethod
+    def _viewer_directory() -> Optional[str]:
+        return os.environ.get("SHIFU_AMD_VIEWER") or None
+
+    def create_viewer(self, sim=None, props=None, *a, **k):
+        if self._viewer_directory() is None or sim is None:
+            return None
+        from ..viewer import Viewer
+        if not sim.envs:
+            raise RuntimeError("create_viewer: create the envs first (the viewer is laid out on create_env's grid)")
+        self._check_renderable_terrain(sim)
+        p = props if props is not None else CameraProperties()
+        sx, sy, per_row = sim.env_grid
+        grid = sx != 0.0 or sy != 0.0
+
+        def source():
+            # the first draw: the sim is on the device by now, and so are its scene and tables (shared with the cameras)
+            if sim.backend is None:
+                raise RuntimeError("draw_viewer: prepare_sim first")
+            self._prepare_render_scene(sim)
+            return sim.renderer, sim.backend.tensors[_abi.T_BODY_STATE], sim.cam_seg, sim.cam_color
+
+        v = Viewer(None, len(sim.envs), None, None, None, int(p.width), int(p.height), float(p.horizontal_fov),
+                   max(float(p.near_plane), 1e-3), min(float(p.far_plane), 1e4), layout="grid" if grid else "world",
+                   spacing=(sx, sy), per_row=per_row, source=source)
+        v.sim = sim
+        return v
+
     def subscribe_viewer_keyboard_event(self, *a, **k): pass
-    def viewer_camera_look_at(self, *a, **k): pass
+
+    def viewer_camera_look_at(self, viewer=None, env=None, pos=None, target=None, *a, **k):
+        """pos / target: world coordinates with env None, else relative to where the viewer puts that env."""
+        if viewer is None:
+            return
+        off = np.zeros(3) if env is None else viewer.env_offset(env.index)
+        viewer.look_at(np.array(tuple(pos), float) + off, np.array(tuple(target), float) + off)
+
     def query_viewer_has_closed(self, viewer): return False
     def query_viewer_action_events(self, viewer): return []
     def step_graphics(self, sim): pass
-    def draw_viewer(self, *a, **k): pass
+
+    def draw_viewer(self, viewer=None, sim=None, *a, **k):
+        if viewer is None:
+            return
+        s = viewer.sim
+        if s.backend is not None and not s.body_fresh:
+            self.refresh_rigid_body_state_tensor(s)
+        viewer.draw()
+
+    def write_viewer_image_to_file(self, viewer, path):
+        """Isaac Gym's name: the viewer's last drawn color image as a PNG (a host copy: it waits for the draw)."""
+        if viewer is None:
+            return
+        from ..viewer import write_png
+        if viewer.images is None:
+            self.draw_viewer(viewer)
+        write_png(path, viewer.images["rgba"].cpu().numpy())
+
     def sync_frame_time(self, sim): pass
     def poll_viewer_events(self, viewer): pass
     def set_light_parameters(self, *a, **k): pass

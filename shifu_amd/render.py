@@ -271,6 +271,47 @@ class Renderer:
                                            ptr(body_state), ptr(cam_pose), ptr(seg), ptr(color), ptr(depth), ptr(seg_out),
                                            ptr(rgba), _stream_ptr(self.device)))
 
+    def render_world(self, body_state, view_pose, seg, color, camera: "_abi.ShfCamera", env_ids=None, env_offset=None,
+                     env_radius: float = 0.0, depth=None, seg_out=None, rgba=None, env_out=None):
+        """One launch of shf_render_world: view_pose (V, 7) cameras that each see many envs.  body_state (N * num_bodies,
+        13), seg (N, num_bodies) int32 and color (N, num_bodies, 3) f32 are render()'s per-env tables, N their number of
+        rows.  env_ids (E,) int32: the envs drawn (None: all N, in order); env_offset (E, 3) f32: the displacement of the
+        env at each LIST POSITION (None: zeros); env_radius > 0: a sphere about body 0 that bounds every env, for the
+        env-level cull (0: none).  Writes depth (V, H, W) f32, seg_out (V, H, W) int32, rgba (V, H, W, 4) u8 and env_out
+        (V, H, W) int32 -- the env id a pixel shows, -1 for the terrain or nothing -- each optional.  The tie rule: module
+        docstring of shifu_amd/viewer.py.  A warped terrain takes the kernel's trimesh form."""
+        import torch
+        from ._lib import check, lib
+        from .backend import _stream_ptr
+        B, H, W = self.scene.num_bodies, camera.height, camera.width
+        for name, t in (("body_state", body_state), ("view_pose", view_pose), ("seg", seg)):
+            if not isinstance(t, torch.Tensor) or t.dim() < 1:
+                raise ValueError(f"render_world: {name} must be a tensor")
+        n, v = int(seg.shape[0]), int(view_pose.shape[0])
+        if n < 1 or v < 1:
+            raise ValueError("render_world: no envs or no views")
+        e = n if env_ids is None else int(env_ids.shape[0]) if env_ids.dim() == 1 else -1
+        if e < 1:
+            raise ValueError("render_world: env_ids must be a non-empty (E,) int32 tensor")
+        for t, shape, dt in ((body_state, (n * B, 13), torch.float32), (view_pose, (v, 7), torch.float32),
+                             (seg, (n, B), torch.int32), (color, (n, B, 3), torch.float32), (env_ids, (e,), torch.int32),
+                             (env_offset, (e, 3), torch.float32), (depth, (v, H, W), torch.float32),
+                             (seg_out, (v, H, W), torch.int32), (rgba, (v, H, W, 4), torch.uint8),
+                             (env_out, (v, H, W), torch.int32)):
+            if t is None:
+                continue
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"render_world: expected a contiguous {dt} tensor of shape {shape} on {self.device}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+        if not np.isfinite(float(env_radius)):
+            raise ValueError("render_world: env_radius must be finite")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(self.device):
+            check(lib().shf_render_world(ptr(self._scene_dev), C.byref(self.terrain), ptr(self._heights), C.byref(camera), v,
+                                         ptr(view_pose), n, e, ptr(env_ids), ptr(env_offset), C.c_float(float(env_radius)),
+                                         ptr(body_state), ptr(seg), ptr(color), ptr(depth), ptr(seg_out), ptr(rgba),
+                                         ptr(env_out), _stream_ptr(self.device)))
+
 
 # -- optical flow -------------------------------------------------------------------------------------------------------
 def flow_to_i16(flow, W: int, H: int):

@@ -16,6 +16,11 @@ three others, against a previous frame one env step older, valid in every env), 
 reports both medians and their ratio.
 
     python tools/bench_camera.py --envs 1000 --flow
+
+--scene world: the headless viewer's world-view launch at 640 x 360 over --envs A1 robots on the height field, with and
+without the env-level cull, against the batched per-env render followed by a torch min composite (bench_world).
+
+    python tools/bench_camera.py --scene world --envs 4096
 """
 import argparse
 import json
@@ -142,15 +147,77 @@ def bench_a1(a):
     env.destroy()
 
 
+def bench_world(a):
+    """--scene world: the headless viewer's launch (shf_render_world) alone, 640 x 360, on FusedA1Env's height field with
+    --envs robots, from a camera behind env 0 that looks over its neighbours -- with the env-level cull (env_radius from
+    the model) and without.  Baseline: what could be done before -- shf_render_cameras batched over the envs, every env's
+    camera at the viewer's pose minus its offset (here zero: the envs are apart on the terrain), then a torch min over the
+    envs' depth images and a gather of the color.  All three are timed in interleaved blocks, --repeats times each;
+    reported as median [min .. max] ms."""
+    import statistics
+    import torch
+    from shifu_amd.gym.a1_fused import FusedA1Env
+    from shifu_amd.render import camera_struct
+    W, H = 640, 360
+    env = FusedA1Env(num_envs=a.envs, terrain="heightfield")
+    env.cam_seg.fill_(1)
+    v = env.add_viewer(W, H, 90.0, 0.05, 100.0)
+    env.reset()
+    g = torch.Generator().manual_seed(0)
+    for _ in range(3):
+        env.step((2 * torch.rand(env.num_envs, env.num_actions, generator=g) - 1).to(env.device))
+    v.follow(0, body=0, offset=(-3.0, -3.0, 2.5))
+    im = v.draw()
+    d = v._dev
+    r, N = env._renderer, env.num_envs
+    world = lambda radius: r.render_world(d["body_state"], d["pose"], d["seg"], d["color"], d["camera"], env_ids=d["env_ids"],
+                                          env_radius=radius, depth=d["depth"], rgba=d["rgba"])
+    # the baseline's buffers: one image per env
+    pose = d["pose"].repeat(N, 1).contiguous()
+    cam = camera_struct(W, H, 90.0, 0.05, 100.0)
+    bd = torch.empty(N, H, W, device=env.device)
+    bc = torch.empty(N, H, W, 4, dtype=torch.uint8, device=env.device)
+
+    def baseline():
+        r.render(env.body_state, pose, env.cam_seg, env.cam_color, cam, depth=bd, rgba=bc)
+        depth, first = bd.min(0)
+        return depth, torch.gather(bc.view(torch.int32).view(N, H, W), 0, first.unsqueeze(0))[0]
+
+    depth0, color0 = baseline()
+    torch.cuda.synchronize()
+    same_depth = bool(torch.equal(depth0, d["depth"][0]))
+    same_color = bool(torch.equal(color0, d["rgba"][0].view(torch.int32).view(H, W)))
+    runs = {"world_cull_off": [], "world_cull_on": [], "baseline_batched_min": []}
+    slow = max(3, a.renders // 20)
+    for _ in range(a.repeats):
+        runs["world_cull_off"].append(time_renders(lambda: world(0.0), a.warmup, a.renders))
+        runs["world_cull_on"].append(time_renders(lambda: world(v.env_radius), a.warmup, a.renders))
+        runs["baseline_batched_min"].append(time_renders(baseline, 1, slow))
+    world(v.env_radius)
+    torch.cuda.synchronize()
+    env_seen = int((torch.unique(v.draw()["env"]) >= 0).sum())
+    out = dict(bench="world_view", scene="a1-heightfield", envs=N, width=W, height=H, renders=a.renders, repeats=a.repeats,
+               baseline_renders=slow, env_radius=round(v.env_radius, 4), envs_in_view=env_seen,
+               pixels_on_robots=round(float((im["env"] >= 0).float().mean()), 4),
+               baseline_depth_bit_equal=same_depth, baseline_color_bit_equal=same_color, device=torch.cuda.get_device_name(0))
+    for k, xs in runs.items():
+        out["ms_" + k] = dict(median=round(statistics.median(xs), 4), min=round(min(xs), 4), max=round(max(xs), 4),
+                              runs=[round(x, 4) for x in xs])
+    print(json.dumps(out))
+    env.destroy()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1000)
     ap.add_argument("--renders", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--scene", choices=["abb", "a1-heightfield", "a1-trimesh"], default="abb")
+    ap.add_argument("--scene", choices=["abb", "a1-heightfield", "a1-trimesh", "world"], default="abb")
     ap.add_argument("--flow", action="store_true", help="also time the launch with optical flow, alternating with the one without")
     ap.add_argument("--repeats", type=int, default=3, help="--flow: timed runs of each form")
     a = ap.parse_args()
+    if a.scene == "world":
+        return bench_world(a)
     if a.scene != "abb":
         return bench_a1(a)
     import torch

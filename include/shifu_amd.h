@@ -1011,6 +1011,46 @@ int shf_render_world(const ShfRenderScene* scene_dev, const ShfTerrain* terrain,
                      const int32_t* seg_ids, const float* colors, float* depth_or_null, int32_t* seg_or_null,
                      uint8_t* rgba_or_null, int32_t* env_or_null, void* stream);
 
+/* Ray caster (lidar, height scanners, point clouds; shifu_amd/raycast.py): num_rays arbitrary rays, the same
+ * pattern in every env, cast from one sensor pose per env through the cameras' intersection code.  Additive entries again:
+ * no new SHF_ABI_VERSION, no struct layout changed.  scene_dev / terrain / height_samples_dev / body_state: as for
+ * shf_render_cameras.  ray_origin / ray_dir (num_rays, 3): the pattern in the sensor frame, directions of any non-zero
+ * length; sensor_pose (num_envs, 7) pos p + quat xyzw.  With the rotation R that `align` chooses, ray r of env e starts at
+ * p_e + R o_r and runs along unit(R d_r) (a true 1 / sqrtf), so the ray parameter is the Euclidean RANGE, not a view depth.
+ * A ray reports the nearest surface ENTERED at a range in [min_range, max_range] (the cameras' rule with range in the place
+ * of depth); among shapes at equal range the lower shape index wins, and the terrain wins only where it is strictly nearer.
+ * shape_mask: bit k clear = shape k of the scene is not cast at all (a scanner on the trunk must not see the robot's legs).
+ * Outputs, each optional but not all NULL -- on a hit: dist (num_envs, num_rays) the range; points (num_envs, num_rays, 3)
+ * origin + range x direction, world frame; normal (.., 3) the unit outward surface normal, world frame; seg the hit body's
+ * seg_ids entry (0: terrain); body the hit shape's body_state row WITHIN the env (ShfRenderShape.body; -1: terrain or
+ * plane).  On a miss: dist +inf, points the ray's end at max_range (finite, so a policy can consume it), normal 0, seg 0,
+ * body -2.  A ray whose rotated direction is zero or not finite is a miss and its points are its origin.  Refused: num_envs
+ * or num_rays < 1, null inputs, every output NULL, align outside 0..2, !(0 <= min_range <= max_range), a max_range that is
+ * not finite, seg_or_null without seg_ids (seg_ids may be NULL otherwise), more than 2^31 - 1 workgroups (one per env and
+ * 256 rays).  No atomics, no host sync, no allocation: stream-ordered and capturable; a ray's outputs depend on its own
+ * env's inputs and its own (o_r, d_r) only -- not on the rays that share its wavefront or workgroup. */
+#define SHF_RAY_ALIGN_BASE  0   /* rays rotate with the sensor's full orientation                      */
+#define SHF_RAY_ALIGN_YAW   1   /* ... with its yaw only: Rz(atan2(R[1][0], R[0][0])), R from the quat */
+#define SHF_RAY_ALIGN_WORLD 2   /* ... not at all: only the sensor's position is used                  */
+int shf_raycast(const ShfRenderScene* scene_dev, const ShfTerrain* terrain, const int16_t* height_samples_dev,
+                int32_t num_envs, int32_t num_rays, const float* ray_origin, const float* ray_dir, const float* body_state,
+                const float* sensor_pose, int32_t align, float min_range, float max_range, uint64_t shape_mask,
+                const int32_t* seg_ids, float* dist_or_null, float* points_or_null, float* normal_or_null,
+                int32_t* seg_or_null, int32_t* body_or_null, void* stream);
+/* Debug switch of the launches that follow (process-wide, host side): 0 turns off shf_raycast's per-ray bounding-sphere
+ * cull, 1 (the default) turns it on; returns the previous value.  The cull is conservative: the outputs are bit-equal
+ * either way, which is what the tests use this for. */
+int shf_raycast_debug_cull(int32_t enable);
+
+/* The point behind every pixel of a rendered depth image: X = o + s d with d the pixel ray of the camera convention above
+ * (d = fwd + right x t + up y t H/W: its component along the view axis is 1) and s = |depth|, so either sign convention of
+ * ShfCamera.depth_negative works; a depth that is not finite (nothing hit) takes s = far_plane.  depth (num_envs, H, W) as
+ * rendered; cam_pose (num_envs, 7), read only when world_frame != 0 (may be NULL otherwise); points (num_envs, H, W, 3).
+ * world_frame != 0: world coordinates, o and the basis from cam_pose.  world_frame == 0: the camera's own axes (+x the view
+ * axis, +y left, +z up), exactly (s, -s (x t), s (y t H/W)).  One element-wise launch; stream-ordered and capturable. */
+int shf_camera_points(const ShfCamera* camera, int32_t num_envs, const float* depth, const float* cam_pose,
+                      int32_t world_frame, float* points, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

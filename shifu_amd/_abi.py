@@ -98,6 +98,8 @@ RENDER_LIGHT = (0.40824829, 0.40824829, 0.81649658)
 RENDER_BG = (140, 170, 200)
 # world view (shf_render_world): candidate records a workgroup lists before a flush; (env, shape) pairs examined per pass
 RENDER_WORLD_LIST, RENDER_WORLD_CHUNK = 512, 256
+# ray caster (shf_raycast): how the rays follow the sensor's orientation -- all of it, its yaw only, not at all
+RAY_ALIGN_BASE, RAY_ALIGN_YAW, RAY_ALIGN_WORLD = 0, 1, 2
 
 
 class ShfRenderShape(C.Structure):

@@ -97,6 +97,13 @@ _SIGS = {
     # body_state, seg_ids, colors, depth, seg, rgba, env, stream
     "shf_render_world": ([vp, C.POINTER(_abi.ShfTerrain), vp, C.POINTER(_abi.ShfCamera), i32, vp, i32, i32, vp, vp, C.c_float]
                          + [vp] * 3 + [vp] * 4 + [vp], i32),
+    # ray caster: scene, terrain, heights, num_envs, num_rays, ray_origin, ray_dir, body_state, sensor_pose, align, min_range,
+    # max_range, shape_mask, seg_ids, dist, points, normal, seg, body, stream
+    "shf_raycast": ([vp, C.POINTER(_abi.ShfTerrain), vp, i32, i32, vp, vp, vp, vp, i32, C.c_float, C.c_float, C.c_uint64, vp]
+                    + [vp] * 5 + [vp], i32),
+    "shf_raycast_debug_cull": ([i32], i32),
+    # camera, num_envs, depth, cam_pose, world_frame, points, stream
+    "shf_camera_points": ([C.POINTER(_abi.ShfCamera), i32, vp, vp, i32, vp, vp], i32),
     # conv-encoder inference (csrc/shf_conv.hip)
     "shf_conv_pack_bytes": ([i32, i32, C.POINTER(i64)], i32),
     "shf_conv_pack_weights": ([vp, vp, i32, i32, vp], i32),

@@ -96,6 +96,10 @@ BUDGETS = [("_Z16k_a1_step_a1_g32", 256, 0),          # default: A1, two envs pe
            # build (the per-pixel hit record, two cones, a pass's shape pose before it is listed) plus a margin of 10; the 52 KB
            # candidate list in LDS holds them to three waves per SIMD either way; nothing on the stack
            ("_Z14k_render_world", 134, 0), ("_Z17k_render_world_tw", 134, 0),
+           # the ray caster (k_raycast / k_raycast_tw behind shf_raycast): 56 and 83 registers in the first clean build (one
+           # ray per lane: its origin, direction, best hit and normal; the shape table sits in LDS) plus a margin of 10 -- 8 and
+           # 5 waves per SIMD; nothing on the stack
+           ("_Z9k_raycast", 66, 0), ("_Z12k_raycast_tw", 93, 0),
            # the conv-encoder layer (csrc/shf_conv.hip), every instantiation: 214 registers at most in the first clean build (64
            # accumulators, a chunk's weight fragments, the gathered rows in flight) plus a margin of 10 for compiler drift -- still
            # two waves per SIMD; nothing on the stack

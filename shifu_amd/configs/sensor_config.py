@@ -1,5 +1,6 @@
 """Sensor configs (reference shifu/configs/sensor_config.py).  Camera sensors are rendered by a ray caster against the
-collision geometry (shifu_amd/units/sensors.py, shifu_amd/render.py)."""
+collision geometry (shifu_amd/units/sensors.py, shifu_amd/render.py); RayCasterSensorConfig (no counterpart in the reference, whose
+to-do list names point clouds) configures a ray-caster sensor on the same caster: a height scanner, a lidar, any pattern."""
 from shifu_amd.isaacgym import gymapi
 
 from .base_config import BaseConfig
@@ -35,3 +36,21 @@ class CameraSensorConfig(BaseSensorConfig):
         near_plane = 0.1
         far_plane = 3
         horizontal_fov = 87
+
+
+class RayCasterSensorConfig(BaseSensorConfig):
+    """units.RayCasterSensor: `pattern` is (origins (R, 3), dirs (R, 3)) in the sensor frame -- shifu_amd.raycast.grid_pattern,
+    lidar_pattern, pinhole_pattern or any arrays.  The sensor sits at `transform` = [position, quat xyzw] in the frame of the
+    state tensors, or at `attach_local_transform` in the frame of the robot's rigid body `attach_body_name`.  align: "base"
+    (the rays turn with the sensor), "yaw" (with its yaw about world z only) or "world"; [min_range, max_range] in metres of
+    Euclidean range; ignore_robot: the rays pass through the robot's own bodies (a scanner on the trunk must not report the
+    legs)."""
+    name = "DummyRayCasterSensor"
+    pattern = None
+    transform = None
+    attach_local_transform = None
+    attach_body_name = None
+    align = "base"
+    min_range = 0.0
+    max_range = 10.0
+    ignore_robot = True

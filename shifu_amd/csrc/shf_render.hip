@@ -32,6 +32,10 @@
 //
 // World view (kernels k_render_world / k_render_world_tw behind shf_render_world, at the end of this file): one camera that
 // sees many envs, each displaced by an offset -- the headless viewer.  Same rays, intersections, walk and shading.
+//
+// Ray caster (kernels k_raycast / k_raycast_tw behind shf_raycast, and k_camera_points behind shf_camera_points, after the
+// world view): arbitrary rays per env -- height scanners, lidars -- through the same intersections and walk, the ray
+// parameter being the Euclidean range; and the point behind every pixel of a rendered depth image.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -942,4 +946,287 @@ extern "C" int shf_render_world(const ShfRenderScene* scene_dev, const ShfTerrai
                      num_drawn, env_ids_or_null, env_offset_or_null, env_radius, body_state, seg_ids, colors, depth_or_null,
                      seg_or_null, reinterpret_cast<uint32_t*>(rgba_or_null), env_or_null);
   return hipGetLastError() == hipSuccess ? 0 : shf_set_error("shf_render_world: launch failed");
+}
+
+// ---- ray caster (shf_raycast; lidar, height scanners, point clouds -- shifu_amd/raycast.py) ---------------------------------
+// Arbitrary rays, the same for every env, from a sensor pose per env: ray r of env e starts at p_e + R o_r and runs along
+// unit(R d_r), R the sensor's rotation as `align` takes it.  The ray parameter is the Euclidean range, so [min_range,
+// max_range] are ranges where the cameras' [near, far] are view depths; otherwise the cameras' hit rule and tie rules.
+// One 256-thread workgroup per (env, chunk of 256 rays), one ray per lane; the env's shape world poses are staged once per
+// workgroup into LDS (one thread per shape, no colors).  There is no strip and so no cone: the loop over the unmasked shapes
+// is wave-uniform, every lane tests its own ray -- the closest approach of the segment [min_range, min(best, max_range)] to
+// the shape's bounding sphere -- and a ballot skips the shape for the wave when no lane can hit it; the lanes that passed
+// run the closed form.  The test is conservative (RC_SLACK), so a lane's result is what it is with the cull off
+// (shf_raycast_debug_cull), and it never depends on the other lanes.  The checker is tests/raycast_ref.py.
+#define RC_SW 16   // floats per shape in LDS: c[3] R[9] param[3] radius
+
+namespace {
+
+// Can the ray (o, unit d) meet the sphere (c, r) at a range in [t0, t1]?  The closest point of that segment to the centre,
+// against r plus a slack far above the float32 error of either this test or the closed forms (both ~1e-7 of the distances
+// involved): 1e-3 r + 1e-4 m + 1e-5 of the range of closest approach.  A NaN fails, as it fails the closed forms' range test.
+__device__ __forceinline__ bool rc_may_hit(const float* o, const float* d, const float* c, float r, float t0, float t1) {
+  const float v[3] = {c[0] - o[0], c[1] - o[1], c[2] - o[2]};
+  const float tc = fminf(fmaxf(dot3(v, d), t0), t1);
+  const float w[3] = {v[0] - tc * d[0], v[1] - tc * d[1], v[2] - tc * d[2]};
+  const float re = r * 1.001f + 1e-4f + 1e-5f * (tc + r);
+  return dot3(w, w) <= re * re;
+}
+
+}  // namespace
+
+template <bool TW>
+__device__ __forceinline__ void raycast(const ShfRenderScene* __restrict__ scene, const ShfTerrain& T,
+                                        const int16_t* __restrict__ hsamp, int num_rays, int chunks,
+                                        const float* __restrict__ ray_origin, const float* __restrict__ ray_dir,
+                                        const float* __restrict__ body_state, const float* __restrict__ sensor_pose, int align,
+                                        float min_range, float max_range, uint64_t shape_mask, const int32_t* __restrict__ seg_ids,
+                                        float* __restrict__ dist, float* __restrict__ points, float* __restrict__ normal,
+                                        int32_t* __restrict__ seg_out, int32_t* __restrict__ body_out, int cull) {
+  __shared__ float S[SHF_RENDER_MAX_SHAPES * RC_SW];
+  __shared__ int SI[SHF_RENDER_MAX_SHAPES * 4];   // kind, poly, segmentation id, body row within the env
+  const int env = blockIdx.x / chunks, chunk = blockIdx.x - env * chunks;
+  const int lid = threadIdx.x;
+  const int ray = chunk * RT_THREADS + lid;
+  const bool active = ray < num_rays;
+  // (the scene is device data: its counts are clamped to the LDS tables here, not trusted)
+  const int ns = min(max(scene->nshapes, 0), SHF_RENDER_MAX_SHAPES), B = max(scene->num_bodies, 1);
+
+  if (lid < ns) {
+    const ShfRenderShape& sh = scene->shape[lid];
+    const int brow = min(max(sh.body, 0), B - 1);
+    const size_t row = (size_t)env * B + brow;
+    const float* bsr = body_state + row * 13;
+    float Rb[9];
+    {
+      const float q[4] = {bsr[3], bsr[4], bsr[5], bsr[6]};
+      quat_mat(q, Rb);
+    }
+    float* s = S + lid * RC_SW;
+    for (int r = 0; r < 3; r++) {
+      s[r] = bsr[r] + Rb[3 * r] * sh.pos[0] + Rb[3 * r + 1] * sh.pos[1] + Rb[3 * r + 2] * sh.pos[2];
+      for (int c = 0; c < 3; c++)
+        s[3 + 3 * r + c] = Rb[3 * r] * sh.rot[c] + Rb[3 * r + 1] * sh.rot[3 + c] + Rb[3 * r + 2] * sh.rot[6 + c];
+      s[12 + r] = sh.param[r];
+    }
+    s[15] = sh.radius;
+    SI[lid * 4] = sh.kind;
+    SI[lid * 4 + 1] = sh.poly;
+    SI[lid * 4 + 2] = seg_ids ? seg_ids[row] : 0;
+    SI[lid * 4 + 3] = brow;
+  }
+
+  // the sensor's rotation as `align` takes it: all of it, its yaw about world z only, or none
+  const float* sp = sensor_pose + (size_t)env * 7;
+  float Rs[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+  if (align != SHF_RAY_ALIGN_WORLD) {
+    const float q[4] = {sp[3], sp[4], sp[5], sp[6]};
+    quat_mat(q, Rs);
+    if (align == SHF_RAY_ALIGN_YAW) {
+      // Rz(atan2(R10, R00)) by its cosine and sine (R00, R10) / |(R00, R10)|; the sensor's x axis vertical: no yaw
+      const float h = sqrtf(Rs[0] * Rs[0] + Rs[3] * Rs[3]);
+      const float cy = h > 0.0f ? Rs[0] / h : 1.0f, sy = h > 0.0f ? Rs[3] / h : 0.0f;
+      Rs[0] = cy;   Rs[1] = -sy;  Rs[2] = 0.0f;
+      Rs[3] = sy;   Rs[4] = cy;   Rs[5] = 0.0f;
+      Rs[6] = 0.0f; Rs[7] = 0.0f; Rs[8] = 1.0f;
+    }
+  }
+  float o[3] = {sp[0], sp[1], sp[2]}, d[3] = {1.0f, 0.0f, 0.0f};
+  bool valid = false;   // a ray of this pattern with a usable direction; the others vote "no" and cast nothing
+  if (active) {
+    const float* ro = ray_origin + (size_t)ray * 3;
+    const float* rd = ray_dir + (size_t)ray * 3;
+    const float a[3] = {ro[0], ro[1], ro[2]}, b[3] = {rd[0], rd[1], rd[2]};
+    float dw[3];
+    for (int k = 0; k < 3; k++) {
+      o[k] += Rs[3 * k] * a[0] + Rs[3 * k + 1] * a[1] + Rs[3 * k + 2] * a[2];
+      dw[k] = Rs[3 * k] * b[0] + Rs[3 * k + 1] * b[1] + Rs[3 * k + 2] * b[2];
+    }
+    const float l2 = dot3(dw, dw);
+    if (l2 > 0.0f && l2 < INFINITY) {      // (a NaN fails both)
+      const float il = 1.0f / sqrtf(l2);
+      for (int k = 0; k < 3; k++) d[k] = dw[k] * il;
+      valid = true;
+    }
+  }
+  __syncthreads();
+
+  float best = INFINITY, nw[3] = {0.0f, 0.0f, 0.0f};
+  int best_i = -1;
+  for (int i = 0; i < ns; i++) {
+    if (!((shape_mask >> i) & 1ull)) continue;
+    const float* s = S + i * RC_SW;
+    const bool may = valid && (!cull || rc_may_hit(o, d, s, s[15], min_range, fminf(best, max_range)));
+    if (!__ballot(may)) continue;
+    if (!may) continue;
+    const float rel[3] = {o[0] - s[0], o[1] - s[1], o[2] - s[2]};
+    float ol[3], dl[3];
+    for (int k = 0; k < 3; k++) {     // into the shape frame: R^T (.)
+      ol[k] = s[3 + k] * rel[0] + s[6 + k] * rel[1] + s[9 + k] * rel[2];
+      dl[k] = s[3 + k] * d[0] + s[6 + k] * d[1] + s[9 + k] * d[2];
+    }
+    const int kind = SI[i * 4];
+    float nl[3] = {0.0f, 0.0f, 1.0f}, sh;
+    if (kind == SHF_RENDER_BOX) {
+      const float h[3] = {s[12], s[13], s[14]};
+      sh = hit_box(ol, dl, h, nl);
+    } else if (kind == SHF_RENDER_SPHERE) {
+      sh = hit_sphere(ol, dl, s[12], nl);
+    } else if (kind == SHF_RENDER_CAPSULE) {
+      sh = hit_capsule(ol, dl, s[12], s[13], nl);
+    } else {
+      const int p = __builtin_amdgcn_readfirstlane(min(max(SI[i * 4 + 1], 0), SHF_RENDER_MAX_POLYS - 1));
+      sh = hit_poly(&scene->poly[p], ol, dl, nl);
+    }
+    if (sh >= min_range && sh <= max_range && sh < best) {
+      best = sh;
+      best_i = i;
+      for (int k = 0; k < 3; k++) nw[k] = s[3 + 3 * k] * nl[0] + s[4 + 3 * k] * nl[1] + s[5 + 3 * k] * nl[2];
+    }
+  }
+
+  if (valid && scene->ground) {
+    const float lim = fminf(best, max_range);
+    float nn[3], sg = INFINITY;
+    if (T.rows == 0) {
+      if (d[2] < 0.0f) {
+        const float s = -o[2] / d[2];
+        if (s >= min_range && s <= lim) { sg = s; nn[0] = 0.0f; nn[1] = 0.0f; nn[2] = 1.0f; }
+      }
+    } else {
+      sg = hit_heightfield<TW>(T, hsamp, scene->hf_zmin, scene->hf_zmax, o, d, min_range, lim, nn);
+    }
+    if (sg < best) {      // the terrain wins only where it is strictly nearer
+      best = sg;
+      best_i = -1;
+      nw[0] = nn[0]; nw[1] = nn[1]; nw[2] = nn[2];
+    }
+  }
+
+  if (!active) return;
+  const size_t ri = (size_t)env * num_rays + ray;
+  const bool any = best < INFINITY;
+  if (dist) dist[ri] = any ? best : INFINITY;
+  if (points) {
+    // the hit, or the ray's end at max_range (finite); a ray without a direction: its origin
+    const float s = any ? best : (valid ? max_range : 0.0f);
+    float* p = points + ri * 3;
+    p[0] = o[0] + s * d[0]; p[1] = o[1] + s * d[1]; p[2] = o[2] + s * d[2];
+  }
+  if (normal) {
+    float* n = normal + ri * 3;
+    if (any) {
+      const float il = 1.0f / sqrtf(dot3(nw, nw));
+      n[0] = nw[0] * il; n[1] = nw[1] * il; n[2] = nw[2] * il;
+    } else {
+      n[0] = 0.0f; n[1] = 0.0f; n[2] = 0.0f;
+    }
+  }
+  if (seg_out) seg_out[ri] = any && best_i >= 0 ? SI[best_i * 4 + 2] : 0;
+  if (body_out) body_out[ri] = !any ? -2 : best_i >= 0 ? SI[best_i * 4 + 3] : -1;
+}
+
+#define RC_KERNEL_ARGS                                                                                                        \
+  const ShfRenderScene *__restrict__ scene, ShfTerrain T, const int16_t *__restrict__ hsamp, int num_rays, int chunks,        \
+      const float *__restrict__ ray_origin, const float *__restrict__ ray_dir, const float *__restrict__ body_state,          \
+      const float *__restrict__ sensor_pose, int align, float min_range, float max_range, uint64_t shape_mask,                \
+      const int32_t *__restrict__ seg_ids, float *__restrict__ dist, float *__restrict__ points, float *__restrict__ normal,  \
+      int32_t *__restrict__ seg_out, int32_t *__restrict__ body_out, int cull
+
+__global__ void __launch_bounds__(RT_THREADS) k_raycast(RC_KERNEL_ARGS) {
+  raycast<false>(scene, T, hsamp, num_rays, chunks, ray_origin, ray_dir, body_state, sensor_pose, align, min_range, max_range,
+                 shape_mask, seg_ids, dist, points, normal, seg_out, body_out, cull);
+}
+__global__ void __launch_bounds__(RT_THREADS) k_raycast_tw(RC_KERNEL_ARGS) {
+  raycast<true>(scene, T, hsamp, num_rays, chunks, ray_origin, ray_dir, body_state, sensor_pose, align, min_range, max_range,
+                shape_mask, seg_ids, dist, points, normal, seg_out, body_out, cull);
+}
+
+// the per-ray cull of the launches that follow (a host-side debug switch: the tests assert that it changes no bit)
+static int g_raycast_cull = 1;
+
+extern "C" int shf_raycast_debug_cull(int32_t enable) {
+  const int was = g_raycast_cull;
+  g_raycast_cull = enable ? 1 : 0;
+  return was;
+}
+
+extern "C" int shf_raycast(const ShfRenderScene* scene_dev, const ShfTerrain* terrain, const int16_t* height_samples_dev,
+                           int32_t num_envs, int32_t num_rays, const float* ray_origin, const float* ray_dir,
+                           const float* body_state, const float* sensor_pose, int32_t align, float min_range, float max_range,
+                           uint64_t shape_mask, const int32_t* seg_ids, float* dist_or_null, float* points_or_null,
+                           float* normal_or_null, int32_t* seg_or_null, int32_t* body_or_null, void* stream) {
+  if (!scene_dev || !terrain) return shf_set_error("shf_raycast: null scene or terrain");
+  if (num_envs < 1 || num_rays < 1) return shf_set_error("shf_raycast: num_envs and num_rays must be at least 1");
+  if (!ray_origin || !ray_dir || !body_state || !sensor_pose) return shf_set_error("shf_raycast: null input tensor");
+  if (!dist_or_null && !points_or_null && !normal_or_null && !seg_or_null && !body_or_null)
+    return shf_set_error("shf_raycast: every output is null");
+  if (align < SHF_RAY_ALIGN_BASE || align > SHF_RAY_ALIGN_WORLD) return shf_set_error("shf_raycast: align must be SHF_RAY_ALIGN_BASE, _YAW or _WORLD");
+  if (!(min_range >= 0.0f && min_range <= max_range) || !(max_range < INFINITY))
+    return shf_set_error("shf_raycast: need 0 <= min_range <= max_range, max_range finite");
+  if (seg_or_null && !seg_ids) return shf_set_error("shf_raycast: a seg output needs seg_ids");
+  if (terrain->warped && terrain->rows == 0) return shf_set_error("shf_raycast: a warped (trimesh) terrain needs height samples");
+  if (terrain->rows != 0 && (terrain->rows < 2 || terrain->cols < 2 || !height_samples_dev))
+    return shf_set_error("shf_raycast: a height field needs at least 2 x 2 samples on the device");
+  const int64_t chunks = ((int64_t)num_rays + RT_THREADS - 1) / RT_THREADS;
+  if (chunks * num_envs > 0x7fffffffLL) return shf_set_error("shf_raycast: too many envs x ray chunks for one launch");
+  hipLaunchKernelGGL(terrain->warped ? k_raycast_tw : k_raycast, dim3((unsigned)(chunks * num_envs)), dim3(RT_THREADS), 0,
+                     (hipStream_t)stream, scene_dev, *terrain, height_samples_dev, num_rays, (int)chunks, ray_origin, ray_dir,
+                     body_state, sensor_pose, align, min_range, max_range, shape_mask, seg_ids, dist_or_null, points_or_null,
+                     normal_or_null, seg_or_null, body_or_null, g_raycast_cull);
+  return hipGetLastError() == hipSuccess ? 0 : shf_set_error("shf_raycast: launch failed");
+}
+
+// The point behind every pixel of a rendered depth image: X = o + s d, d the camera convention's pixel ray (its component
+// along the view axis is 1, so s is the view depth) and s = |depth| -- either sign convention of ShfCamera.depth_negative; a
+// depth that is not finite (nothing hit): s = far_plane.  One pixel per lane, a 12-byte store each.
+__global__ void __launch_bounds__(RT_THREADS) k_camera_points(ShfCamera cam, size_t total, const float* __restrict__ depth,
+                                                              const float* __restrict__ cam_pose, int world_frame,
+                                                              float* __restrict__ points) {
+  const size_t i = (size_t)blockIdx.x * RT_THREADS + threadIdx.x;
+  if (i >= total) return;
+  const int W = cam.width, Hh = cam.height;
+  const size_t hw = (size_t)W * Hh;
+  const size_t env = i / hw;
+  const int pix = (int)(i - env * hw);
+  const int rowp = pix / W, col = pix - rowp * W;
+  const float t = tanf(0.5f * cam.horizontal_fov * 0.017453292519943295f);
+  const float ty_scale = t * (float)Hh / (float)W;
+  const float iW = 1.0f / (float)W, iH = 1.0f / (float)Hh;
+  const float px = 2.0f * ((float)col + 0.5f) * iW - 1.0f, py = 1.0f - 2.0f * ((float)rowp + 0.5f) * iH;
+  const float dv = fabsf(depth[i]);
+  const float s = dv < INFINITY ? dv : cam.far_plane;     // (a NaN fails the comparison too)
+  float* p = points + i * 3;
+  if (world_frame) {
+    const float* cp = cam_pose + env * 7;
+    float Rc[9];
+    {
+      const float q[4] = {cp[3], cp[4], cp[5], cp[6]};
+      quat_mat(q, Rc);
+    }
+    const float fwd[3] = {Rc[0], Rc[3], Rc[6]}, right[3] = {-Rc[1], -Rc[4], -Rc[7]}, up[3] = {Rc[2], Rc[5], Rc[8]};
+    for (int k = 0; k < 3; k++) p[k] = cp[k] + s * (fwd[k] + right[k] * (px * t) + up[k] * (py * ty_scale));
+  } else {
+    // the camera's own axes: +x the view axis, +y to the left (right = -y), +z up
+    p[0] = s; p[1] = -(s * (px * t)); p[2] = s * (py * ty_scale);
+  }
+}
+
+extern "C" int shf_camera_points(const ShfCamera* camera, int32_t num_envs, const float* depth, const float* cam_pose,
+                                 int32_t world_frame, float* points, void* stream) {
+  if (!camera) return shf_set_error("shf_camera_points: null camera");
+  const ShfCamera& c = *camera;
+  if (c.width <= 0 || c.height <= 0 || c.width > 16384 || c.height > 16384)
+    return shf_set_error("shf_camera_points: width and height must be in 1..16384");
+  if (!(c.horizontal_fov > 0.0f && c.horizontal_fov < 180.0f))
+    return shf_set_error("shf_camera_points: horizontal_fov must be in (0, 180) degrees");
+  if (!(c.far_plane > 0.0f && c.far_plane < INFINITY)) return shf_set_error("shf_camera_points: far_plane must be positive and finite");
+  if (num_envs < 1) return shf_set_error("shf_camera_points: num_envs must be at least 1");
+  if (!depth || !points || (world_frame && !cam_pose)) return shf_set_error("shf_camera_points: null depth, points or cam_pose");
+  const size_t total = (size_t)num_envs * c.width * c.height;
+  const size_t blocks = (total + RT_THREADS - 1) / RT_THREADS;
+  if (blocks > 0x7fffffffULL) return shf_set_error("shf_camera_points: too many pixels for one launch");
+  hipLaunchKernelGGL(k_camera_points, dim3((unsigned)blocks), dim3(RT_THREADS), 0, (hipStream_t)stream, c, total, depth, cam_pose,
+                     world_frame, points);
+  return hipGetLastError() == hipSuccess ? 0 : shf_set_error("shf_camera_points: launch failed");
 }

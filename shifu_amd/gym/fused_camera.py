@@ -44,6 +44,7 @@ class FusedCamera:
         self._images = dict(rgba=torch.zeros(n, self.height, self.width, 4, dtype=torch.uint8, device=dev),
                             depth=torch.full((n, self.height, self.width), -float("inf"), dtype=torch.float32, device=dev),
                             seg=torch.zeros(n, self.height, self.width, dtype=torch.int32, device=dev))
+        self._clouds = {}                                        # point_cloud(): allocated on first use
         self.flow = bool(flow)
         if self.flow:
             self._images["flow"] = torch.zeros(n, self.height, self.width, 2, dtype=torch.float32, device=dev)
@@ -91,6 +92,17 @@ class FusedCamera:
         if self.flow:
             self.history.invalidate(env_ids)
 
+    def point_cloud(self, world_frame: bool = True) -> torch.Tensor:
+        """(N, H, W, 3) f32: the point behind every pixel of the LAST render's depth image (shf_camera_points), in world
+        coordinates on the camera poses as they are now -- call it after render(), before the next step -- or, with
+        world_frame=False, in the camera's own axes (+x view axis, +y left, +z up).  A pixel that shows nothing: the point at
+        far_plane along its ray.  One launch into a tensor allocated on first use; no host sync."""
+        key = "points_w" if world_frame else "points_c"
+        if key not in self._clouds:
+            self._clouds[key] = torch.zeros(self.env.num_envs, self.height, self.width, 3, dtype=torch.float32, device=self.env.device)
+        self.env._renderer.camera_points(self._images["depth"], self.world_pose(), self.camera, self._clouds[key], world_frame)
+        return self._clouds[key]
+
     def raw_images(self):
         """{"rgba": (N, H, W, 4) u8, "depth": (N, H, W) f32, negative view depth, -inf where nothing is hit, "seg":
         (N, H, W) i32} -- the tensors render() writes (CameraSensor.raw_images's conventions).  Views, not copies.  A camera
@@ -98,8 +110,68 @@ class FusedCamera:
         return self._images
 
 
+class FusedRayCaster:
+    """A ray-caster sensor in every env (shifu_amd/raycast.py; shf_raycast): one pattern, one launch per cast().  Fixed:
+    pose (position, quat) in the frame of root_state.  Attached: the pose is body pose o (position, quat) at every cast.
+    origins / dirs: the pattern on the device; align, min_range, max_range, shape_mask: as Renderer.raycast takes them."""
+
+    def __init__(self, env, pattern, position, quat, attach_body: Optional[int], align: str, min_range: float, max_range: float,
+                 shape_mask: int, outputs: Sequence[str]):
+        from ..raycast import ALIGN, check_pattern
+        n, dev = env.num_envs, env.device
+        o, d = check_pattern(*pattern)
+        if align not in ALIGN:
+            raise ValueError(f"add_ray_caster: align must be one of {sorted(ALIGN)}, got {align!r}")
+        if not (0.0 <= float(min_range) <= float(max_range) and np.isfinite(float(max_range))):
+            raise ValueError("add_ray_caster: need 0 <= min_range <= max_range, max_range finite")
+        names = ("dist", "points", "normal", "seg", "body")
+        if not outputs or any(k not in names for k in outputs):
+            raise ValueError(f"add_ray_caster: outputs must name some of {names}, got {tuple(outputs)}")
+        self.env = env
+        self.origins, self.dirs = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
+        self.num_rays = int(o.shape[0])
+        self.align, self.min_range, self.max_range = align, float(min_range), float(max_range)
+        self.shape_mask = int(shape_mask)
+        self.attach_body = None if attach_body is None else int(attach_body)
+        B = env.cam_seg.shape[1]
+        if self.attach_body is not None and not 0 <= self.attach_body < B:
+            raise ValueError(f"add_ray_caster: attach_body {attach_body} outside the env's {B} body-state rows")
+        pose = torch.tensor(np.concatenate([np.asarray(position, float), np.asarray(quat, float)]), dtype=torch.float32)
+        self.pose = pose.repeat(n, 1).to(dev).contiguous()
+        if self.attach_body is not None:
+            self._rows = torch.arange(n, device=dev, dtype=torch.long) * B + self.attach_body
+            self._world = torch.zeros(n, 7, dtype=torch.float32, device=dev)
+        R = self.num_rays
+        make = dict(dist=lambda: torch.full((n, R), float("inf"), dtype=torch.float32, device=dev),
+                    points=lambda: torch.zeros(n, R, 3, dtype=torch.float32, device=dev),
+                    normal=lambda: torch.zeros(n, R, 3, dtype=torch.float32, device=dev),
+                    seg=lambda: torch.zeros(n, R, dtype=torch.int32, device=dev),
+                    body=lambda: torch.full((n, R), -2, dtype=torch.int32, device=dev))
+        self._out = {k: make[k]() for k in names if k in outputs}
+
+    def world_pose(self) -> torch.Tensor:
+        """(N, 7) sensor poses (pos, quat xyzw) on the env's current body states."""
+        if self.attach_body is None:
+            return self.pose
+        from ..isaacgym.torch_utils import quat_apply, quat_mul
+        bs = self.env.body_state.index_select(0, self._rows)
+        return torch.cat([bs[:, :3] + quat_apply(bs[:, 3:7], self.pose[:, :3]), quat_mul(bs[:, 3:7], self.pose[:, 3:7])],
+                         dim=1, out=self._world)
+
+    def cast(self) -> dict:
+        """One launch for all envs on the body states of the last step / reset, into this sensor's own tensors; no host
+        sync.  {"dist": (N, R) f32 range, +inf a miss; "points": (N, R, 3) f32 world frame, a miss: the ray's end at
+        max_range; "normal": (N, R, 3); "seg": (N, R) int32 from env.cam_seg; "body": (N, R) int32 body-state row within
+        the env, -1 terrain, -2 a miss} -- those named in `outputs`.  Views, not copies."""
+        env, o = self.env, self._out
+        env._renderer.raycast(env.body_state, self.world_pose(), self.origins, self.dirs, self.align, self.min_range,
+                              self.max_range, self.shape_mask, seg=env.cam_seg if "seg" in o else None, dist=o.get("dist"),
+                              points=o.get("points"), normal=o.get("normal"), seg_out=o.get("seg"), body=o.get("body"))
+        return o
+
+
 class FusedCameraHost:
-    """What FusedA1Env and FusedAbbEnv share: the per-env segmentation / color tables and add_camera."""
+    """What FusedA1Env and FusedAbbEnv share: the per-env segmentation / color tables, add_camera and add_ray_caster."""
 
     def _init_cameras(self, box_dims: Sequence = (), reset_count=None):
         """box_dims: full extents of the env's box actors, in body-state row order after the articulation's bodies;
@@ -111,6 +183,7 @@ class FusedCameraHost:
         self.cam_seg = torch.zeros(self.num_envs, B, dtype=torch.int32, device=self.device)
         self.cam_color = torch.tensor(DEFAULT_BODY_COLOR, dtype=torch.float32, device=self.device).repeat(self.num_envs, B, 1)
         self.cameras = []
+        self.ray_casters = []
         self.viewers = []
         self._renderer = None
         self._cam_reset_count = reset_count
@@ -140,6 +213,28 @@ class FusedCameraHost:
         cam = FusedCamera(self, width, height, horizontal_fov, near_plane, far_plane, position, quat, attach_body, flow=flow)
         self.cameras.append(cam)
         return cam
+
+    def add_ray_caster(self, pattern, position=(0.0, 0.0, 0.0), quat=None, attach_body: Optional[int] = None,
+                       align: str = "base", min_range: float = 0.0, max_range: float = 10.0, ignore_bodies=(),
+                       outputs: Sequence[str] = ("dist", "points")) -> FusedRayCaster:
+        """A ray-caster sensor in every env -- a height scanner, a lidar, any (origins, dirs) pattern of shifu_amd/raycast.py
+        -- at `position` with orientation `quat` (xyzw) in the frame of root_state or, with attach_body (a row of the env's
+        body states), in that body's frame.  align: "base" (the rays turn with the sensor), "yaw" (with its yaw about world
+        z only: a height scanner under a pitching trunk keeps looking straight down) or "world".  ignore_bodies: body-state
+        rows whose shapes the rays pass through; "articulation": every row of the articulation (the box actors stay).
+        outputs: which of "dist", "points", "normal", "seg", "body" cast() writes.  Derived data, like the cameras."""
+        from ..render import shape_mask_for
+        quat = (0.0, 0.0, 0.0, 1.0) if quat is None else quat
+        quat = np.asarray(quat, float) / np.linalg.norm(quat)
+        r = self._ensure_renderer()
+        if isinstance(ignore_bodies, str):
+            if ignore_bodies != "articulation":
+                raise ValueError(f"add_ray_caster: ignore_bodies must be body rows or 'articulation', got {ignore_bodies!r}")
+            ignore_bodies = range(int(self.cm.blob.nb))
+        rc = FusedRayCaster(self, pattern, position, quat, attach_body, align, min_range, max_range,
+                            shape_mask_for(r.scene, ignore_bodies), tuple(outputs))
+        self.ray_casters.append(rc)
+        return rc
 
     def _ensure_renderer(self):
         from ..render import Renderer, build_scene

@@ -251,6 +251,7 @@ class SimHandle:
         self.num_actors = 0
         self.jacobian = None
         self.camera_groups: List[dict] = []   # after prepare_sim: one per camera handle (one camera per env each)
+        self.ray_caster_groups: List[dict] = []   # create_ray_caster_group: one ray-caster sensor per env each
         self.renderer = None
         self.body_fresh = False               # body_state refreshed since the last simulate (render_all_camera_sensors)
         self.env_grid = (0.0, 0.0, 1)         # create_env's (pitch x, pitch y, envs per row): the viewer's layout
@@ -857,6 +858,69 @@ class Gym:
         if "flow_i16" in g:
             out["flow"] = g["flow_i16"]
         return out
+
+    def camera_group_points(self, sim, camera_handle, world_frame=True):
+        """Not an Isaac Gym call: the (N, H, W, 3) f32 point behind every pixel of the group's last rendered depth image
+        (shf_camera_points), in the frame of the state tensors on the group's poses as they are now, or with
+        world_frame=False in the camera's own axes.  One launch into a tensor the group keeps; no host sync."""
+        import torch
+        g = sim.camera_groups[camera_handle]
+        key = "points_w" if world_frame else "points_c"
+        if key not in g:
+            g[key] = torch.zeros(len(sim.envs), g["height"], g["width"], 3, dtype=torch.float32, device=sim.backend.device)
+        pose = g["pose"] if g["attach"] is None else self._attached_poses(sim, g).contiguous()
+        sim.renderer.camera_points(g["depth"], pose, g["camera"], g[key], world_frame)
+        return g[key]
+
+    # ---- ray-caster sensors (shifu_amd/raycast.py: arbitrary rays against the collision shapes and the terrain) -----------
+    def create_ray_caster_group(self, sim, pattern, position=(0.0, 0.0, 0.0), quat=(0.0, 0.0, 0.0, 1.0), attach_body=None,
+                                align="base", min_range=0.0, max_range=10.0, ignore_bodies=()):
+        """Not an Isaac Gym call: a ray-caster sensor in every env -- pattern = (origins (R, 3), dirs (R, 3)) in the sensor
+        frame, the sensor at (position, quat xyzw) in the frame of the state tensors or, with attach_body (a row of the
+        env's rigid-body states), in that body's frame.  AFTER prepare_sim, unlike cameras: it is built on the render
+        scene, which the sim builds on first use (a warped trimesh terrain: behind SHIFU_AMD_TRIMESH_CAMERAS=1, as for
+        cameras).  ignore_bodies: rigid-body rows the rays pass through.  Returns the group's handle; its tensors --
+        dist (N, R) f32, points (N, R, 3) f32 -- are sim.ray_caster_groups[handle]["dist" / "points"]."""
+        import torch
+        from ..raycast import ALIGN, check_pattern
+        from ..render import shape_mask_for
+        if sim.backend is None:
+            raise NotImplementedError("create_ray_caster_group: after prepare_sim (the render scene is built from the prepared sim)")
+        self._prepare_render_scene(sim)
+        o, d = check_pattern(*pattern)
+        if align not in ALIGN:
+            raise ValueError(f"create_ray_caster_group: align must be one of {sorted(ALIGN)}, got {align!r}")
+        if not (0.0 <= float(min_range) <= float(max_range) and np.isfinite(float(max_range))):
+            raise ValueError("create_ray_caster_group: need 0 <= min_range <= max_range, max_range finite")
+        dev, n, B = sim.backend.device, len(sim.envs), sim.cam_seg.shape[1]
+        q = np.asarray(tuple(quat), float)
+        local = torch.tensor(np.concatenate([np.asarray(tuple(position), float), q / np.linalg.norm(q)]), dtype=torch.float32)
+        g = dict(origins=torch.from_numpy(o).to(dev), dirs=torch.from_numpy(d).to(dev), num_rays=int(o.shape[0]), align=align,
+                 min_range=float(min_range), max_range=float(max_range), shape_mask=shape_mask_for(sim.renderer.scene, ignore_bodies),
+                 pose=local.repeat(n, 1).to(dev).contiguous(), attach=None,
+                 dist=torch.full((n, o.shape[0]), float("inf"), dtype=torch.float32, device=dev),
+                 points=torch.zeros(n, o.shape[0], 3, dtype=torch.float32, device=dev))
+        if attach_body is not None:
+            if not 0 <= int(attach_body) < B:
+                raise ValueError(f"create_ray_caster_group: attach_body {attach_body} outside the env's {B} rigid-body rows")
+            g["attach"] = (torch.arange(n, dtype=torch.long, device=dev) * B + int(attach_body), g["pose"][:, :3].contiguous(),
+                           g["pose"][:, 3:].contiguous())
+            g["pose"] = torch.zeros(n, 7, dtype=torch.float32, device=dev)
+        sim.ray_caster_groups.append(g)
+        return len(sim.ray_caster_groups) - 1
+
+    def cast_ray_caster_group(self, sim, handle):
+        """Not an Isaac Gym call: casts one ray-caster group (every env, one launch) on the state of the last simulate -- the
+        rigid-body states are refreshed first when they have not been since, as render_camera_group does -- into the
+        group's dist / points tensors, which it returns as a dict.  No host sync."""
+        if not sim.body_fresh:
+            self.refresh_rigid_body_state_tensor(sim)
+        g = sim.ray_caster_groups[handle]
+        if g["attach"] is not None:
+            g["pose"].copy_(self._attached_poses(sim, g))
+        sim.renderer.raycast(sim.backend.tensors[_abi.T_BODY_STATE], g["pose"], g["origins"], g["dirs"], g["align"],
+                             g["min_range"], g["max_range"], g["shape_mask"], dist=g["dist"], points=g["points"])
+        return dict(dist=g["dist"], points=g["points"])
 
     # ---- graphics: accepted and ignored by default (no window on this path).  SHIFU_AMD_VIEWER=<directory> opts into the
     # headless viewer (shifu_amd/viewer.py): create_viewer then returns a Viewer -- one camera over all envs, laid out on

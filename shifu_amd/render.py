@@ -16,6 +16,9 @@ owns the conventions the kernel mirrors (DESIGN.md "Camera sensors"):
     in pixels, u to the right, v downwards -- backward-looking.  Exactly +0.0 where nothing is hit, where the point was
     behind the previous camera, where the env's previous frame is marked invalid (FlowHistory) and where neither the
     body's pose nor the camera's changed bits.  flow_to_i16 / flow_from_i16: Isaac Gym's int16 encoding.
+  * ray caster (shf_raycast; Renderer.raycast, shifu_amd/raycast.py): arbitrary rays per env from a sensor pose; the ray
+    parameter is the Euclidean range, not the view depth; otherwise the cameras' hit and tie rules.  Renderer.camera_points
+    (shf_camera_points): the point o + |depth| d behind every pixel of a rendered depth image.
 """
 from __future__ import annotations
 
@@ -311,6 +314,87 @@ class Renderer:
                                          ptr(view_pose), n, e, ptr(env_ids), ptr(env_offset), C.c_float(float(env_radius)),
                                          ptr(body_state), ptr(seg), ptr(color), ptr(depth), ptr(seg_out), ptr(rgba),
                                          ptr(env_out), _stream_ptr(self.device)))
+
+    def raycast(self, body_state, sensor_pose, origins_dev, dirs_dev, align, min_range: float, max_range: float,
+                shape_mask: int, seg=None, dist=None, points=None, normal=None, seg_out=None, body=None):
+        """One launch of shf_raycast (shifu_amd/raycast.py): the pattern origins_dev / dirs_dev (R, 3) f32 on the device, the
+        same in every env, from sensor_pose (N, 7); body_state (N * num_bodies, 13) as for render().  align: _abi.RAY_ALIGN_*
+        or "base" | "yaw" | "world"; [min_range, max_range]: Euclidean ranges; shape_mask: bit k = shape k of the scene is
+        cast (shape_mask_for).  Writes, each optional but not all None: dist (N, R) f32 (+inf: a miss), points (N, R, 3) f32
+        world frame (a miss: the ray's end at max_range), normal (N, R, 3) f32, seg_out (N, R) int32 (needs seg, the (N,
+        num_bodies) int32 table) and body (N, R) int32 -- the hit body's row within the env, -1 terrain, -2 a miss."""
+        import torch
+        from ._lib import check, lib
+        from .backend import _stream_ptr
+        from .raycast import ALIGN
+        for name, t in (("body_state", body_state), ("sensor_pose", sensor_pose), ("origins_dev", origins_dev), ("dirs_dev", dirs_dev)):
+            if not isinstance(t, torch.Tensor) or t.dim() < 1:
+                raise ValueError(f"raycast: {name} must be a tensor")
+        n, R, B = int(sensor_pose.shape[0]), int(origins_dev.shape[0]), self.scene.num_bodies
+        if n < 1 or R < 1:
+            raise ValueError("raycast: no envs or no rays")
+        if isinstance(align, str):
+            if align not in ALIGN:
+                raise ValueError(f"raycast: align must be one of {sorted(ALIGN)}, got {align!r}")
+            align = ALIGN[align]
+        if int(align) not in ALIGN.values():
+            raise ValueError(f"raycast: align {align} outside 0..2")
+        lo, hi = float(min_range), float(max_range)
+        if not (0.0 <= lo <= hi and np.isfinite(hi)):
+            raise ValueError("raycast: need 0 <= min_range <= max_range, max_range finite")
+        if dist is None and points is None and normal is None and seg_out is None and body is None:
+            raise ValueError("raycast: no output tensor given")
+        if seg_out is not None and seg is None:
+            raise ValueError("raycast: seg_out needs the seg table")
+        for t, shape, dt in ((body_state, (n * B, 13), torch.float32), (sensor_pose, (n, 7), torch.float32),
+                             (origins_dev, (R, 3), torch.float32), (dirs_dev, (R, 3), torch.float32), (seg, (n, B), torch.int32),
+                             (dist, (n, R), torch.float32), (points, (n, R, 3), torch.float32),
+                             (normal, (n, R, 3), torch.float32), (seg_out, (n, R), torch.int32), (body, (n, R), torch.int32)):
+            if t is None:
+                continue
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"raycast: expected a contiguous {dt} tensor of shape {shape} on {self.device}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(self.device):
+            check(lib().shf_raycast(ptr(self._scene_dev), C.byref(self.terrain), ptr(self._heights), n, R, ptr(origins_dev),
+                                    ptr(dirs_dev), ptr(body_state), ptr(sensor_pose), int(align), C.c_float(lo), C.c_float(hi),
+                                    C.c_uint64(int(shape_mask) & 0xFFFFFFFFFFFFFFFF), ptr(seg), ptr(dist), ptr(points),
+                                    ptr(normal), ptr(seg_out), ptr(body), _stream_ptr(self.device)))
+
+    def camera_points(self, depth, cam_pose, camera: "_abi.ShfCamera", points, world_frame: bool = True):
+        """One launch of shf_camera_points: the point behind every pixel of a rendered depth image (N, H, W) -- either sign
+        convention; a pixel that shows nothing: the point at far_plane along its ray -- into points (N, H, W, 3) f32, in
+        world coordinates from cam_pose (N, 7), or with world_frame=False in the camera's axes (+x view axis, +y left, +z up)."""
+        import torch
+        from ._lib import check, lib
+        from .backend import _stream_ptr
+        if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+            raise ValueError("camera_points: depth must be an (N, H, W) tensor")
+        n, H, W = int(depth.shape[0]), camera.height, camera.width
+        if n < 1:
+            raise ValueError("camera_points: no envs")
+        for t, shape in ((depth, (n, H, W)), (cam_pose, (n, 7)), (points, (n, H, W, 3))):
+            if t is None or tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"camera_points: expected a contiguous float32 tensor of shape {shape} on {self.device}, got "
+                                 + ("None" if t is None else f"{tuple(t.shape)} {t.dtype} on {t.device}"))
+        with torch.cuda.device(self.device):
+            check(lib().shf_camera_points(C.byref(camera), n, C.c_void_p(depth.data_ptr()), C.c_void_p(cam_pose.data_ptr()),
+                                          int(bool(world_frame)), C.c_void_p(points.data_ptr()), _stream_ptr(self.device)))
+
+
+def shape_mask_for(scene: "_abi.ShfRenderScene", ignore_bodies=()) -> int:
+    """shf_raycast's 64-bit shape_mask of a scene: bit k set for every shape k whose body row is not in ignore_bodies (rows
+    within the env, 0 .. num_bodies - 1)."""
+    ignore = {int(b) for b in ignore_bodies}
+    bad = [b for b in ignore if not 0 <= b < int(scene.num_bodies)]
+    if bad:
+        raise ValueError(f"shape_mask_for: body rows {sorted(bad)} outside the scene's 0..{int(scene.num_bodies) - 1}")
+    mask = 0
+    for k in range(int(scene.nshapes)):
+        if int(scene.shape[k].body) not in ignore:
+            mask |= 1 << k
+    return mask
 
 
 # -- optical flow -------------------------------------------------------------------------------------------------------

@@ -13,7 +13,11 @@ flow = where a pixel's surface point is now minus where it was at this sensor's 
 encoding (DESIGN.md "Camera sensors"; no parity with Isaac Gym's own sign conventions is claimed).  optical_flow_buf is
 (N, H, W, 2) int16, u first -- the reference allocates (N, H, W) and its own comment doubts that shape (sensors.py:88-94);
 a flow image has two channels.  normalize_optical_flow(optical_flow, width, height) returns pixels.  reset_idx(env_ids)
-marks those envs' previous frame unusable: their next flow image is zero."""
+marks those envs' previous frame unusable: their next flow image is zero.
+
+CameraSensor.point_cloud() and RayCasterSensor have no counterpart in the reference (its to-do list, sensors.py:16-20, names
+point clouds): the world-frame point behind every pixel of the last depth image, and a sensor of arbitrary rays -- a height
+scanner, a lidar -- on the same ray caster (shifu_amd/raycast.py; DESIGN.md 8e "Ray caster")."""
 import enum
 
 import numpy as np
@@ -140,6 +144,13 @@ class CameraSensor(Sensor):
     def refresh(self):
         self.refresh_image_tensors()
 
+    def point_cloud(self, world_frame=True):
+        """(N, H, W, 3) f32: the point behind every pixel of the camera group's last rendered depth image, in the frame of
+        the state tensors (world_frame=False: in the camera's own axes, +x the view axis, +y left, +z up); a pixel that shows
+        nothing gives the point at far_plane along its ray.  One launch (shf_camera_points) into a tensor allocated on first
+        use; refresh() and the image buffers are as they were."""
+        return self.gym.camera_group_points(self.sim, self.camera_handle, world_frame)
+
     def refresh_image_tensors(self):
         im = self._images
         types = self.cfg.image_types
@@ -154,3 +165,55 @@ class CameraSensor(Sensor):
             self.segmentation_buf.copy_(im["seg"])
         if IMAGE_TYPE_OPTICAL_FLOW in types:
             self.optical_flow_buf.copy_(im["flow"])
+
+
+class RayCasterSensor(Sensor):
+    """A ray-caster sensor (configs.RayCasterSensorConfig): after refresh(), ray_distances (N, R) f32 holds every ray's range
+    (+inf: nothing within max_range) and ray_hits_w (N, R, 3) f32 its hit point in the frame of the state tensors (a miss:
+    the ray's end at max_range, finite).  The rays see the env's collision world -- the robot unless ignore_robot, the box
+    actors, the terrain with everything standing on it -- where get_heights samples the height-field lattice.  Nothing is
+    registered with the gym before prepare_sim: the sensor is built in init_buffers on the render scene the sim builds
+    lazily, and IsaacGymEnv.refresh_sensors casts it (one launch, no host sync)."""
+
+    def __init__(self, cfg):
+        super().__init__(cfg)
+        from shifu_amd.raycast import ALIGN, check_pattern
+        if cfg.pattern is None:
+            raise ValueError("RayCasterSensor: cfg.pattern must be (origins, dirs) -- see shifu_amd.raycast")
+        self.origins, self.dirs = check_pattern(*cfg.pattern)
+        self.num_rays = int(self.origins.shape[0])
+        if cfg.align not in ALIGN:
+            raise ValueError(f"RayCasterSensor: align must be one of {sorted(ALIGN)}, got {cfg.align!r}")
+        if (cfg.transform is None) == (cfg.attach_local_transform is None):
+            raise ValueError("RayCasterSensor: give exactly one of transform and attach_local_transform")
+        if cfg.attach_local_transform is not None and cfg.attach_body_name is None:
+            raise ValueError("RayCasterSensor: attach_local_transform needs attach_body_name")
+        self._handle = None
+
+    def _init_props(self):
+        pass
+
+    def load_to(self, env_id, env_handle, seg_id):
+        pass                                                 # nothing to create per env: one group for all envs, after prepare_sim
+
+    def reset_idx(self, env_ids):
+        pass
+
+    def init_buffers(self):
+        cfg, robot = self.cfg, self.env.robot
+        attach = None
+        pos, quat = cfg.transform if cfg.transform is not None else cfg.attach_local_transform
+        if cfg.attach_local_transform is not None:
+            bodies = robot.rigid_body_dict
+            if cfg.attach_body_name not in bodies:
+                raise ValueError(f"RayCasterSensor: the robot has no rigid body {cfg.attach_body_name!r} (it has {sorted(bodies)})")
+            attach = int(bodies[cfg.attach_body_name])
+        ignore = range(int(robot.num_bodies)) if cfg.ignore_robot else ()
+        self._handle = self.gym.create_ray_caster_group(self.sim, (self.origins, self.dirs), pos, quat, attach_body=attach,
+                                                        align=cfg.align, min_range=cfg.min_range, max_range=cfg.max_range,
+                                                        ignore_bodies=ignore)
+        self._group = self.sim.ray_caster_groups[self._handle]
+        self.ray_distances, self.ray_hits_w = self._group["dist"], self._group["points"]
+
+    def refresh(self):
+        self.gym.cast_ray_caster_group(self.sim, self._handle)

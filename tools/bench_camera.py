@@ -21,6 +21,15 @@ reports both medians and their ratio.
 without the env-level cull, against the batched per-env render followed by a torch min composite (bench_world).
 
     python tools/bench_camera.py --scene world --envs 4096
+
+--rays grid / lidar / pinhole (with --scene a1-heightfield, a1-trimesh or abb): the ray caster (shf_raycast) on FusedA1Env or
+FusedAbbEnv after a reset and a few random steps, timed in interleaved blocks (--repeats), median [min .. max] ms.  pinhole:
+the 64 x 48, fov 87 pinhole pattern writing `dist` only against shf_render_cameras writing depth only from the same poses --
+the same rays, so the ratio is what arbitrary rays cost.  grid: the A1 height scan (17 x 11 rays under the trunk, yaw-aligned,
+the robot ignored, max_range 3), beside shf_get_heights on the same envs and points.  lidar: 16 x 360 rays from the trunk /
+the end effector, the articulation ignored.
+
+    python tools/bench_camera.py --scene a1-trimesh --envs 4096 --rays grid
 """
 import argparse
 import json
@@ -147,6 +156,86 @@ def bench_a1(a):
     env.destroy()
 
 
+def bench_rays(a):
+    """--rays: see the module docstring.  One JSON line; every timed call is the launch alone (poses composed once)."""
+    import math
+    import statistics
+    import torch
+    from shifu_amd.raycast import grid_pattern, lidar_pattern, pinhole_pattern
+    a1 = a.scene.startswith("a1-")
+    if a1:
+        from shifu_amd.gym.a1_fused import FusedA1Env
+        env = FusedA1Env(num_envs=a.envs, terrain=a.scene[len("a1-"):])
+        actions, body = env.num_actions, 0
+        cam_kw = dict(position=(0.25, 0.0, 0.05), quat=(0.0, math.sin(0.25), 0.0, math.cos(0.25)), attach_body=0)
+    else:
+        from shifu_amd.gym.abb_fused import FusedAbbEnv
+        env = FusedAbbEnv(num_envs=a.envs, seed=0)
+        actions, body = 3, int(env.task_params.ee_body)
+        cam_kw = dict(position=(0.7, 0.0, 0.7), target=(0.0, 0.0, 0.1))
+    W, H, FOV, NEAR, FAR = 64, 48, 87.0, 0.05, 6.0
+    cam = env.add_camera(W, H, FOV, NEAR, FAR, **cam_kw)
+    if a.rays == "pinhole":
+        o, d = pinhole_pattern(W, H, FOV)
+        lim = float(FAR * (d.astype("float64") ** 2).sum(1).max() ** 0.5)          # every surface the camera shows is in range
+        rc = env.add_ray_caster((o, d), align="base", min_range=NEAR, max_range=lim, outputs=("dist",),
+                                **{k: v for k, v in cam_kw.items() if k != "target"},
+                                **({} if a1 else {"quat": cam.pose[0, 3:].cpu().numpy()}))
+    elif a.rays == "grid":
+        rc = env.add_ray_caster(grid_pattern(), position=(0.0, 0.0, 0.5) if a1 else (0.45, 0.0, 1.0), attach_body=0 if a1 else None,
+                                align="yaw", ignore_bodies="articulation", max_range=3.0, outputs=("dist", "points"))
+    else:
+        rc = env.add_ray_caster(lidar_pattern(16, (-15.0, 15.0), horizontal_res=1.0), position=(0.0, 0.0, 0.2 if a1 else 0.0),
+                                attach_body=body, align="base", ignore_bodies="articulation", min_range=0.05, max_range=10.0,
+                                outputs=("dist", "points"))
+    env.reset()
+    g = torch.Generator().manual_seed(0)
+    for _ in range(3):
+        env.step((2 * torch.rand(env.num_envs, actions, generator=g) - 1).to(env.device))
+    r, o_ = env._renderer, rc._out
+    pose = rc.world_pose().clone()
+    cast = lambda: r.raycast(env.body_state, pose, rc.origins, rc.dirs, rc.align, rc.min_range, rc.max_range, rc.shape_mask,
+                             dist=o_.get("dist"), points=o_.get("points"))
+    runs = {"raycast": cast}
+    if a.rays == "pinhole":
+        cpose, im = cam.world_pose().clone(), cam.raw_images()
+        runs["camera_depth_only"] = lambda: r.render(env.body_state, cpose, env.cam_seg, env.cam_color, cam.camera, depth=im["depth"])
+    if a.rays == "grid" and a1 and env.sim.terrain.rows > 0:
+        import copy
+        from shifu_amd import glue
+        t = copy.copy(env.sim.terrain)
+        nv = int(t.rows) * int(t.cols)
+        samples = env.sim._heights[:nv].view(int(t.rows), int(t.cols))
+        pts = rc.origins[:, :2].contiguous()
+        runs["get_heights"] = lambda: glue.get_heights(t, samples, env.root_state, None, pts, env.num_envs)
+    ms = {k: [] for k in runs}
+    for _ in range(a.repeats):
+        for k, fn in runs.items():
+            ms[k].append(time_renders(fn, a.warmup, a.renders))
+    cast()
+    torch.cuda.synchronize()
+    dist = o_["dist"]
+    n_rays = env.num_envs * rc.num_rays
+    out = dict(bench="raycast", rays=a.rays, scene=a.scene if a1 else "abb_pushbox", envs=a.envs, rays_per_env=rc.num_rays,
+               outputs=sorted(o_), renders=a.renders, repeats=a.repeats, warped=int(env.sim.terrain.warped),
+               shapes=int(r.scene.nshapes), shapes_cast=bin(rc.shape_mask).count("1"),
+               rays_hit=round(float(torch.isfinite(dist).float().mean()), 4), device=torch.cuda.get_device_name(0))
+    for k, xs in ms.items():
+        out["ms_" + k] = dict(median=round(statistics.median(xs), 4), min=round(min(xs), 4), max=round(max(xs), 4),
+                              runs=[round(x, 4) for x in xs])
+    med = statistics.median(ms["raycast"])
+    out["rays_per_s"] = round(n_rays / (med * 1e-3), 1)
+    if "camera_depth_only" in ms:
+        out["raycast_over_camera"] = round(med / statistics.median(ms["camera_depth_only"]), 4)
+        both = torch.isfinite(im["depth"].view(env.num_envs, -1)) & torch.isfinite(dist)
+        norm = rc.dirs.norm(dim=1)[None, :]
+        # (the camera writes minus the view depth; a ray on a silhouette may fall on either side of it: a fraction, not a maximum)
+        diff = ((dist / norm) + im["depth"].view(env.num_envs, -1))[both].abs()
+        out["rays_differing_over_1mm"] = round(float((diff > 1e-3).float().mean()), 6)
+    print(json.dumps(out))
+    env.destroy()
+
+
 def bench_world(a):
     """--scene world: the headless viewer's launch (shf_render_world) alone, 640 x 360, on FusedA1Env's height field with
     --envs robots, from a camera behind env 0 that looks over its neighbours -- with the env-level cull (env_radius from
@@ -214,8 +303,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--scene", choices=["abb", "a1-heightfield", "a1-trimesh", "world"], default="abb")
     ap.add_argument("--flow", action="store_true", help="also time the launch with optical flow, alternating with the one without")
-    ap.add_argument("--repeats", type=int, default=3, help="--flow: timed runs of each form")
+    ap.add_argument("--repeats", type=int, default=3, help="--flow / --rays / --scene world: timed runs of each form")
+    ap.add_argument("--rays", choices=["grid", "lidar", "pinhole"], default=None,
+                    help="time the ray caster with this pattern (scenes a1-heightfield, a1-trimesh, abb)")
     a = ap.parse_args()
+    if a.rays is not None:
+        if a.scene == "world":
+            ap.error("--rays needs --scene a1-heightfield, a1-trimesh or abb")
+        return bench_rays(a)
     if a.scene == "world":
         return bench_world(a)
     if a.scene != "abb":

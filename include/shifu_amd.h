@@ -461,6 +461,16 @@ int shf_sim_step_plan(const ShfSim* sim, ShfLaunchPlan* plan);
 /* gym.refresh_{dof_state,actor_root_state,rigid_body_state,jacobian,
  * net_contact_force}_tensor(s) (isaac_gym.py:145-154, a1_conditional.py:72) */
 int shf_sim_refresh(ShfSim* sim, int32_t mask, void* stream);
+/* gym.acquire_mass_matrix_tensor / refresh_mass_matrix_tensors for a fixed-base articulation, one launch (csrc/shf_dyn.hip):
+ * mass_matrix (N, nd, nd) = the composite-rigid-body matrix M(q) + ShfModel.armature on the diagonal, both triangles,
+ * exactly symmetric, exact zeros between dofs on different branches; bias (N, nd) = h(q, qd), the gravity, Coriolis and
+ * centrifugal forces (recursive Newton-Euler with qdd = 0, base acceleration -gravity * gravity_on), so that
+ * M qdd + h = tau is what shf_sim_step integrates in effort mode inside the joint limits, without contact and with zero joint
+ * damping.  Joint damping, the drive gains and the joint-limit penalty are NOT part of either.  Computed from the solver's
+ * state (SHF_T_SIM_DOF, SHF_T_SIM_ROOT: what shf_sim_refresh reads), with the factors of SHF_T_BODY_MASS_SCALE when bound.
+ * Either output may be null, not both.  Refused (shf_last_error): a null or unfinalised sim, a floating base, both outputs
+ * null.  An additive entry: no new SHF_ABI_VERSION, no struct layout changed. */
+int shf_sim_dynamics(ShfSim* sim, float* mass_matrix_or_null, float* bias_or_null, void* stream);
 /* gym.set_dof_actuation_force_tensor / set_dof_position_target_tensor /
  * set_dof_velocity_target_tensor (robot.py:55-64): copies (N*nd) floats. */
 int shf_sim_set_dof_command(ShfSim* sim, int32_t tensor_id, const float* values_dev, void* stream);
@@ -892,6 +902,20 @@ int shf_reset_dof_rows(float* dof_state, float* dof_targets, const float* defaul
 int shf_ik_dls(const float* j_ee, int64_t j_env_stride, const float* dof_pos, int32_t dof_elem_stride, const float* ee_pose,
                int64_t ee_env_stride, const float* goal_pose, int32_t n, int32_t num_dof, float damping,
                float* dof_targets_out, void* stream);
+/* ArmRobot.operational_space_control: the torque-level controller of Isaac Gym's arm examples, one launch, one thread per env.
+ *   e = [goal_pos - ee_pos; orientation_error(goal_quat, ee_quat)] (as shf_ik_dls),  a = kp6 (.) e - kd6 (.) J qd,
+ *   X = M^-1 J^T (LDL^T of M),  A = (J X + (J X)^T) / 2 + damping^2 I,  tau = J^T A^-1 a (LDL^T, as shf_ik_dls);
+ * with q_rest given and num_dof > 6 the null-space posture term M u - J^T A^-1 J u,
+ *   u = kp_null wrap_to_pi(q_rest - q) - kd_null qd,
+ * is added; then bias (shf_sim_dynamics' h: gravity compensation) when given; the clamp to +-effort_limit[d] comes last
+ * (entries <= 0: no limit).  Views as for shf_ik_dls: J = the (6, num_dof) block at j_ee + e * j_env_stride, the ee_pose row
+ * at ee_pose + e * ee_env_stride; dof (e, d) has its position at dof_state[(e * num_dof + d) * dof_elem_stride] and its
+ * velocity one float later (2 for dof_state itself).  mass_matrix (n, nd, nd), bias (n, nd), goal_pose (n, 7), kp6 / kd6 (6),
+ * q_rest / effort_limit (nd): contiguous device tensors.  Any num_dof <= SHF_MAX_DOFS.  Additive: no new SHF_ABI_VERSION. */
+int shf_osc(const float* j_ee, int64_t j_env_stride, const float* mass_matrix, const float* bias_or_null, const float* dof_state,
+            int32_t dof_elem_stride, const float* ee_pose, int64_t ee_env_stride, const float* goal_pose, const float* kp6,
+            const float* kd6, float damping, const float* q_rest_or_null, float kp_null, float kd_null,
+            const float* effort_limit_or_null, int32_t n, int32_t num_dof, float* efforts_out, void* stream);
 /* ShifuVecEnv.compute_reward's accumulation (env.py:180-185): rew = terms[0] + terms[1] + ... in that order,
  * sums[k] += terms[k]; HOST arrays of num_keys <= 16 device pointers to (num_envs) fp32 tensors. */
 int shf_reward_accumulate(const float* const* terms, float* const* sums, int32_t num_keys, int64_t num_envs, float* rew,

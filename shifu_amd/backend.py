@@ -353,6 +353,18 @@ class Sim:
         with torch.cuda.device(self.device):
             check(f_refresh(self._h, mask, _stream_ptr(self.device)))
 
+    @_on_device
+    def dynamics(self, mass_matrix: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
+        """Fills mass_matrix (num_envs, nd, nd) and / or bias (num_envs, nd) from the solver's state in one launch
+        (shf_sim_dynamics: M(q) with armature, h(q, qd) = gravity + Coriolis + centrifugal forces; fixed base only)."""
+        if self._held is not None or self._defer:
+            self._flush_held()
+        n, nd = self.num_envs, self.model.nd if self.model is not None else 0
+        for t, shape in ((mass_matrix, (n, nd, nd)), (bias, (n, nd))):
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and tuple(t.shape) == shape)
+        check(lib().shf_sim_dynamics(self._h, C.c_void_p(mass_matrix.data_ptr()) if mass_matrix is not None else None,
+                                     C.c_void_p(bias.data_ptr()) if bias is not None else None, _stream_ptr(self.device)))
+
     def set_dof_command(self, tid: int, values: torch.Tensor):
         v = values if values.is_contiguous() else values.contiguous()
         assert v.dtype == torch.float32 and v.numel() == self.num_envs * self.model.nd

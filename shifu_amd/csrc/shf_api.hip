@@ -21,6 +21,7 @@
 #include "shf_device.h"
 #include "shf_task.h"
 #include "shf_arm.h"
+#include "shf_dyn.h"
 
 // ------------------------------------------------------------ host state --
 static thread_local std::string g_err;
@@ -589,6 +590,26 @@ extern "C" int shf_sim_refresh(ShfSim* sim, int32_t mask, void* stream) {
     }
   }
   return 0;
+}
+
+// gym.refresh_mass_matrix_tensors: M(q) and the bias forces h(q, qd) from the solver's state (csrc/shf_dyn.h, k_sim_dynamics)
+extern "C" int shf_sim_dynamics(ShfSim* sim, float* mass_matrix_or_null, float* bias_or_null, void* stream) {
+  if (!sim) return fail("shf_sim_dynamics: null sim");
+  if (!sim->finalized) return fail("shf_sim_dynamics: sim not finalized");
+  if (!sim->model.fixed_base) return fail("shf_sim_dynamics: fixed base only (as the Jacobian tensor's dof columns)");
+  if (!mass_matrix_or_null && !bias_or_null) return fail("shf_sim_dynamics: both outputs are null");
+  if (int r = need(sim, {SHF_T_SIM_DOF, SHF_T_SIM_ROOT, SHF_T_MODEL}, "shf_sim_dynamics")) return r;
+  if (sim->model.nd == 0) return 0;
+  ShfDynArgs A;
+  A.model = (const ShfModel*)sim->t[SHF_T_MODEL];
+  A.n = sim->n; A.actors = 1 + sim->nboxes;
+  A.dof = (const float*)sim->t[SHF_T_SIM_DOF];
+  A.root = (const float*)sim->t[SHF_T_SIM_ROOT];
+  A.mscale = (const float*)sim->t[SHF_T_BODY_MASS_SCALE];
+  for (int k = 0; k < 3; k++) A.gravity[k] = sim->sp.gravity[k];
+  A.mass = mass_matrix_or_null; A.bias = bias_or_null;
+  const int epb = 256 / sim->group;
+  return launch_ptr(shf_dyn_kernel(sim->group), dim3((sim->n + epb - 1) / epb), dim3(256), shf_dyn_lds_bytes(sim->model, sim->group), stream, A);
 }
 
 extern "C" int shf_sim_set_dof_command(ShfSim* sim, int32_t tensor_id, const float* values_dev, void* stream) {

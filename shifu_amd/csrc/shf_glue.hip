@@ -283,6 +283,154 @@ extern "C" int shf_ik_dls(const float* j_ee, int64_t j_env_stride, const float* 
   return GLUE_LAUNCH_OK("shf_ik_dls");
 }
 
+// K11 -- ArmRobot.operational_space_control: the torque-level controller of Isaac Gym's arm examples,
+//   tau = J^T A^-1 (kp (.) e - kd (.) J qd),  A = J M^-1 J^T + damping^2 I,
+// plus, with q_rest and nd > 6, the posture term M u - J^T A^-1 J u (u = kp_null wrap_to_pi(q_rest - q) - kd_null qd), which
+// shares the one 6x6 solve: tau = J^T A^-1 (a - J u) + M u.  Then + bias, then the effort clamp.
+// One thread per env, as k_ik_dls.  M^-1 J^T by LDL^T of M (any nd <= SHF_MAX_DOFS): the factor, X = M^-1 J^T, J and u live in
+// LDS, word k of thread t at [k * T + t] (a thread touches its own words only: no barrier, no bank conflict); the 6x6 system in
+// registers by the packed LDL^T of k_ik_dls.  The host sizes the block (T <= 64 threads) so that the LDS stays within 48 KiB.
+struct OscArgs {
+  const float* j_ee; long long j_stride;
+  const float* mass; const float* bias;
+  const float* dof; int dof_stride;
+  const float* ee; long long ee_stride;
+  const float* goal; const float* kp6; const float* kd6;
+  float lam2;
+  const float* q_rest; float kp_null, kd_null;
+  const float* limit;
+  int n, nd;
+  float* out;
+};
+static int osc_words(int nd) { return nd * (nd + 1) / 2 + nd + 6 * nd + nd + 6 * nd; }
+__global__ void k_osc(OscArgs A) {
+  extern __shared__ float osc_lds[];
+  const int T = blockDim.x, t = threadIdx.x, nd = A.nd;
+  const int e = blockIdx.x * T + t;
+  if (e >= A.n) return;
+  float* Lw = osc_lds + t;                       // LDL^T of M: L below the diagonal, D on it, row-packed lower triangle
+  float* iD = Lw + (nd * (nd + 1) / 2) * T;      // 1 / D
+  float* Xw = iD + nd * T;                       // X[d][c]
+  float* Uw = Xw + 6 * nd * T;                   // u[d]
+  float* Jw = Uw + nd * T;                       // J[k][d]
+#define OSC_L(i, j) Lw[((i) * ((i) + 1) / 2 + (j)) * T]
+#define OSC_X(d, c) Xw[((d) * 6 + (c)) * T]
+#define OSC_J(k, d) Jw[((k) * nd + (d)) * T]
+  const float* J = A.j_ee + (long long)e * A.j_stride;
+  const float* Mg = A.mass + (long long)e * nd * nd;
+  const float* ds = A.dof + (long long)e * nd * A.dof_stride;
+  const float* ee = A.ee + (long long)e * A.ee_stride;
+  const float* gp = A.goal + (long long)e * 7;
+  for (int k = 0; k < 6 * nd; k++) Jw[k * T] = J[k];
+  float a[6], cc[4], qr[4];
+#pragma unroll
+  for (int k = 0; k < 3; k++) a[k] = gp[k] - ee[k];
+  cc[0] = -ee[3]; cc[1] = -ee[4]; cc[2] = -ee[5]; cc[3] = ee[6];
+  const float tq[4] = {gp[3], gp[4], gp[5], gp[6]};
+  glue_quat_mul(tq, cc, qr);
+  const float sg = qr[3] > 0.0f ? 1.0f : (qr[3] < 0.0f ? -1.0f : 0.0f);
+#pragma unroll
+  for (int k = 0; k < 3; k++) a[3 + k] = qr[k] * sg;
+  // a = kp (.) e - kd (.) J qd  [- J u]
+  const bool posture = A.q_rest && nd > 6;
+  float xd[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, ju[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  for (int d = 0; d < nd; d++) {
+    const float q = ds[d * A.dof_stride], qd = ds[d * A.dof_stride + 1];
+    float u = 0.0f;
+    if (posture) {
+      float x = A.q_rest[d] - q;
+      x = fmaf(-6.283185307179586f, rintf(x * 0.15915494309189535f), x);   // wrap_to_pi
+      u = A.kp_null * x - A.kd_null * qd;
+      Uw[d * T] = u;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; k++) { xd[k] = fmaf(OSC_J(k, d), qd, xd[k]); ju[k] = fmaf(OSC_J(k, d), u, ju[k]); }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; k++) a[k] = A.kp6[k] * a[k] - A.kd6[k] * xd[k] - ju[k];
+  // M = L D L^T
+  for (int j = 0; j < nd; j++) {
+    float dj = Mg[j * nd + j];
+    for (int k = 0; k < j; k++) { const float v = OSC_L(j, k); dj = fmaf(-(v * v), OSC_L(k, k), dj); }
+    OSC_L(j, j) = dj;
+    const float id = glue_rcp_spec(dj);
+    iD[j * T] = id;
+    for (int i = j + 1; i < nd; i++) {
+      float v = Mg[i * nd + j];
+      for (int k = 0; k < j; k++) v = fmaf(-(OSC_L(i, k) * OSC_L(j, k)), OSC_L(k, k), v);
+      OSC_L(i, j) = v * id;
+    }
+  }
+  // X = M^-1 J^T, column by column
+  for (int c = 0; c < 6; c++) {
+    for (int i = 0; i < nd; i++) {
+      float v = OSC_J(c, i);
+      for (int k = 0; k < i; k++) v = fmaf(-OSC_L(i, k), OSC_X(k, c), v);
+      OSC_X(i, c) = v;
+    }
+    for (int i = 0; i < nd; i++) OSC_X(i, c) = OSC_X(i, c) * iD[i * T];
+    for (int i = nd - 1; i >= 0; i--) {
+      float v = OSC_X(i, c);
+      for (int k = i + 1; k < nd; k++) v = fmaf(-OSC_L(k, i), OSC_X(k, c), v);
+      OSC_X(i, c) = v;
+    }
+  }
+  // A = (J X + (J X)^T) / 2 + damping^2 I, packed
+  float Am[21], neg[6], F[6];
+#pragma unroll
+  for (int k = 0; k < 21; k++) Am[k] = 0.0f;
+  for (int d = 0; d < nd; d++) {
+    float Jd[6], Xd[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) { Jd[k] = OSC_J(k, d); Xd[k] = OSC_X(d, k); }
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+      for (int j = i; j < 6; j++) Am[GSYM(i, j)] = fmaf(Jd[j], Xd[i], fmaf(Jd[i], Xd[j], Am[GSYM(i, j)]));
+  }
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+#pragma unroll
+    for (int j = i; j < 6; j++) Am[GSYM(i, j)] = (i == j) ? fmaf(0.5f, Am[GSYM(i, j)], A.lam2) : 0.5f * Am[GSYM(i, j)];
+#pragma unroll
+  for (int k = 0; k < 6; k++) neg[k] = -a[k];
+  glue_ldlt_solve6(Am, neg, F);
+  for (int d = 0; d < nd; d++) {
+    float tau = OSC_J(0, d) * F[0];
+#pragma unroll
+    for (int k = 1; k < 6; k++) tau = fmaf(OSC_J(k, d), F[k], tau);
+    if (posture) {
+      float mu = Mg[d * nd] * Uw[0];
+      for (int j = 1; j < nd; j++) mu = fmaf(Mg[d * nd + j], Uw[j * T], mu);
+      tau += mu;
+    }
+    if (A.bias) tau += A.bias[(long long)e * nd + d];
+    const float lim = A.limit ? A.limit[d] : 0.0f;
+    if (lim > 0.0f) tau = tau > lim ? lim : (tau < -lim ? -lim : tau);
+    A.out[(long long)e * nd + d] = tau;
+  }
+#undef OSC_L
+#undef OSC_X
+#undef OSC_J
+}
+
+extern "C" int shf_osc(const float* j_ee, int64_t j_env_stride, const float* mass_matrix, const float* bias_or_null,
+                       const float* dof_state, int32_t dof_elem_stride, const float* ee_pose, int64_t ee_env_stride,
+                       const float* goal_pose, const float* kp6, const float* kd6, float damping, const float* q_rest_or_null,
+                       float kp_null, float kd_null, const float* effort_limit_or_null, int32_t n, int32_t num_dof,
+                       float* efforts_out, void* stream) {
+  if (!j_ee || !mass_matrix || !dof_state || !ee_pose || !goal_pose || !kp6 || !kd6 || !efforts_out) return shf_set_error("shf_osc: null tensor");
+  if (n <= 0 || num_dof <= 0) return 0;
+  if (num_dof > SHF_MAX_DOFS) return shf_set_error("shf_osc: too many dofs");
+  if (dof_elem_stride < 2) return shf_set_error("shf_osc: dof_state holds position and velocity (element stride >= 2)");
+  int T = 64;
+  while ((size_t)T * osc_words(num_dof) * 4 > 48 * 1024) T >>= 1;
+  OscArgs A = {j_ee, (long long)j_env_stride, mass_matrix, bias_or_null, dof_state, (int)dof_elem_stride, ee_pose, (long long)ee_env_stride,
+               goal_pose, kp6, kd6, damping * damping, q_rest_or_null, kp_null, kd_null, effort_limit_or_null, (int)n, (int)num_dof, efforts_out};
+  hipLaunchKernelGGL(k_osc, dim3((n + T - 1) / T), dim3(T), (size_t)T * osc_words(num_dof) * 4, (hipStream_t)stream, A);
+  return GLUE_LAUNCH_OK("shf_osc");
+}
+
 extern "C" int shf_base_frame_state(const float* root_state, const int64_t* root_idx_or_null, int64_t num_root_rows, int32_t n,
                                     int32_t up_axis, float* base_lin_vel, float* base_ang_vel, float* projected_gravity,
                                     float* gravity_vec, void* stream) {

@@ -139,3 +139,29 @@ def ik_dls(j_ee, dof_pos, ee_pose, goal_pose, damping):
                                _vp(ee_pose.data_ptr()), ee_pose.stride(0), _f32c(goal), n, nd, float(damping), _f32c(out),
                                _stream(j_ee.device)))
     return out
+
+
+def osc(j_ee, mass_matrix, bias, dof_state, ee_pose, goal_pose, kp6, kd6, damping=0.0, q_rest=None, kp_null=0.0, kd_null=0.0,
+        effort_limit=None):
+    """ArmRobot.operational_space_control in one launch (shf_osc): efforts (n, nd).  j_ee (n, 6, nd) and ee_pose (n, 7) may be
+    strided views as for ik_dls; dof_state (n, nd, >= 2) holds position and velocity in its last axis (the dof-state tensor
+    itself, or any view with unit stride there and rows packed per env).  mass_matrix (n, nd, nd), bias (n, nd) or None,
+    kp6 / kd6 (6), q_rest / effort_limit (nd) or None."""
+    n, six, nd = j_ee.shape
+    assert six == 6 and j_ee.stride(2) == 1 and j_ee.stride(1) == nd and ee_pose.stride(1) == 1
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in (j_ee, ee_pose, dof_state)), "float32 CUDA tensors expected"
+    assert dof_state.shape[:2] == (n, nd) and dof_state.shape[2] >= 2 and dof_state.stride(2) == 1
+    assert dof_state.stride(1) >= 2 and dof_state.stride(0) == nd * dof_state.stride(1)
+    assert mass_matrix.shape == (n, nd, nd) and (bias is None or bias.shape == (n, nd))
+    assert kp6.numel() == 6 and kd6.numel() == 6
+    assert q_rest is None or q_rest.numel() == nd
+    assert effort_limit is None or effort_limit.numel() == nd
+    goal = goal_pose.contiguous()
+    out = torch.empty(n, nd, device=j_ee.device, dtype=torch.float32)
+    with torch.cuda.device(j_ee.device):
+        check(lib().shf_osc(_vp(j_ee.data_ptr()), j_ee.stride(0), _f32c(mass_matrix), None if bias is None else _f32c(bias),
+                            _vp(dof_state.data_ptr()), dof_state.stride(1), _vp(ee_pose.data_ptr()), ee_pose.stride(0), _f32c(goal),
+                            _f32c(kp6), _f32c(kd6), float(damping), None if q_rest is None else _f32c(q_rest), float(kp_null),
+                            float(kd_null), None if effort_limit is None else _f32c(effort_limit), n, nd, _f32c(out),
+                            _stream(j_ee.device)))
+    return out

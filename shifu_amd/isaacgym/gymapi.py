@@ -250,6 +250,8 @@ class SimHandle:
         self.actors_per_env = 0
         self.num_actors = 0
         self.jacobian = None
+        self.mass_matrix = None               # acquire_mass_matrix_tensor / acquire_dof_bias_force_tensor: allocated on first
+        self.dof_bias = None                  # acquire, filled by refresh_mass_matrix_tensors
         self.camera_groups: List[dict] = []   # after prepare_sim: one per camera handle (one camera per env each)
         self.ray_caster_groups: List[dict] = []   # create_ray_caster_group: one ray-caster sensor per env each
         self.renderer = None
@@ -586,7 +588,32 @@ class Gym:
         call (shifu's refresh_state issues the six refresh_* calls back to back, shifu/gym/isaac_gym.py:145-154)."""
         sim.backend.refresh(_abi.REFRESH_ALL)
         sim.body_fresh = True
-    def refresh_mass_matrix_tensors(self, sim): pass
+
+    def _acquire_dynamics(self, sim, attr, shape):
+        import torch
+        be = sim.backend
+        if not be.model.fixed_base:
+            raise NotImplementedError("mass-matrix and bias-force tensors: fixed base only (as the Jacobian tensor's dof columns)")
+        if getattr(sim, attr) is None:        # allocated once per sim
+            setattr(sim, attr, torch.zeros(shape, dtype=torch.float32, device=be.device))
+        return _TensorHandle(getattr(sim, attr))
+
+    def acquire_mass_matrix_tensor(self, sim, name):
+        """(num_envs, nd, nd): M(q) of the articulation, armature on the diagonal (csrc/shf_dyn.h); filled by
+        refresh_mass_matrix_tensors."""
+        nd = sim.backend.model.nd
+        return self._acquire_dynamics(sim, "mass_matrix", (sim.backend.num_envs, nd, nd))
+
+    def acquire_dof_bias_force_tensor(self, sim, name):
+        """Not an Isaac Gym call: (num_envs, nd) gravity + Coriolis + centrifugal joint forces h(q, qd), so that
+        M qdd + h = tau in effort mode (gravity compensation = applying h); filled by refresh_mass_matrix_tensors."""
+        return self._acquire_dynamics(sim, "dof_bias", (sim.backend.num_envs, sim.backend.model.nd))
+
+    def refresh_mass_matrix_tensors(self, sim):
+        """Fills whichever of the mass-matrix / bias-force tensors was acquired, in one launch; nothing to do otherwise."""
+        if sim.mass_matrix is None and sim.dof_bias is None:
+            return
+        sim.backend.dynamics(sim.mass_matrix, sim.dof_bias)
 
     # ---- stepping --------------------------------------------------------------
     def simulate(self, sim):

@@ -154,6 +154,69 @@ class ArmRobot(Robot):
         u = (jt @ torch.inverse(self.j_ee @ jt + lam) @ dpose).view(self.env.num_envs, self.num_dof)
         return self.dof_pos + u
 
+    # -- torque-level control (not in the reference: the controller of Isaac Gym's own arm examples) ---------------------
+    @property
+    def mass_matrix(self):
+        """(num_envs, nd, nd) joint-space mass matrix; gym.refresh_mass_matrix_tensors fills it."""
+        if getattr(self, "_mass_matrix", None) is None:
+            self._mass_matrix = gymtorch.wrap_tensor(self.gym.acquire_mass_matrix_tensor(self.sim, self.name))
+        return self._mass_matrix
+
+    @property
+    def bias_forces(self):
+        """(num_envs, nd) gravity + Coriolis + centrifugal joint forces; gym.refresh_mass_matrix_tensors fills it."""
+        if getattr(self, "_bias_forces", None) is None:
+            self._bias_forces = gymtorch.wrap_tensor(self.gym.acquire_dof_bias_force_tensor(self.sim, self.name))
+        return self._bias_forces
+
+    def _gain6(self, g):
+        g = torch.as_tensor(g, dtype=torch.float32, device=self.device)
+        return (g.expand(6) if g.dim() == 0 else g.reshape(6)).contiguous()
+
+    def operational_space_control(self, goal_pose, kp=150., kd=None, damping=0., gravity_compensation=True, q_rest=None,
+                                  kp_null=10., kd_null=None):
+        """Efforts (num_envs, nd) that drive the end effector to goal_pose (n, 7): u = J^T Lambda (kp e - kd xdot),
+        Lambda = (J M^-1 J^T + damping^2 I)^-1, from the Jacobian, mass-matrix, dof and body tensors as last refreshed.
+        kp / kd: scalars or 6-vectors; kd None = critical damping 2 sqrt(kp).  gravity_compensation adds bias_forces.
+        q_rest (nd), for arms with more than 6 dofs: a posture task in the null space of the end effector (kd_null None =
+        2 sqrt(kp_null)).  Clamped to the asset's effort limits."""
+        kp6 = self._gain6(kp)
+        kd6 = 2.0 * torch.sqrt(kp6) if kd is None else self._gain6(kd)
+        if kd_null is None:
+            kd_null = 2.0 * float(kp_null) ** 0.5
+        bias = self.bias_forces if gravity_compensation else None
+        M = self.mass_matrix
+        if q_rest is not None:
+            q_rest = torch.as_tensor(q_rest, dtype=torch.float32, device=self.device).reshape(self.num_dof).contiguous()
+        n = self.env.num_envs
+        if self.j_ee.is_cuda and self.j_ee.dim() == 3 and self.j_ee.dtype == torch.float32 and goal_pose.is_cuda \
+                and hasattr(self, "_ee0"):
+            # the expressions of utils.torch_utils.operational_space_control as one launch (csrc/shf_glue.hip: shf_osc)
+            from shifu_amd import glue
+            ee = self.env.body_state.view(n, -1, 13)[:, self._ee0, :7]
+            return glue.osc(self.j_ee, M, bias, self.env.dof_state.view(n, self.num_dof, 2), ee, goal_pose, kp6, kd6, damping,
+                            q_rest, kp_null, kd_null, self.torque_limits.contiguous())
+        from shifu_amd.utils.torch_utils import operational_space_control
+        ee_pos, ee_quat = self.ee_pose[:, 0, :3], self.ee_pose[:, 0, 3:7]
+        return operational_space_control(self.j_ee, M, self.dof_pos, self.dof_vel, ee_pos, ee_quat, goal_pose[:, :3],
+                                         goal_pose[:, 3:7], kp6, kd6, damping, bias, q_rest, kp_null, kd_null, self.torque_limits)
+
+    def apply_target_end_positions_osc(self, tar_pose, **gains):
+        """decimation x {refresh dof / body / Jacobian / mass matrix / bias, compute efforts, set them, simulate, refresh the
+        dof state}: apply_target_end_positions at torque level.  The asset must be in DOF_MODE_EFFORT."""
+        if self.asset_options.default_dof_drive_mode != gymapi.DOF_MODE_EFFORT:
+            raise RuntimeError("apply_target_end_positions_osc: the asset's default_dof_drive_mode must be DOF_MODE_EFFORT")
+        self.mass_matrix, self.bias_forces      # acquired before the first refresh
+        for _ in range(int(self.env.decimation)):
+            self.gym.refresh_all_state_tensors(self.sim)      # dof, body and Jacobian tensors among them, one backend call
+            self.gym.refresh_mass_matrix_tensors(self.sim)
+            efforts = self.operational_space_control(tar_pose, **gains)
+            self.gym.set_dof_actuation_force_tensor(self.sim, gymtorch.unwrap_tensor(efforts))
+            self.gym.simulate(self.sim)
+            if self.device == 'cpu':
+                self.gym.fetch_results(self.sim, True)
+            self.gym.refresh_dof_state_tensor(self.sim)
+
 
 class LeggedRobot(ArmRobot):
     def __init__(self, cfg):

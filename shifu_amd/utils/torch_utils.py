@@ -25,3 +25,32 @@ def inverse_kinematics(dof_pos, ee_pos, ee_quat, tar_pos, tar_quat, j_ee, device
     lam = torch.eye(6, device=device) * (damping ** 2)
     u = (jt @ torch.inverse(j_ee @ jt + lam) @ dpose).view(dof_pos.shape[0], dof_pos.shape[1])
     return dof_pos + u
+
+
+def wrap_to_pi(x):
+    return x - 2.0 * torch.pi * torch.round(x / (2.0 * torch.pi))
+
+
+def operational_space_control(j_ee, mass_matrix, dof_pos, dof_vel, ee_pos, ee_quat, tar_pos, tar_quat, kp6, kd6, damping=0.0,
+                              bias=None, q_rest=None, kp_null=0.0, kd_null=0.0, effort_limit=None):
+    """Operational-space (torque) control, the controller of Isaac Gym's arm examples: tau = J^T A^-1 (kp e - kd J qd) with
+    A = J M^-1 J^T + damping^2 I (symmetrised); with q_rest and more than 6 dofs the null-space posture term
+    M u - J^T A^-1 J u, u = kp_null wrap_to_pi(q_rest - q) - kd_null qd; then + bias, then the clamp to +-effort_limit
+    (entries <= 0: no limit).  The torch expressions of csrc/shf_glue.hip's shf_osc (which solves by LDL^T)."""
+    n, nd = dof_pos.shape
+    e = torch.cat([tar_pos - ee_pos, orientation_error(tar_quat, ee_quat)], -1)
+    a = kp6 * e - kd6 * (j_ee @ dof_vel.unsqueeze(-1)).squeeze(-1)
+    jt = torch.transpose(j_ee, 1, 2)
+    x = torch.linalg.solve(mass_matrix, jt)
+    A = j_ee @ x
+    A = 0.5 * (A + torch.transpose(A, 1, 2)) + torch.eye(6, device=j_ee.device, dtype=j_ee.dtype) * (damping ** 2)
+    tau = (jt @ torch.linalg.solve(A, a.unsqueeze(-1))).squeeze(-1)
+    if q_rest is not None and nd > 6:
+        u = (kp_null * wrap_to_pi(q_rest - dof_pos) - kd_null * dof_vel).unsqueeze(-1)
+        tau = tau + (mass_matrix @ u - jt @ torch.linalg.solve(A, j_ee @ u)).squeeze(-1)
+    if bias is not None:
+        tau = tau + bias
+    if effort_limit is not None:
+        lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
+        tau = torch.maximum(torch.minimum(tau, lim), -lim)
+    return tau

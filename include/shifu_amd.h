@@ -471,6 +471,24 @@ int shf_sim_refresh(ShfSim* sim, int32_t mask, void* stream);
  * Either output may be null, not both.  Refused (shf_last_error): a null or unfinalised sim, a floating base, both outputs
  * null.  An additive entry: no new SHF_ABI_VERSION, no struct layout changed. */
 int shf_sim_dynamics(ShfSim* sim, float* mass_matrix_or_null, float* bias_or_null, void* stream);
+/* The same for a FLOATING base, with the Jacobian of every body, one launch for any non-null subset of the three outputs
+ * (csrc/shf_dyn_fb.hip: k_sim_dynamics_fb).  Generalised velocity nu = (v, w, qd): v the world-axes velocity of the root link's
+ * origin, w the root's world angular velocity (root-state columns 7:10 and 10:13), qd the nd dof velocities; base columns
+ * first, linear before angular.  The order of the base columns is this project's own.
+ *   jacobian (N, nb, 6, nd+6), the layout of SHF_T_JACOBIAN: body b's rows [velocity of b's origin; angular velocity of b] =
+ *     J_b nu in world axes; base columns [[I, -[r_b]x], [0, I]], r_b = p_b - p_root; dof columns as shf_sim_refresh forms them
+ *     for a fixed base, for every moving ancestor (a welded body: its parent chain's columns at its own origin); body 0's block
+ *     is [I6 | 0]; exact zeros off a body's chain.
+ *   mass_matrix (N, nd+6, nd+6): the composite-rigid-body matrix in that order, bit-symmetric; base block = the whole robot's
+ *     composite inertia about the root origin [[m I, -m [c]x], [m [c]x, I_o]]; ShfModel.armature on the dof diagonal only.
+ *   bias (N, nd+6): the generalised forces of one Newton-Euler sweep with nu_dot = 0 (zero CLASSICAL acceleration of the root
+ *     origin, zero root angular acceleration, zero qdd) under gravity * gravity_on; rows 0:3 / 3:6 = net force / moment about
+ *     the root origin.  M nu_dot + h = (external wrench on the root about its origin, tau) + sum J_c^T f_c.
+ * Joint damping, drive gains and the joint-limit penalty are left out as for shf_sim_dynamics.  Reads SHF_T_SIM_DOF,
+ * SHF_T_SIM_ROOT and SHF_T_BODY_MASS_SCALE when bound.  Refused (shf_last_error): a null or unfinalised sim, a fixed base, all
+ * three outputs null, unbound state.  An additive entry: no new SHF_ABI_VERSION, no struct layout changed. */
+int shf_sim_floating_dynamics(ShfSim* sim, float* jacobian_or_null, float* mass_matrix_or_null, float* bias_or_null,
+                              void* stream);
 /* gym.set_dof_actuation_force_tensor / set_dof_position_target_tensor /
  * set_dof_velocity_target_tensor (robot.py:55-64): copies (N*nd) floats. */
 int shf_sim_set_dof_command(ShfSim* sim, int32_t tensor_id, const float* values_dev, void* stream);
@@ -916,6 +934,19 @@ int shf_osc(const float* j_ee, int64_t j_env_stride, const float* mass_matrix, c
             int32_t dof_elem_stride, const float* ee_pose, int64_t ee_env_stride, const float* goal_pose, const float* kp6,
             const float* kd6, float damping, const float* q_rest_or_null, float kp_null, float kd_null,
             const float* effort_limit_or_null, int32_t n, int32_t num_dof, float* efforts_out, void* stream);
+/* LeggedRobot.foot_impedance_control: a Cartesian spring-damper on each of num_feet end bodies in the base frame, one launch,
+ * one thread per env looping over its feet.  With R the root's rotation and Jl the dof columns (6:) of a foot's linear rows:
+ *   p = R^T (p_foot - p_root),  pd = R^T (Jl qd),  F = R (kp3 (.) (target - p) - kd3 (.) pd),  tau += Jl^T F;
+ * then bias[e, 6 + d] (shf_sim_floating_dynamics' h) when given, the clamp to +-effort_limit[d] last (entries <= 0: no limit).
+ * Views: foot f's (6, num_dof + 6) block, rows packed, at j_feet + e * j_env_stride + f * j_foot_stride (the foot rows of
+ * SHF_T_JACOBIAN); dof state as for shf_osc; the root's (pos, quat xyzw) row at root_pose + e * root_env_stride; foot f's
+ * world origin at foot_pos + e * foot_env_stride + f * foot_stride.  target (n, num_feet, 3) in the base frame, kp3 / kd3 (3),
+ * bias (n, num_dof + 6), effort_limit (num_dof): contiguous.  Additive: no new SHF_ABI_VERSION. */
+int shf_foot_impedance(const float* j_feet, int64_t j_env_stride, int64_t j_foot_stride, const float* dof_state,
+                       int32_t dof_elem_stride, const float* root_pose, int64_t root_env_stride, const float* foot_pos,
+                       int64_t foot_env_stride, int64_t foot_stride, const float* target, const float* kp3, const float* kd3,
+                       const float* bias_or_null, const float* effort_limit_or_null, int32_t n, int32_t num_feet,
+                       int32_t num_dof, float* efforts_out, void* stream);
 /* ShifuVecEnv.compute_reward's accumulation (env.py:180-185): rew = terms[0] + terms[1] + ... in that order,
  * sums[k] += terms[k]; HOST arrays of num_keys <= 16 device pointers to (num_envs) fp32 tensors. */
 int shf_reward_accumulate(const float* const* terms, float* const* sums, int32_t num_keys, int64_t num_envs, float* rew,

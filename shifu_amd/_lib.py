@@ -35,6 +35,7 @@ _SIGS = {
     "shf_sim_step_plan": ([vp, C.POINTER(_abi.ShfLaunchPlan)], i32),
     "shf_sim_refresh": ([vp, i32, vp], i32),
     "shf_sim_dynamics": ([vp, vp, vp, vp], i32),
+    "shf_sim_floating_dynamics": ([vp, vp, vp, vp, vp], i32),
     "shf_sim_set_dof_command": ([vp, i32, vp, vp], i32),
     "shf_sim_set_pos_target_indexed": ([vp, vp, vp, i32, vp], i32),
     "shf_sim_apply_body_force": ([vp, vp, vp], i32),
@@ -89,6 +90,9 @@ _SIGS = {
     # j_ee, j_env_stride, mass_matrix, bias, dof_state, dof_elem_stride, ee_pose, ee_env_stride, goal_pose, kp6, kd6, damping,
     # q_rest, kp_null, kd_null, effort_limit, n, num_dof, efforts_out, stream
     "shf_osc": ([vp, i64, vp, vp, vp, i32, vp, i64, vp, vp, vp, C.c_float, vp, C.c_float, C.c_float, vp, i32, i32, vp, vp], i32),
+    # j_feet, j_env_stride, j_foot_stride, dof_state, dof_elem_stride, root_pose, root_env_stride, foot_pos, foot_env_stride,
+    # foot_stride, target, kp3, kd3, bias, effort_limit, n, num_feet, num_dof, efforts_out, stream
+    "shf_foot_impedance": ([vp, i64, i64, vp, i32, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp], i32),
     "shf_reward_accumulate": ([C.POINTER(vp), C.POINTER(vp), i32, i64, vp, vp], i32),
     "shf_gae": ([vp, vp, vp, vp, i32, i64, C.c_float, C.c_float, vp, vp], i32),
     "shf_ppo_loss_workspace": ([i64, i32, C.POINTER(i64)], i32),

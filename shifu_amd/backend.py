@@ -365,6 +365,20 @@ class Sim:
         check(lib().shf_sim_dynamics(self._h, C.c_void_p(mass_matrix.data_ptr()) if mass_matrix is not None else None,
                                      C.c_void_p(bias.data_ptr()) if bias is not None else None, _stream_ptr(self.device)))
 
+    @_on_device
+    def floating_dynamics(self, jacobian: Optional[torch.Tensor] = None, mass_matrix: Optional[torch.Tensor] = None,
+                          bias: Optional[torch.Tensor] = None):
+        """The floating-base form, one launch for any of the three (shf_sim_floating_dynamics): jacobian (num_envs, nb, 6,
+        nd + 6) -- the sim's own T_JACOBIAN, viewed so, is the normal use --, mass_matrix (num_envs, nd + 6, nd + 6) and bias
+        (num_envs, nd + 6) in the order nu = (root linear, root angular, dofs)."""
+        if self._held is not None or self._defer:
+            self._flush_held()
+        n, nb, D = self.num_envs, self.model.nb if self.model is not None else 0, (self.model.nd if self.model is not None else 0) + 6
+        for t, shape in ((jacobian, (n, nb, 6, D)), (mass_matrix, (n, D, D)), (bias, (n, D))):
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and tuple(t.shape) == shape)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(lib().shf_sim_floating_dynamics(self._h, ptr(jacobian), ptr(mass_matrix), ptr(bias), _stream_ptr(self.device)))
+
     def set_dof_command(self, tid: int, values: torch.Tensor):
         v = values if values.is_contiguous() else values.contiguous()
         assert v.dtype == torch.float32 and v.numel() == self.num_envs * self.model.nd

@@ -612,6 +612,28 @@ extern "C" int shf_sim_dynamics(ShfSim* sim, float* mass_matrix_or_null, float* 
   return launch_ptr(shf_dyn_kernel(sim->group), dim3((sim->n + epb - 1) / epb), dim3(256), shf_dyn_lds_bytes(sim->model, sim->group), stream, A);
 }
 
+// The floating-base form: Jacobian (N, nb, 6, nd+6), M (N, nd+6, nd+6) and h (N, nd+6) in one launch (csrc/shf_dyn.h, csrc/shf_dyn_fb.hip:
+// k_sim_dynamics_fb).  shf_sim_dynamics and shf_sim_refresh keep serving (and keep refusing) what they did.
+extern "C" int shf_sim_floating_dynamics(ShfSim* sim, float* jacobian_or_null, float* mass_matrix_or_null, float* bias_or_null,
+                                         void* stream) {
+  if (!sim) return fail("shf_sim_floating_dynamics: null sim");
+  if (!sim->finalized) return fail("shf_sim_floating_dynamics: sim not finalized");
+  if (sim->model.fixed_base) return fail("shf_sim_floating_dynamics: floating base only: shf_sim_dynamics / shf_sim_refresh serve a fixed base");
+  if (!jacobian_or_null && !mass_matrix_or_null && !bias_or_null) return fail("shf_sim_floating_dynamics: all three outputs are null");
+  if (int r = need(sim, {SHF_T_SIM_DOF, SHF_T_SIM_ROOT, SHF_T_MODEL}, "shf_sim_floating_dynamics")) return r;
+  ShfDynFbArgs A;
+  A.d.model = (const ShfModel*)sim->t[SHF_T_MODEL];
+  A.d.n = sim->n; A.d.actors = 1 + sim->nboxes;
+  A.d.dof = (const float*)sim->t[SHF_T_SIM_DOF];
+  A.d.root = (const float*)sim->t[SHF_T_SIM_ROOT];
+  A.d.mscale = (const float*)sim->t[SHF_T_BODY_MASS_SCALE];
+  for (int k = 0; k < 3; k++) A.d.gravity[k] = sim->sp.gravity[k];
+  A.d.mass = mass_matrix_or_null; A.d.bias = bias_or_null;
+  A.jac = jacobian_or_null;
+  const int epb = 256 / sim->group;
+  return launch_ptr(shf_dyn_fb_kernel(sim->group), dim3((sim->n + epb - 1) / epb), dim3(256), shf_dyn_fb_lds_bytes(sim->model, sim->group), stream, A);
+}
+
 extern "C" int shf_sim_set_dof_command(ShfSim* sim, int32_t tensor_id, const float* values_dev, void* stream) {
   if (tensor_id != SHF_T_EFFORT && tensor_id != SHF_T_POS_TARGET && tensor_id != SHF_T_VEL_TARGET)
     return fail("shf_sim_set_dof_command: tensor_id must be EFFORT, POS_TARGET or VEL_TARGET");

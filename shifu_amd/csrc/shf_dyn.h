@@ -32,3 +32,29 @@ struct ShfDynArgs {
 };
 const void* shf_dyn_kernel(int group);
 size_t shf_dyn_lds_bytes(const ShfModel& host_model, int group);
+
+// ---- floating base: shf_sim_floating_dynamics (shf_dyn_fb.hip: k_sim_dynamics_fb, the same launch shape) ----------------
+// Generalised velocity nu = (v, w, qd): v the world-axes velocity of the root link's origin and w the root's world angular
+// velocity (columns 7:10 and 10:13 of the root-state row), qd the nd dof velocities.  Base columns first, linear before
+// angular -- the row order [linear; angular] of the fixed-base Jacobian.  This order is the project's own: the reference never
+// reads the base columns.
+//   jac  (n, nb, 6, nd + 6): body b's rows are [velocity of b's origin; angular velocity of b] = J_b nu in world axes.  Base
+//        columns [[I, -[r_b]x], [0, I]] with r_b = p_b - p_root; dof columns as the fixed-base writer forms them, for every
+//        moving ancestor (a welded body gets its parent chain's columns at its own origin); body 0's block is [I6 | 0];
+//        entries off a body's chain are exact zeros.  One writer per entry.
+//   mass (n, nd + 6, nd + 6): the composite-rigid-body matrix in that order.  Base block = the whole robot's composite inertia
+//        about the root origin, [[m I, -m [c]x], [m [c]x, I_o]]; coupling rows / columns F_d = Ic S_d (permuted from the kernel's
+//        angular-first spatial order); dof block as k_sim_dynamics', armature on the dof diagonal only.  Every off-diagonal
+//        value is stored twice from one register: bit-symmetric.
+//   bias (n, nd + 6): the generalised forces of one Newton-Euler sweep with nu_dot = 0 -- the CLASSICAL acceleration of the
+//        root origin, the root's angular acceleration and qdd all zero, gravity * gravity_on acting.  Rows 0:3 / 3:6: the net
+//        force and the moment about the root origin.  The kernel's spatial acceleration of the root is therefore
+//        (0, -w x v - g): spatial and classical linear acceleration of a moving reference point differ by w x v.
+// With these, M nu_dot + h = (external wrench on the root about its origin, tau) + sum J_c^T f_c.  Left out as above: joint
+// damping, drive gains, the joint-limit penalty.
+struct ShfDynFbArgs {
+  ShfDynArgs d;   // mass (n, nd+6, nd+6), bias (n, nd+6); either may be null
+  float* jac;     // (n, nb, 6, nd+6) or null
+};
+const void* shf_dyn_fb_kernel(int group);
+size_t shf_dyn_fb_lds_bytes(const ShfModel& host_model, int group);

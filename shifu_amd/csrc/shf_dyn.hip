@@ -1,5 +1,6 @@
 // shf_dyn.hip -- k_sim_dynamics: mass matrix and bias forces of a fixed-base articulation, one launch for every env
-// (definitions and what they leave out: shf_dyn.h).
+// (definitions and what they leave out: shf_dyn.h).  The floating-base form, k_sim_dynamics_fb, is shf_dyn_fb.hip: a unit of
+// its own, so that this one compiles to the machine code it had.
 //
 // Layout: k_body_state's -- the model staged in LDS, one EnvLds per env, one lane per body, `G` lanes per env, 256 / G envs
 // per block.  Per env:

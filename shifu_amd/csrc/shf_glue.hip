@@ -431,6 +431,86 @@ extern "C" int shf_osc(const float* j_ee, int64_t j_env_stride, const float* mas
   return GLUE_LAUNCH_OK("shf_osc");
 }
 
+// K12 -- LeggedRobot.foot_impedance_control: Cartesian spring-damper on every foot in the base frame, the legged twin of K11.
+// Per foot f, with R the root's rotation and Jl = the dof columns of the foot's linear Jacobian rows (the foot's velocity
+// relative to the base):  p = R^T (p_f - p_root),  pd = R^T (Jl qd),  F = R (kp (.) (target - p) - kd (.) pd),  tau += Jl^T F.
+// Then + bias[6:] (gravity and Coriolis compensation of the legs), then the effort clamp.
+// One thread per env looping over its feet, so end bodies that share an ancestor dof accumulate in one thread; tau (run-time
+// sized) lives in LDS, word d of thread t at [d * T + t], as K11's arrays.
+struct FootArgs {
+  const float* j; long long j_env, j_foot;
+  const float* dof; int dof_stride;
+  const float* root; long long root_env;
+  const float* foot; long long foot_env, foot_stride;
+  const float* target; const float* kp3; const float* kd3;
+  const float* bias; const float* limit;
+  int n, nf, nd;
+  float* out;
+};
+__global__ void k_foot_impedance(FootArgs A) {
+  extern __shared__ float foot_lds[];
+  const int T = blockDim.x, t = threadIdx.x, nd = A.nd, D = A.nd + 6;
+  const int e = blockIdx.x * T + t;
+  if (e >= A.n) return;
+  float* tau = foot_lds + t;
+  const float* ds = A.dof + (long long)e * nd * A.dof_stride;
+  const float* rp = A.root + (long long)e * A.root_env;
+  for (int d = 0; d < nd; d++) tau[d * T] = 0.0f;
+  const float x = rp[3], y = rp[4], z = rp[5], w = rp[6];
+  const float R[9] = {1.0f - 2.0f * (y * y + z * z), 2.0f * (x * y - w * z), 2.0f * (x * z + w * y),
+                      2.0f * (x * y + w * z), 1.0f - 2.0f * (x * x + z * z), 2.0f * (y * z - w * x),
+                      2.0f * (x * z - w * y), 2.0f * (y * z + w * x), 1.0f - 2.0f * (x * x + y * y)};
+  const float kp[3] = {A.kp3[0], A.kp3[1], A.kp3[2]}, kd[3] = {A.kd3[0], A.kd3[1], A.kd3[2]};
+  for (int f = 0; f < A.nf; f++) {
+    const float* J = A.j + (long long)e * A.j_env + (long long)f * A.j_foot + 6;   // linear rows, dof columns
+    const float* pf = A.foot + (long long)e * A.foot_env + (long long)f * A.foot_stride;
+    const float* tg = A.target + ((long long)e * A.nf + f) * 3;
+    float vw[3] = {0.0f, 0.0f, 0.0f};
+    for (int d = 0; d < nd; d++) {
+      const float qd = ds[d * A.dof_stride + 1];
+#pragma unroll
+      for (int k = 0; k < 3; k++) vw[k] = fmaf(J[k * D + d], qd, vw[k]);
+    }
+    const float dw[3] = {pf[0] - rp[0], pf[1] - rp[1], pf[2] - rp[2]};
+    float g[3], F[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const float p = fmaf(R[6 + k], dw[2], fmaf(R[3 + k], dw[1], R[k] * dw[0]));      // R^T
+      const float pd = fmaf(R[6 + k], vw[2], fmaf(R[3 + k], vw[1], R[k] * vw[0]));
+      g[k] = kp[k] * (tg[k] - p) - kd[k] * pd;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) F[k] = fmaf(R[3 * k + 2], g[2], fmaf(R[3 * k + 1], g[1], R[3 * k] * g[0]));
+    for (int d = 0; d < nd; d++)
+      tau[d * T] = fmaf(J[2 * D + d], F[2], fmaf(J[D + d], F[1], fmaf(J[d], F[0], tau[d * T])));
+  }
+  for (int d = 0; d < nd; d++) {
+    float v = tau[d * T];
+    if (A.bias) v += A.bias[(long long)e * D + 6 + d];
+    const float lim = A.limit ? A.limit[d] : 0.0f;
+    if (lim > 0.0f) v = v > lim ? lim : (v < -lim ? -lim : v);
+    A.out[(long long)e * nd + d] = v;
+  }
+}
+
+extern "C" int shf_foot_impedance(const float* j_feet, int64_t j_env_stride, int64_t j_foot_stride, const float* dof_state,
+                                  int32_t dof_elem_stride, const float* root_pose, int64_t root_env_stride, const float* foot_pos,
+                                  int64_t foot_env_stride, int64_t foot_stride, const float* target, const float* kp3,
+                                  const float* kd3, const float* bias_or_null, const float* effort_limit_or_null, int32_t n,
+                                  int32_t num_feet, int32_t num_dof, float* efforts_out, void* stream) {
+  if (!j_feet || !dof_state || !root_pose || !foot_pos || !target || !kp3 || !kd3 || !efforts_out) return shf_set_error("shf_foot_impedance: null tensor");
+  if (n <= 0 || num_dof <= 0) return 0;
+  if (num_feet < 0) return shf_set_error("shf_foot_impedance: negative foot count");
+  if (num_dof > SHF_MAX_DOFS) return shf_set_error("shf_foot_impedance: too many dofs");
+  if (dof_elem_stride < 2) return shf_set_error("shf_foot_impedance: dof_state holds position and velocity (element stride >= 2)");
+  const int T = 64;
+  FootArgs A = {j_feet, (long long)j_env_stride, (long long)j_foot_stride, dof_state, (int)dof_elem_stride, root_pose, (long long)root_env_stride,
+                foot_pos, (long long)foot_env_stride, (long long)foot_stride, target, kp3, kd3, bias_or_null, effort_limit_or_null,
+                (int)n, (int)num_feet, (int)num_dof, efforts_out};
+  hipLaunchKernelGGL(k_foot_impedance, dim3((n + T - 1) / T), dim3(T), (size_t)T * num_dof * 4, (hipStream_t)stream, A);
+  return GLUE_LAUNCH_OK("shf_foot_impedance");
+}
+
 extern "C" int shf_base_frame_state(const float* root_state, const int64_t* root_idx_or_null, int64_t num_root_rows, int32_t n,
                                     int32_t up_axis, float* base_lin_vel, float* base_ang_vel, float* projected_gravity,
                                     float* gravity_vec, void* stream) {

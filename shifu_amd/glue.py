@@ -165,3 +165,29 @@ def osc(j_ee, mass_matrix, bias, dof_state, ee_pose, goal_pose, kp6, kd6, dampin
                             float(kd_null), None if effort_limit is None else _f32c(effort_limit), n, nd, _f32c(out),
                             _stream(j_ee.device)))
     return out
+
+
+def foot_impedance(j_feet, dof_state, root_pose, foot_pos, target, kp3, kd3, bias=None, effort_limit=None):
+    """LeggedRobot.foot_impedance_control in one launch (shf_foot_impedance): efforts (n, nd).  j_feet (n, F, 6, nd + 6): the
+    foot rows of the floating-base Jacobian tensor (a view: rows packed inside a foot's block, any stride between feet and
+    envs); dof_state as for osc; root_pose (n, >= 7) rows (pos, quat xyzw) and foot_pos (n, F, 3) world origins, unit stride
+    in the last axis; target (n, F, 3) in the base frame; kp3 / kd3 (3); bias (n, nd + 6) or None; effort_limit (nd) or None."""
+    n, F, six, D = j_feet.shape
+    nd = D - 6
+    assert six == 6 and j_feet.stride(3) == 1 and j_feet.stride(2) == D
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in (j_feet, dof_state, root_pose, foot_pos)), "float32 CUDA tensors expected"
+    assert dof_state.shape[:2] == (n, nd) and dof_state.shape[2] >= 2 and dof_state.stride(2) == 1
+    assert dof_state.stride(1) >= 2 and dof_state.stride(0) == nd * dof_state.stride(1)
+    assert root_pose.shape[0] == n and root_pose.shape[1] >= 7 and root_pose.stride(1) == 1
+    assert foot_pos.shape == (n, F, 3) and foot_pos.stride(2) == 1 and tuple(target.shape) == (n, F, 3)
+    assert kp3.numel() == 3 and kd3.numel() == 3
+    assert bias is None or tuple(bias.shape) == (n, D)
+    assert effort_limit is None or effort_limit.numel() == nd
+    out = torch.empty(n, nd, device=j_feet.device, dtype=torch.float32)
+    with torch.cuda.device(j_feet.device):
+        check(lib().shf_foot_impedance(_vp(j_feet.data_ptr()), j_feet.stride(0), j_feet.stride(1), _vp(dof_state.data_ptr()),
+                                       dof_state.stride(1), _vp(root_pose.data_ptr()), root_pose.stride(0), _vp(foot_pos.data_ptr()),
+                                       foot_pos.stride(0), foot_pos.stride(1), _f32c(target.contiguous()), _f32c(kp3), _f32c(kd3),
+                                       None if bias is None else _f32c(bias), None if effort_limit is None else _f32c(effort_limit),
+                                       n, F, nd, _f32c(out), _stream(j_feet.device)))
+    return out

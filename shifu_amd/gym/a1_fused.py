@@ -236,6 +236,28 @@ class FusedA1Env(FusedCameraHost):
     def get_privileged_observations(self):
         return self.privileged_obs_buf
 
+    # -- whole-body dynamics (csrc/shf_dyn.h: the floating-base form; not part of the fused step) ------------------------------
+    def whole_body_dynamics(self):
+        """{"jacobian" (n, nb, 6, nd + 6), "mass_matrix" (n, nd + 6, nd + 6), "bias" (n, nd + 6)} of the solver's current state,
+        in the order nu = (root linear, root angular, dofs); one launch.  The tensors are allocated once (the Jacobian is the
+        sim's own tensor) and refreshed by every call."""
+        if getattr(self, "_wbd", None) is None:
+            D = self.cm.blob.nd + 6
+            self._wbd = {"jacobian": self.sim.tensors[_abi.T_JACOBIAN],
+                         "mass_matrix": torch.zeros(self.num_envs, D, D, device=self.device),
+                         "bias": torch.zeros(self.num_envs, D, device=self.device)}
+        w = self._wbd
+        self.sim.floating_dynamics(w["jacobian"], w["mass_matrix"], w["bias"])
+        return w
+
+    @property
+    def foot_jacobians(self):
+        """(n, 4, 6, nd + 6): the feet's rows of the Jacobian tensor (a view; whole_body_dynamics fills it), feet in body order."""
+        feet = [b for b, name in enumerate(self.cm.body_names) if name.endswith("_foot")]
+        step = feet[1] - feet[0]
+        assert len(feet) == 4 and all(b - a == step for a, b in zip(feet, feet[1:])), "the A1's feet are evenly spaced bodies"
+        return self.sim.tensors[_abi.T_JACOBIAN][:, feet[0]:feet[-1] + 1:step]
+
     def state_dict(self):
         """Checkpoint of the whole simulation + task state (shifu_amd/checkpoint.py)."""
         from ..checkpoint import env_state_dict

@@ -580,7 +580,9 @@ class Gym:
         sim.backend.refresh(_abi.REFRESH_BODY)
         sim.body_fresh = True
     def refresh_net_contact_force_tensor(self, sim): sim.backend.refresh(_abi.REFRESH_CONTACT)
-    def refresh_jacobian_tensors(self, sim): sim.backend.refresh(_abi.REFRESH_JACOBIAN)
+    def refresh_jacobian_tensors(self, sim):
+        sim.backend.refresh(_abi.REFRESH_JACOBIAN)
+        self._refresh_floating_jacobian(sim)
     def refresh_force_sensor_tensor(self, sim): pass
 
     def refresh_all_state_tensors(self, sim):
@@ -588,11 +590,27 @@ class Gym:
         call (shifu's refresh_state issues the six refresh_* calls back to back, shifu/gym/isaac_gym.py:145-154)."""
         sim.backend.refresh(_abi.REFRESH_ALL)
         sim.body_fresh = True
+        self._refresh_floating_jacobian(sim)
+
+    @staticmethod
+    def _floating_dynamics_enabled(sim):
+        """SHIFU_AMD_FLOATING_DYNAMICS=1 (read at call time) and a floating base: the Jacobian tensor (N, nb, 6, nd + 6), the
+        mass matrix (N, nd + 6, nd + 6) and the bias forces (N, nd + 6) in the order nu = (root linear, root angular, dofs) of
+        csrc/shf_dyn.h (shf_sim_floating_dynamics).  Unset, every call is what it was; fixed-base sims
+        are not affected either way."""
+        return os.environ.get("SHIFU_AMD_FLOATING_DYNAMICS", "0") == "1" and not sim.backend.model.fixed_base
+
+    def _refresh_floating_jacobian(self, sim):
+        if self._floating_dynamics_enabled(sim):          # one more launch, for those who asked
+            sim.backend.floating_dynamics(jacobian=sim.backend.tensors[_abi.T_JACOBIAN])
 
     def _acquire_dynamics(self, sim, attr, shape):
         import torch
         be = sim.backend
-        if not be.model.fixed_base:
+        if self._floating_dynamics_enabled(sim):
+            D = be.model.nd + 6
+            shape = (be.num_envs, D, D) if attr == "mass_matrix" else (be.num_envs, D)
+        elif not be.model.fixed_base:
             raise NotImplementedError("mass-matrix and bias-force tensors: fixed base only (as the Jacobian tensor's dof columns)")
         if getattr(sim, attr) is None:        # allocated once per sim
             setattr(sim, attr, torch.zeros(shape, dtype=torch.float32, device=be.device))
@@ -600,7 +618,8 @@ class Gym:
 
     def acquire_mass_matrix_tensor(self, sim, name):
         """(num_envs, nd, nd): M(q) of the articulation, armature on the diagonal (csrc/shf_dyn.h); filled by
-        refresh_mass_matrix_tensors."""
+        refresh_mass_matrix_tensors.  A floating base under SHIFU_AMD_FLOATING_DYNAMICS=1: (num_envs, nd + 6, nd + 6), root
+        columns first (and the bias forces (num_envs, nd + 6))."""
         nd = sim.backend.model.nd
         return self._acquire_dynamics(sim, "mass_matrix", (sim.backend.num_envs, nd, nd))
 
@@ -612,6 +631,9 @@ class Gym:
     def refresh_mass_matrix_tensors(self, sim):
         """Fills whichever of the mass-matrix / bias-force tensors was acquired, in one launch; nothing to do otherwise."""
         if sim.mass_matrix is None and sim.dof_bias is None:
+            return
+        if self._floating_dynamics_enabled(sim):
+            sim.backend.floating_dynamics(None, sim.mass_matrix, sim.dof_bias)
             return
         sim.backend.dynamics(sim.mass_matrix, sim.dof_bias)
 

@@ -54,3 +54,32 @@ def operational_space_control(j_ee, mass_matrix, dof_pos, dof_vel, ee_pos, ee_qu
         lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
         tau = torch.maximum(torch.minimum(tau, lim), -lim)
     return tau
+
+
+def quat_to_matrix(q):
+    """(n, 4) xyzw -> (n, 3, 3)."""
+    x, y, z, w = q.unbind(-1)
+    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                        2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                        2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1).view(-1, 3, 3)
+
+
+def foot_impedance_control(j_feet, dof_vel, root_pos, root_quat, foot_pos, target, kp3, kd3, bias=None, effort_limit=None):
+    """Cartesian foot control in the base frame.  j_feet (n, F, 6, nd + 6): the foot rows of the floating-base Jacobian; with
+    R the root's rotation and Jl = j_feet[:, f, :3, 6:] (the foot's velocity relative to the base per unit dof velocity):
+    p = R^T (p_foot - p_root), pd = R^T (Jl qd), F = R (kp3 (p_target - p) - kd3 pd), tau = sum over feet of Jl^T F; then
+    + bias[:, 6:], then the clamp to +-effort_limit (entries <= 0: no limit).  The torch expressions of csrc/shf_glue.hip's
+    shf_foot_impedance."""
+    R = quat_to_matrix(root_quat).unsqueeze(1)                      # (n, 1, 3, 3)
+    Rt = torch.transpose(R, 2, 3)
+    jl = j_feet[:, :, :3, 6:]                                       # (n, F, 3, nd)
+    p = (Rt @ (foot_pos - root_pos.unsqueeze(1)).unsqueeze(-1)).squeeze(-1)
+    pd = (Rt @ (jl @ dof_vel.unsqueeze(1).unsqueeze(-1))).squeeze(-1)
+    f = (R @ (kp3 * (target - p) - kd3 * pd).unsqueeze(-1))         # (n, F, 3, 1)
+    tau = (torch.transpose(jl, 2, 3) @ f).squeeze(-1).sum(1)
+    if bias is not None:
+        tau = tau + bias[:, 6:]
+    if effort_limit is not None:
+        lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
+        tau = torch.maximum(torch.minimum(tau, lim), -lim)
+    return tau

@@ -947,6 +947,34 @@ int shf_foot_impedance(const float* j_feet, int64_t j_env_stride, int64_t j_foot
                        int64_t foot_env_stride, int64_t foot_stride, const float* target, const float* kp3, const float* kd3,
                        const float* bias_or_null, const float* effort_limit_or_null, int32_t n, int32_t num_feet,
                        int32_t num_dof, float* efforts_out, void* stream);
+/* LeggedRobot.balance_control: the foot forces that give the base a wanted wrench without slipping, and the joint efforts
+ * that produce them; one launch, one thread per env (csrc/shf_qp.hip, whose header states the algorithm step by step).  Per
+ * env, num_feet <= 4 feet, world axes with z up, r_f = p_foot_f - p_root, G = [[I .. I], [[r_1]x .. [r_F]x]]:
+ *   minimise  1/2 (G f - w)^T S (G f - w) + 1/2 alpha |f|^2 + 1/2 beta |f - f_prev|^2,   S = diag(weights6),
+ *   stance foot: fz_min <= f_z <= fz_max, |f_x| <= mu f_z, |f_y| <= mu f_z;   swing foot (stance[e, f] == 0): f = 0,
+ * by `iters` sweeps of ADMM on one LDL^T factor (a fixed trip count), then a per-foot clamp of f_z and of f_x, f_y to
+ * +-mu f_z, so that forces_out (n, num_feet, 3) satisfies every constraint exactly.  efforts_out (n, num_dof) =
+ * -sum_f Jl_f^T f_f over the dof columns (6:) of each foot's linear Jacobian rows, then bias[e, 6 + d] when given, the clamp
+ * to +-effort_limit[d] last (entries <= 0: no limit), as shf_foot_impedance.
+ * The wanted wrench w: wrench (n, 6) when given; otherwise, from shf_sim_floating_dynamics' mass_matrix (n, D, D) and
+ * dyn_bias (n, D), D = num_dof + 6, the root's 13-float row (pos, quat xyzw, v, omega) at root_pose, base_target (n, 13) of
+ * the same layout and gains12 = (kp_lin, kd_lin, kp_ang, kd_ang):
+ *   a_lin = kp_lin (.) (p* - p) + kd_lin (.) (v* - v),  a_ang = kp_ang (.) orientation_error(q*, q) + kd_ang (.) (omega* - omega),
+ *   w = M[0:6, 0:6] (a_lin, a_ang) + h[0:6]   (orientation_error as shf_ik_dls; the coupling M[0:6, 6:] qdd is neglected).
+ * Views as for shf_foot_impedance: foot f's (6, D) block at j_feet + e * j_env_stride + f * j_foot_stride; the root's row at
+ * root_pose + e * root_env_stride (7 floats read when the wrench is given, 13 otherwise); foot f's world origin at foot_pos +
+ * e * foot_env_stride + f * foot_stride.  stance (n, num_feet) uint8; mu (n) or NULL for mu_scalar (per-env entries below 0
+ * count as 0); f_prev (n, num_feet, 3) or NULL (beta unused); fz_max may be +inf; bias (n, D); weights6 (6), effort_limit
+ * (num_dof): contiguous.  Refused with a message: num_feet outside 1..4, num_dof outside 1..SHF_MAX_DOFS, alpha <= 0, beta < 0,
+ * fz_min > fz_max, mu_scalar < 0, iters < 1, a null required tensor.  Additive: no new SHF_ABI_VERSION. */
+int shf_foot_force_qp(const float* j_feet, int64_t j_env_stride, int64_t j_foot_stride, const float* root_pose,
+                      int64_t root_env_stride, const float* foot_pos, int64_t foot_env_stride, int64_t foot_stride,
+                      const float* wrench_or_null, const float* mass_matrix_or_null, const float* dyn_bias_or_null,
+                      const float* base_target_or_null, const float* gains12_or_null, const uint8_t* stance,
+                      const float* mu_or_null, float mu_scalar, const float* weights6, float alpha, float beta,
+                      const float* f_prev_or_null, float fz_min, float fz_max, int32_t iters, const float* bias_or_null,
+                      const float* effort_limit_or_null, int32_t n, int32_t num_feet, int32_t num_dof, float* forces_out,
+                      float* efforts_out, void* stream);
 /* ShifuVecEnv.compute_reward's accumulation (env.py:180-185): rew = terms[0] + terms[1] + ... in that order,
  * sums[k] += terms[k]; HOST arrays of num_keys <= 16 device pointers to (num_envs) fp32 tensors. */
 int shf_reward_accumulate(const float* const* terms, float* const* sums, int32_t num_keys, int64_t num_envs, float* rew,

@@ -93,6 +93,11 @@ _SIGS = {
     # j_feet, j_env_stride, j_foot_stride, dof_state, dof_elem_stride, root_pose, root_env_stride, foot_pos, foot_env_stride,
     # foot_stride, target, kp3, kd3, bias, effort_limit, n, num_feet, num_dof, efforts_out, stream
     "shf_foot_impedance": ([vp, i64, i64, vp, i32, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp], i32),
+    # j_feet, j_env_stride, j_foot_stride, root_pose, root_env_stride, foot_pos, foot_env_stride, foot_stride, wrench, mass_matrix,
+    # dyn_bias, base_target, gains12, stance, mu, mu_scalar, weights6, alpha, beta, f_prev, fz_min, fz_max, iters, bias,
+    # effort_limit, n, num_feet, num_dof, forces_out, efforts_out, stream (csrc/shf_qp.hip)
+    "shf_foot_force_qp": ([vp, i64, i64, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, C.c_float, C.c_float, vp,
+                           C.c_float, C.c_float, i32, vp, vp, i32, i32, i32, vp, vp, vp], i32),
     "shf_reward_accumulate": ([C.POINTER(vp), C.POINTER(vp), i32, i64, vp, vp], i32),
     "shf_gae": ([vp, vp, vp, vp, i32, i64, C.c_float, C.c_float, vp, vp], i32),
     "shf_ppo_loss_workspace": ([i64, i32, C.POINTER(i64)], i32),

@@ -191,3 +191,86 @@ def foot_impedance(j_feet, dof_state, root_pose, foot_pos, target, kp3, kd3, bia
                                        None if bias is None else _f32c(bias), None if effort_limit is None else _f32c(effort_limit),
                                        n, F, nd, _f32c(out), _stream(j_feet.device)))
     return out
+
+
+QP_ITERS = 100       # default sweeps of foot_force_qp (DESIGN.md 8h "Balance controller": what they leave of the optimum)
+
+
+def foot_force_qp(j_feet, root_pose, foot_pos, stance, mu, weights6, wrench=None, mass_matrix=None, dyn_bias=None, base_target=None,
+                  gains12=None, alpha=1e-2, beta=0.0, f_prev=None, fz_min=5.0, fz_max=float("inf"), iters=QP_ITERS, bias=None,
+                  effort_limit=None):
+    """LeggedRobot.balance_control in one launch (shf_foot_force_qp): (forces (n, F, 3), efforts (n, nd)).  j_feet, root_pose,
+    foot_pos: views as for foot_impedance (root_pose rows of >= 13 floats (pos, quat, v, omega) unless `wrench` is given).
+    stance (n, F) uint8 / bool; mu a float or a (n) tensor; weights6 (6).  The wanted base wrench: `wrench` (n, 6), or
+    mass_matrix (n, nd + 6, nd + 6), dyn_bias (n, nd + 6), base_target (n, 13) and gains12 (12) = (kp_lin, kd_lin, kp_ang,
+    kd_ang).  f_prev (n, F, 3) or None; bias (n, nd + 6) or None: added to the efforts; effort_limit (nd) or None."""
+    n, F, six, D = j_feet.shape
+    nd = D - 6
+    assert six == 6 and j_feet.stride(3) == 1 and j_feet.stride(2) == D
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in (j_feet, root_pose, foot_pos)), "float32 CUDA tensors expected"
+    assert root_pose.shape[0] == n and root_pose.shape[1] >= (7 if wrench is not None else 13) and root_pose.stride(1) == 1
+    assert foot_pos.shape == (n, F, 3) and foot_pos.stride(2) == 1
+    assert tuple(stance.shape) == (n, F) and stance.dtype in (torch.uint8, torch.bool) and stance.is_cuda
+    assert weights6.numel() == 6
+    if wrench is None:
+        assert mass_matrix is not None and dyn_bias is not None and base_target is not None and gains12 is not None, \
+            "without a wrench: mass_matrix, dyn_bias, base_target and gains12"
+        assert tuple(mass_matrix.shape) == (n, D, D) and tuple(dyn_bias.shape) == (n, D)
+        assert tuple(base_target.shape) == (n, 13) and gains12.numel() == 12
+    else:
+        assert tuple(wrench.shape) == (n, 6)
+    assert f_prev is None or tuple(f_prev.shape) == (n, F, 3)
+    assert bias is None or tuple(bias.shape) == (n, D)
+    assert effort_limit is None or effort_limit.numel() == nd
+    per_env = torch.is_tensor(mu) and mu.numel() > 1
+    assert not per_env or mu.numel() == n
+    st = stance.contiguous().view(torch.uint8)
+    keep = []                 # contiguous copies of optional inputs stay referenced until the launch is enqueued
+
+    def o(t):
+        if t is None:
+            return None
+        keep.append(t.contiguous())
+        return _f32c(keep[-1])
+
+    forces = torch.empty(n, F, 3, device=j_feet.device, dtype=torch.float32)
+    out = torch.empty(n, nd, device=j_feet.device, dtype=torch.float32)
+    with torch.cuda.device(j_feet.device):
+        check(lib().shf_foot_force_qp(_vp(j_feet.data_ptr()), j_feet.stride(0), j_feet.stride(1), _vp(root_pose.data_ptr()),
+                                      root_pose.stride(0), _vp(foot_pos.data_ptr()), foot_pos.stride(0), foot_pos.stride(1),
+                                      o(wrench), o(mass_matrix), o(dyn_bias), o(base_target), o(gains12), _vp(st.data_ptr()),
+                                      o(mu.reshape(n)) if per_env else None, 0.0 if per_env else float(mu), o(weights6),
+                                      float(alpha), float(beta), o(f_prev), float(fz_min), float(fz_max), int(iters), o(bias),
+                                      o(effort_limit), n, F, nd, _f32c(forces), _f32c(out), _stream(j_feet.device)))
+    return forces, out
+
+
+def gain3(g, device):
+    g = torch.as_tensor(g, dtype=torch.float32, device=device)
+    return (g.expand(3) if g.dim() == 0 else g.reshape(3)).contiguous()
+
+
+def balance_control(j_feet, root_state, foot_pos, contact_z, shape_friction, ground_friction, mass_matrix, bias, target, effort_limit,
+                    base_pos, base_quat, base_lin_vel=None, base_ang_vel=None, stance=None, kp_lin=100., kd_lin=None, kp_ang=400.,
+                    kd_ang=None, mu=None, fz_min=5., fz_max=None, weights=(1, 1, 1, 10, 10, 10), alpha=1e-2, beta=0.,
+                    gravity_compensation=True, f_prev=None):
+    """What LeggedRobot.balance_control and FusedA1Env.balance_control share: the gains (kd None = 2 sqrt(kp)), the base target
+    written into the caller's (n, 13) buffer `target`, stance None = the feet whose contact force z (contact_z (n, F)) exceeds
+    1 N, mu None = the friction the simulator applies, (shape_friction (n) + ground_friction) / 2 -- formed per call, so it
+    follows the friction tensor --, then foot_force_qp.  Returns (efforts, forces)."""
+    dev = j_feet.device
+    kpl, kpa = gain3(kp_lin, dev), gain3(kp_ang, dev)
+    gains = torch.cat([kpl, 2.0 * torch.sqrt(kpl) if kd_lin is None else gain3(kd_lin, dev),
+                       kpa, 2.0 * torch.sqrt(kpa) if kd_ang is None else gain3(kd_ang, dev)])
+    target[:, :3], target[:, 3:7] = base_pos, base_quat
+    target[:, 7:10] = 0.0 if base_lin_vel is None else base_lin_vel
+    target[:, 10:13] = 0.0 if base_ang_vel is None else base_ang_vel
+    if stance is None:
+        stance = (contact_z > 1.0).to(torch.uint8)
+    if mu is None:
+        mu = 0.5 * (shape_friction + float(ground_friction))
+    S = torch.as_tensor(weights, dtype=torch.float32, device=dev).reshape(6).contiguous()
+    forces, efforts = foot_force_qp(j_feet, root_state, foot_pos, stance, mu, S, None, mass_matrix, bias, target, gains, alpha, beta,
+                                    f_prev if beta > 0 else None, fz_min, float("inf") if fz_max is None else float(fz_max), QP_ITERS,
+                                    bias if gravity_compensation else None, effort_limit)
+    return efforts, forces

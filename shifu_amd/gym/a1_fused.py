@@ -258,6 +258,31 @@ class FusedA1Env(FusedCameraHost):
         assert len(feet) == 4 and all(b - a == step for a, b in zip(feet, feet[1:])), "the A1's feet are evenly spaced bodies"
         return self.sim.tensors[_abi.T_JACOBIAN][:, feet[0]:feet[-1] + 1:step]
 
+    def balance_control(self, base_pos, base_quat, base_lin_vel=None, base_ang_vel=None, stance=None, kp_lin=100., kd_lin=None,
+                        kp_ang=400., kd_ang=None, mu=None, fz_min=5., fz_max=None, weights=(1, 1, 1, 10, 10, 10), alpha=1e-2,
+                        beta=0., gravity_compensation=True):
+        """(efforts (n, nd), forces (n, 4, 3)) of LeggedRobot.balance_control (csrc/shf_qp.hip: shf_foot_force_qp, one launch)
+        from whole_body_dynamics()'s tensors and the root, body and contact tensors as the last step left them: the stance
+        feet's ground-reaction forces that pull the base towards base_pos (n, 3) / base_quat (n, 4), and the efforts that
+        produce them.  stance None = the feet whose net contact force z exceeds 1 N; mu None = the env's contact friction.  Not
+        part of the fused step."""
+        from .. import glue
+        w = self.whole_body_dynamics()
+        n, nb = self.num_envs, self.cm.blob.nb
+        if getattr(self, "_bal_target", None) is None:
+            self._bal_target = torch.zeros(n, 13, device=self.device)
+            self._bal_limit = torch.tensor([self.cm.blob.effort[d] for d in range(self.cm.blob.nd)], device=self.device)
+        fb = [b for b, name in enumerate(self.cm.body_names) if name.endswith("_foot")]     # evenly spaced (foot_jacobians)
+        rows = slice(fb[0], fb[-1] + 1, fb[1] - fb[0])
+        efforts, forces = glue.balance_control(
+            self.foot_jacobians, self.root_state.view(n, 13), self.body_state.view(n, nb, 13)[:, rows, :3],
+            self.contact_state.view(n, nb, 3)[:, rows, 2], self.sim.tensors[_abi.T_FRICTION], self.sim.terrain.friction,
+            w["mass_matrix"], w["bias"], self._bal_target, self._bal_limit, base_pos, base_quat, base_lin_vel, base_ang_vel, stance,
+            kp_lin, kd_lin, kp_ang, kd_ang, mu, fz_min, fz_max, weights, alpha, beta, gravity_compensation,
+            getattr(self, "_bal_forces", None))
+        self._bal_forces = forces
+        return efforts, forces
+
     def state_dict(self):
         """Checkpoint of the whole simulation + task state (shifu_amd/checkpoint.py)."""
         from ..checkpoint import env_state_dict

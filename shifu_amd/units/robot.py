@@ -328,3 +328,106 @@ class LeggedRobot(ArmRobot):
             if self.device == 'cpu':
                 self.gym.fetch_results(self.sim, True)
             self.gym.refresh_dof_state_tensor(self.sim)
+
+    # -- balance control: the stance feet's forces from a QP (not in the reference; SHIFU_AMD_FLOATING_DYNAMICS=1) ----------
+    def _contact_friction(self):
+        """(num_envs) the friction coefficient the simulator applies between this robot's shapes and the ground, as it stands."""
+        from shifu_amd import _abi
+        be = self.sim.backend
+        return 0.5 * (be.tensors[_abi.T_FRICTION] + float(be.terrain.friction)).to(self.device)
+
+    def _foot_dof_mask(self):
+        """(num_ee, nd): 1 where a dof lies on the chain from the root to an end body."""
+        if getattr(self, "_bal_chain", None) is None:
+            m = self.sim.backend.model
+            mask = torch.zeros(len(self._ee_list), self.num_dof)
+            for f, b in enumerate(self._ee_list):
+                while b > 0:
+                    if m.dof[b] >= 0:
+                        mask[f, m.dof[b]] = 1.0
+                    b = m.parent[b]
+            self._bal_chain = mask.to(self.device)
+        return self._bal_chain
+
+    def stance_from_contacts(self, threshold=1.0):
+        """(num_envs, num_ee) uint8: the end bodies whose net contact force along z, as last refreshed, exceeds `threshold`."""
+        return (self._end_rows(self.contact_forces)[..., 2] > threshold).to(torch.uint8)
+
+    def balance_control(self, base_pos, base_quat, base_lin_vel=None, base_ang_vel=None, stance=None, kp_lin=100., kd_lin=None,
+                        kp_ang=400., kd_ang=None, mu=None, fz_min=5., fz_max=None, weights=(1, 1, 1, 10, 10, 10), alpha=1e-2,
+                        beta=0., gravity_compensation=True):
+        """(efforts (num_envs, nd), forces (num_envs, num_ee, 3)): the ground-reaction forces that give the base the wrench
+        w = M[0:6, 0:6] (a_lin, a_ang) + h[0:6] of a spring-damper towards base_pos (n, 3) / base_quat (n, 4) (and the world
+        velocities base_lin_vel / base_ang_vel, None = rest) without slipping, and the efforts -sum J^T f that produce them; from
+        the mass-matrix, bias, Jacobian, root, body and contact tensors as last refreshed.  a_lin = kp_lin (p* - p) + kd_lin (v* - v),
+        a_ang = kp_ang orientation_error(q*, q) + kd_ang (omega* - omega); the coupling of the dof accelerations is neglected.
+        The forces minimise 1/2 |G f - w|^2 weighted by `weights` + 1/2 alpha |f|^2 + 1/2 beta |f - previous call's f|^2 subject to
+        fz_min <= f_z <= fz_max (None: no upper bound) and |f_x|, |f_y| <= mu f_z on the stance feet, f = 0 on the others
+        (csrc/shf_qp.hip).  stance (n, num_ee) None = stance_from_contacts(); mu None = the env's contact friction, else a
+        float or (n); kp / kd: scalars or 3-vectors, kd None = 2 sqrt(kp).  gravity_compensation adds bias_forces[:, 6:].
+        Clamped to the asset's effort limits."""
+        h = self.bias_forces                     # (refused with "fixed base" unless SHIFU_AMD_FLOATING_DYNAMICS=1)
+        M = self.mass_matrix
+        n = self.env.num_envs
+        if getattr(self, "_bal_target", None) is None:
+            self._bal_target = torch.zeros(n, 13, device=self.device)
+        tg = self._bal_target
+        jf = self.foot_jacobians
+        root = self.env.root_state.view(n, -1, 13)[:, 0]
+        feet = self._end_rows(self.env.body_state.view(n, -1, 13))[..., :3]
+        f_prev = getattr(self, "_bal_forces", None)
+        if jf.is_cuda and jf.dtype == torch.float32 and tg.is_cuda:
+            # the expressions of utils.torch_utils.balance_wrench / foot_force_qp as one launch (csrc/shf_qp.hip: shf_foot_force_qp)
+            from shifu_amd import _abi, glue
+            be = self.sim.backend
+            efforts, forces = glue.balance_control(
+                jf, root, feet, self._end_rows(self.contact_forces)[..., 2], be.tensors[_abi.T_FRICTION], be.terrain.friction, M, h, tg,
+                self.torque_limits.contiguous(), base_pos, base_quat, base_lin_vel, base_ang_vel, stance, kp_lin, kd_lin, kp_ang,
+                kd_ang, mu, fz_min, fz_max, weights, alpha, beta, gravity_compensation, f_prev)
+        else:
+            from shifu_amd.utils.torch_utils import balance_wrench, foot_force_qp
+            kpl, kpa = self._gain3(kp_lin), self._gain3(kp_ang)
+            gains = torch.cat([kpl, 2.0 * torch.sqrt(kpl) if kd_lin is None else self._gain3(kd_lin),
+                               kpa, 2.0 * torch.sqrt(kpa) if kd_ang is None else self._gain3(kd_ang)])
+            tg[:, :3], tg[:, 3:7] = base_pos, base_quat
+            tg[:, 7:10] = 0.0 if base_lin_vel is None else base_lin_vel
+            tg[:, 10:13] = 0.0 if base_ang_vel is None else base_ang_vel
+            S = torch.as_tensor(weights, dtype=torch.float32, device=self.device).reshape(6)
+            forces, efforts = foot_force_qp(jf, root[:, :3], feet, balance_wrench(M, h, root, tg, gains),
+                                            self.stance_from_contacts() if stance is None else stance,
+                                            self._contact_friction() if mu is None else mu, S, alpha, beta, f_prev if beta > 0 else None,
+                                            fz_min, float("inf") if fz_max is None else float(fz_max), 100,
+                                            h if gravity_compensation else None, self.torque_limits)
+        self._bal_forces = forces
+        return efforts, forces
+
+    def apply_balance_control(self, base_pos, base_quat, swing_targets=None, swing_gains=None, **kw):
+        """decimation x {refresh the state, Jacobian, mass-matrix and bias tensors, balance_control, set the efforts, simulate,
+        refresh the dof state}.  swing_targets (n, num_ee, 3), positions in the base frame: the efforts of
+        foot_impedance_control(swing_targets, **swing_gains) without its bias are added on the dofs of the feet that are not in
+        stance (one more launch).  The asset must be in DOF_MODE_EFFORT.  Returns the last (efforts, forces)."""
+        if self.asset_options.default_dof_drive_mode != gymapi.DOF_MODE_EFFORT:
+            raise RuntimeError("apply_balance_control: the asset's default_dof_drive_mode must be DOF_MODE_EFFORT")
+        self.mass_matrix, self.bias_forces      # acquired before the first refresh
+        efforts = forces = None
+        for _ in range(int(self.env.decimation)):
+            self.gym.refresh_all_state_tensors(self.sim)
+            self.gym.refresh_mass_matrix_tensors(self.sim)
+            stance = kw.get("stance")
+            if stance is None:
+                stance = self.stance_from_contacts()
+            efforts, forces = self.balance_control(base_pos, base_quat, **dict(kw, stance=stance))
+            if swing_targets is not None:
+                swing = self.foot_impedance_control(swing_targets, gravity_compensation=False, **(swing_gains or {}))
+                dofs = ((1.0 - stance.to(torch.float32)) @ self._foot_dof_mask()).clamp(max=1.0)
+                efforts = torch.maximum(torch.minimum(efforts + dofs * swing, self._effort_cap()), -self._effort_cap())
+            self.gym.set_dof_actuation_force_tensor(self.sim, gymtorch.unwrap_tensor(efforts))
+            self.gym.simulate(self.sim)
+            if self.device == 'cpu':
+                self.gym.fetch_results(self.sim, True)
+            self.gym.refresh_dof_state_tensor(self.sim)
+        return efforts, forces
+
+    def _effort_cap(self):
+        lim = self.torque_limits
+        return torch.where(lim > 0, lim, torch.full_like(lim, float("inf")))

@@ -83,3 +83,114 @@ def foot_impedance_control(j_feet, dof_vel, root_pos, root_quat, foot_pos, targe
         lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
         tau = torch.maximum(torch.minimum(tau, lim), -lim)
     return tau
+
+
+def balance_wrench(mass_matrix, bias, root_state, base_target, gains12):
+    """The base wrench (n, 6) the balance controller asks the feet for: w = M[0:6, 0:6] (a_lin, a_ang) + h[0:6] with
+    a_lin = kp_lin (p* - p) + kd_lin (v* - v), a_ang = kp_ang orientation_error(q*, q) + kd_ang (omega* - omega); root_state
+    and base_target rows (pos, quat xyzw, v, omega), gains12 = (kp_lin, kd_lin, kp_ang, kd_ang).  The coupling of the dof
+    accelerations, M[0:6, 6:] qdd, is neglected."""
+    g = gains12.reshape(4, 3)
+    a = torch.cat([g[0] * (base_target[:, :3] - root_state[:, :3]) + g[1] * (base_target[:, 7:10] - root_state[:, 7:10]),
+                   g[2] * orientation_error(base_target[:, 3:7], root_state[:, 3:7])
+                   + g[3] * (base_target[:, 10:13] - root_state[:, 10:13])], -1)
+    return (mass_matrix[:, :6, :6] @ a.unsqueeze(-1)).squeeze(-1) + bias[:, :6]
+
+
+def _ldlt_inverse(K):
+    """K^-1 of a batch of symmetric positive definite matrices (n, N, N) by K = L D L^T, column by column as csrc/shf_qp.hip
+    factors it, then the solves against the identity; elementwise and matmul expressions only.  (torch's batched Cholesky
+    solver is not used: in float32 on the GPU it returned wrong solutions inside this loop at 4096 envs.)"""
+    n, N, _ = K.shape
+    L = torch.zeros_like(K)
+    D = torch.zeros(n, N, dtype=K.dtype, device=K.device)
+    for j in range(N):
+        D[:, j] = K[:, j, j] - (L[:, j, :j] * L[:, j, :j] * D[:, :j]).sum(-1)
+        if j + 1 < N:
+            L[:, j + 1:, j] = (K[:, j + 1:, j] - (L[:, j + 1:, :j] * L[:, j:j + 1, :j] * D[:, None, :j]).sum(-1)) / D[:, j:j + 1]
+    X = torch.eye(N, dtype=K.dtype, device=K.device).repeat(n, 1, 1)
+    for i in range(1, N):
+        X[:, i] = X[:, i] - (L[:, i, :i].unsqueeze(1) @ X[:, :i]).squeeze(1)
+    X = X / D.unsqueeze(-1)
+    for i in range(N - 2, -1, -1):
+        X[:, i] = X[:, i] - (L[:, i + 1:, i].unsqueeze(1) @ X[:, i + 1:]).squeeze(1)
+    return X
+
+
+def foot_force_qp(j_feet, root_pos, foot_pos, wrench, stance, mu, weights6, alpha=1e-2, beta=0.0, f_prev=None, fz_min=5.0,
+                  fz_max=float("inf"), iters=100, bias=None, effort_limit=None):
+    """Foot-force distribution of the balance controller: (forces (n, F, 3), efforts (n, nd)).  Per env, with r_f = p_foot_f -
+    p_root and G = [[I .. I], [[r_1]x .. [r_F]x]], minimise 1/2 (G f - w)^T S (G f - w) + 1/2 alpha |f|^2 + 1/2 beta |f - f_prev|^2
+    subject to fz_min <= f_z <= fz_max, |f_x|, |f_y| <= mu f_z on the stance feet and f = 0 on the others, by `iters` sweeps of
+    ADMM (rho = sqrt((alpha + beta) m), sigma = 1e-6 m, m the mean diagonal of the stance feet's Hessian block; relaxation
+    1.6) on K^-1 from one LDL^T, then the exact per-foot clamp; efforts = -sum_f Jl_f^T f_f (+ bias[:, 6:]), clamped to +-effort_limit last.  The
+    algorithm of csrc/shf_qp.hip's shf_foot_force_qp in torch (its CPU fallback); tests/qp_ref.py holds the NumPy twin."""
+    n, F = stance.shape
+    N, dt, dev = 3 * F, j_feet.dtype, j_feet.device
+    s = stance.to(dt)
+    st = stance.to(torch.bool)
+    mu = torch.as_tensor(mu, dtype=dt, device=dev).expand(n).clamp(min=0.0)
+    S = weights6.to(dt)
+    be = float(beta) if f_prev is not None else 0.0
+    ab = float(alpha) + be
+    r = (foot_pos - root_pos.unsqueeze(1)) * s.unsqueeze(-1)
+    G = torch.zeros(n, 6, F, 3, dtype=dt, device=dev)
+    for k in range(3):
+        G[:, k, :, k] = s
+    G[:, 3, :, 1], G[:, 3, :, 2] = -r[..., 2], r[..., 1]
+    G[:, 4, :, 0], G[:, 4, :, 2] = r[..., 2], -r[..., 0]
+    G[:, 5, :, 0], G[:, 5, :, 1] = -r[..., 1], r[..., 0]
+    G = G.reshape(n, 6, N)
+    eye = torch.eye(N, dtype=dt, device=dev)
+    P = torch.transpose(G, 1, 2) @ (S.view(1, 6, 1) * G) + ab * eye
+    q = -(torch.transpose(G, 1, 2) @ (S * wrench).unsqueeze(-1)).squeeze(-1)
+    if f_prev is not None:
+        q = q - be * (f_prev * s.unsqueeze(-1)).reshape(n, N)
+    sv = s.repeat_interleave(3, 1)
+    ns = s.sum(1)
+    mean = (torch.diagonal(P, dim1=1, dim2=2) * sv).sum(1) / (3.0 * ns.clamp(min=1.0))
+    mean = torch.where(ns > 0, mean, torch.ones_like(mean))
+    rho, sigma = torch.sqrt(ab * mean).view(n, 1), (1e-6 * mean).view(n, 1)
+    # the rows of one foot: f_z, mu f_z - f_x, mu f_z + f_x, mu f_z - f_y, mu f_z + f_y
+    Af = torch.zeros(n, 5, 3, dtype=dt, device=dev)
+    Af[:, :, 2] = mu.view(n, 1)
+    Af[:, 0, 2] = 1.0
+    Af[:, 1, 0], Af[:, 2, 0], Af[:, 3, 1], Af[:, 4, 1] = -1.0, 1.0, -1.0, 1.0
+    A = torch.zeros(n, F, 5, F, 3, dtype=dt, device=dev)
+    for f in range(F):
+        A[:, f, :, f, :] = Af
+    A = A.reshape(n, 5 * F, N)
+    At = torch.transpose(A, 1, 2)
+    K = P + sigma.unsqueeze(-1) * eye + rho.unsqueeze(-1) * (At @ A)
+    Kinv = _ldlt_inverse(K)
+    inf = float("inf")
+    lo = torch.zeros(n, F, 5, dtype=dt, device=dev)
+    hi = torch.zeros(n, F, 5, dtype=dt, device=dev)
+    lo[:, :, 0] = fz_min
+    hi[:, :, 0], hi[:, :, 1:] = fz_max, inf
+    lo = torch.where(st.unsqueeze(-1), lo, torch.zeros_like(lo)).reshape(n, 5 * F)
+    hi = torch.where(st.unsqueeze(-1), hi, torch.zeros_like(hi)).reshape(n, 5 * F)
+    x = torch.zeros(n, N, dtype=dt, device=dev)
+    z = torch.zeros(n, 5 * F, dtype=dt, device=dev)
+    y = torch.zeros(n, 5 * F, dtype=dt, device=dev)
+    for _ in range(int(iters)):
+        b = sigma * x - q + (At @ (rho * z - y).unsqueeze(-1)).squeeze(-1)
+        xt = Kinv @ b.unsqueeze(-1)
+        zt = (A @ xt).squeeze(-1)
+        x = 1.6 * xt.squeeze(-1) + (1.0 - 1.6) * x
+        zr = 1.6 * zt + (1.0 - 1.6) * z
+        zn = torch.minimum(torch.maximum(zr + y / rho, lo), hi)
+        y = y + rho * (zr - zn)
+        z = zn
+    x = x.view(n, F, 3)
+    fz = x[..., 2].clamp(fz_min, fz_max)
+    bnd = mu.view(n, 1) * fz
+    forces = torch.stack([torch.minimum(torch.maximum(x[..., 0], -bnd), bnd), torch.minimum(torch.maximum(x[..., 1], -bnd), bnd), fz], -1)
+    forces = torch.where(st.unsqueeze(-1), forces, torch.zeros_like(forces))
+    tau = -(torch.transpose(j_feet[:, :, :3, 6:], 2, 3) @ forces.unsqueeze(-1)).squeeze(-1).sum(1)
+    if bias is not None:
+        tau = tau + bias[:, 6:]
+    if effort_limit is not None:
+        lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
+        tau = torch.maximum(torch.minimum(tau, lim), -lim)
+    return forces, tau

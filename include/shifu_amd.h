@@ -975,6 +975,49 @@ int shf_foot_force_qp(const float* j_feet, int64_t j_env_stride, int64_t j_foot_
                       const float* f_prev_or_null, float fz_min, float fz_max, int32_t iters, const float* bias_or_null,
                       const float* effort_limit_or_null, int32_t n, int32_t num_feet, int32_t num_dof, float* forces_out,
                       float* efforts_out, void* stream);
+/* LeggedRobot.locomotion_control's planner: gait clock, foothold planner, swing trajectory and base-target integrator for
+ * every env in one launch, one thread per env (csrc/shf_gait.hip, whose header states the algorithm step by step).  One call is
+ * one tick of an integer gait clock: period_ticks P, and per foot (HOST arrays of num_feet <= 4 ints) offset_ticks in 0..P-1
+ * and stance_ticks in 1..P (= P: always standing); foot f is scheduled to stand while (tick + offset_f) mod P < stance_ticks_f.
+ * Per-env state, read and written in place, owned by the caller: tick (n) int32, sched (n, num_feet) uint8 (last call's
+ * schedule), anchor (n, num_feet, 3) world (the lift-off point of a swinging foot, the planned foothold of a standing one),
+ * target (n, 13) (the base target, shf_foot_force_qp's base_target layout), yaw (n) (the target's heading).  Inputs: the
+ * root's 13-float row at root_pose + e * root_env_stride; foot f's world origin at foot_pos + e * foot_env_stride + f *
+ * foot_stride; its contact force z at contact_z + e * contact_env_stride + f * contact_foot_stride, or NULL; command (n, 3) =
+ * (vx, vy, yaw rate) in the target's heading frame; nominal (num_feet, 3), the feet in the base frame at the default pose;
+ * reset (n) uint8 or NULL (an env with reset != 0 restarts its clock, anchors its feet under where they are, late_depth below touchdown_z, and puts the base target
+ * over the base, heading as the base).  The base target advances by the commanded velocity (kept within `leash` of the base,
+ * +inf: never pulled back); a swinging foot moves from its anchor to foothold = hip + clamp_norm(v_des T_stance / 2 + k_fb
+ * (v - v_cmd), max_step) by a cubic blend in xy and down to touchdown_z with a parabola of height `apex` on top; a foot
+ * scheduled to stand that does not touch is pushed to its anchor, late_depth below touchdown_z.  Outputs: stance_out (n,
+ * num_feet) uint8 = scheduled and contact z > contact_threshold (no contact tensor: the schedule alone), swing_target_out (n,
+ * num_feet, 3) in the base frame (what shf_foot_impedance takes; a standing, touching foot gets its own position), phase_out
+ * (n, num_feet) in [0, 1).  Refused with a message: num_feet outside 1..4, period_ticks < 1, a stance_ticks outside 1..P, an
+ * offset_ticks outside 0..P-1, dt <= 0, max_step < 0, a null required tensor.  Additive: no new SHF_ABI_VERSION. */
+typedef struct ShfGaitParams {
+  float dt;                 /* seconds per tick */
+  float height;             /* the base target's z */
+  float apex;               /* swing height above the chord from lift-off to touchdown */
+  float touchdown_z;        /* world z of a foot's origin at the end of its swing */
+  float late_depth;         /* how far below touchdown_z a late foot is pushed */
+  float k_fb;               /* foothold feedback on the velocity error (s) */
+  float max_step;           /* bound on the foothold's distance from the hip */
+  float leash;              /* bound on the base target's horizontal distance from the base (+inf: none) */
+  float contact_threshold;  /* newtons of contact force z above which a foot touches */
+} ShfGaitParams;
+int shf_gait_plan(const float* root_pose, int64_t root_env_stride, const float* foot_pos, int64_t foot_env_stride,
+                  int64_t foot_stride, const float* contact_z_or_null, int64_t contact_env_stride, int64_t contact_foot_stride,
+                  const float* command, const float* nominal, const uint8_t* reset_or_null, int32_t period_ticks,
+                  const int32_t* offset_ticks, const int32_t* stance_ticks, ShfGaitParams params, int32_t* tick, uint8_t* sched,
+                  float* anchor, float* target, float* yaw, int32_t n, int32_t num_feet, uint8_t* stance_out,
+                  float* swing_target_out, float* phase_out, void* stream);
+/* Merges the stance efforts of shf_foot_force_qp with the swing efforts of shf_foot_impedance, one thread per env:
+ *   efforts_out[e, d] = clamp(stance_efforts[e, d] + m swing_efforts[e, d], +-effort_limit[d]),
+ * m = 1 if dof d lies on the chain of a foot with stance[e, f] == 0 (chain_mask (num_feet, num_dof) uint8), else 0; limit
+ * entries <= 0 or a NULL limit: no clamp.  Contiguous tensors; num_feet <= 32.  Additive: no new SHF_ABI_VERSION. */
+int shf_leg_effort_mix(const float* stance_efforts, const float* swing_efforts, const uint8_t* stance, const uint8_t* chain_mask,
+                       const float* effort_limit_or_null, int32_t n, int32_t num_feet, int32_t num_dof, float* efforts_out,
+                       void* stream);
 /* ShifuVecEnv.compute_reward's accumulation (env.py:180-185): rew = terms[0] + terms[1] + ... in that order,
  * sums[k] += terms[k]; HOST arrays of num_keys <= 16 device pointers to (num_envs) fp32 tensors. */
 int shf_reward_accumulate(const float* const* terms, float* const* sums, int32_t num_keys, int64_t num_envs, float* rew,

@@ -122,6 +122,11 @@ class ShfCamera(C.Structure):
                 ("depth_negative", i32)]
 
 
+class ShfGaitParams(C.Structure):      # shf_gait_plan's scalars, passed by value (csrc/shf_gait.hip)
+    _fields_ = [("dt", f32), ("height", f32), ("apex", f32), ("touchdown_z", f32), ("late_depth", f32), ("k_fb", f32),
+                ("max_step", f32), ("leash", f32), ("contact_threshold", f32)]
+
+
 class ShfA1TaskParams(C.Structure):
     _fields_ = [
         ("decimation", i32), ("extra_substep", i32), ("num_history", i32), ("num_height_points", i32),

@@ -98,6 +98,13 @@ _SIGS = {
     # effort_limit, n, num_feet, num_dof, forces_out, efforts_out, stream (csrc/shf_qp.hip)
     "shf_foot_force_qp": ([vp, i64, i64, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, C.c_float, C.c_float, vp,
                            C.c_float, C.c_float, i32, vp, vp, i32, i32, i32, vp, vp, vp], i32),
+    # root_pose, root_env_stride, foot_pos, foot_env_stride, foot_stride, contact_z, contact_env_stride, contact_foot_stride,
+    # command, nominal, reset, period_ticks, offset_ticks (host), stance_ticks (host), params (by value), tick, sched, anchor,
+    # target, yaw, n, num_feet, stance_out, swing_target_out, phase_out, stream (csrc/shf_gait.hip)
+    "shf_gait_plan": ([vp, i64, vp, i64, i64, vp, i64, i64, vp, vp, vp, i32, C.POINTER(i32), C.POINTER(i32), _abi.ShfGaitParams,
+                       vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp], i32),
+    # stance_efforts, swing_efforts, stance, chain_mask, effort_limit, n, num_feet, num_dof, efforts_out, stream
+    "shf_leg_effort_mix": ([vp, vp, vp, vp, vp, i32, i32, i32, vp, vp], i32),
     "shf_reward_accumulate": ([C.POINTER(vp), C.POINTER(vp), i32, i64, vp, vp], i32),
     "shf_gae": ([vp, vp, vp, vp, i32, i64, C.c_float, C.c_float, vp, vp], i32),
     "shf_ppo_loss_workspace": ([i64, i32, C.POINTER(i64)], i32),

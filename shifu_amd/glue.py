@@ -274,3 +274,110 @@ def balance_control(j_feet, root_state, foot_pos, contact_z, shape_friction, gro
                                     f_prev if beta > 0 else None, fz_min, float("inf") if fz_max is None else float(fz_max), QP_ITERS,
                                     bias if gravity_compensation else None, effort_limit)
     return efforts, forces
+
+
+# -- locomotion: gait plan -> foot-force QP -> swing spring -> merge (csrc/shf_gait.hip) ---------------------------------------
+def gait_params(dt, height, touchdown_z, gait):
+    """The by-value scalars of shf_gait_plan from a units.gait.Gait."""
+    from ._abi import ShfGaitParams
+    return ShfGaitParams(float(dt), float(height), gait.apex, float(touchdown_z), gait.late_depth, gait.k_fb, gait.max_step, gait.leash,
+                         gait.contact_threshold)
+
+
+def gait_plan(state, root_state, foot_pos, contact_z, command, nominal, reset, ticks, params):
+    """One tick of the gait planner in one launch (shf_gait_plan): (stance (n, F) uint8, swing_target (n, F, 3) base frame,
+    phase (n, F)).  state: a units.gait.GaitState, updated in place.  root_state (n, >= 13) rows and foot_pos (n, F, 3): views
+    as for foot_impedance; contact_z (n, F) any strides, or None: the schedule alone decides the stance; command (n, 3) = (vx,
+    vy, yaw rate) in the target's heading frame; nominal (F, 3): the feet in the base frame at the default pose; reset (n)
+    uint8 / bool or None; ticks = (period_ticks, offset_ticks, stance_ticks) of Gait.ticks(dt); params: gait_params(...)."""
+    n, F = foot_pos.shape[:2]
+    P, offsets, stance_ticks = ticks
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in (root_state, foot_pos, command, nominal)), "float32 CUDA tensors expected"
+    assert root_state.shape[0] == n and root_state.shape[1] >= 13 and root_state.stride(1) == 1
+    assert foot_pos.shape == (n, F, 3) and foot_pos.stride(2) == 1
+    assert contact_z is None or (tuple(contact_z.shape) == (n, F) and contact_z.is_cuda and contact_z.dtype == torch.float32)
+    assert tuple(command.shape) == (n, 3) and tuple(nominal.shape) == (F, 3)
+    assert len(offsets) == F and len(stance_ticks) == F
+    assert reset is None or (reset.numel() == n and reset.dtype in (torch.uint8, torch.bool) and reset.is_cuda)
+    tick, sched, anchor, target, yaw = state.tensors()
+    assert tick.dtype == torch.int32 and sched.dtype == torch.uint8 and tuple(sched.shape) == (n, F) and tuple(anchor.shape) == (n, F, 3)
+    assert tuple(target.shape) == (n, 13) and yaw.numel() == n and all(t.is_cuda and t.is_contiguous() for t in state.tensors())
+    dev = foot_pos.device
+    cmd, nom = command.contiguous(), nominal.contiguous()
+    rs = None if reset is None else reset.contiguous().view(torch.uint8)
+    stance = torch.empty(n, F, dtype=torch.uint8, device=dev)
+    swing = torch.empty(n, F, 3, dtype=torch.float32, device=dev)
+    phase = torch.empty(n, F, dtype=torch.float32, device=dev)
+    ia = C.c_int32 * F
+    with torch.cuda.device(dev):
+        check(lib().shf_gait_plan(_vp(root_state.data_ptr()), root_state.stride(0), _vp(foot_pos.data_ptr()), foot_pos.stride(0),
+                                  foot_pos.stride(1), None if contact_z is None else _vp(contact_z.data_ptr()),
+                                  0 if contact_z is None else contact_z.stride(0), 0 if contact_z is None else contact_z.stride(1),
+                                  _f32c(cmd), _f32c(nom), None if rs is None else _vp(rs.data_ptr()), int(P),
+                                  ia(*[int(o) for o in offsets]), ia(*[int(s) for s in stance_ticks]), params, _vp(tick.data_ptr()),
+                                  _vp(sched.data_ptr()), _f32c(anchor), _f32c(target), _f32c(yaw), n, F, _vp(stance.data_ptr()),
+                                  _f32c(swing), _f32c(phase), _stream(dev)))
+    return stance, swing, phase
+
+
+def leg_effort_mix(stance_efforts, swing_efforts, stance, chain_mask, effort_limit=None):
+    """clamp(stance_efforts + m swing_efforts, +-effort_limit) in one launch (shf_leg_effort_mix): m = 1 on the dofs of the feet
+    that are not in stance (chain_mask (F, nd) uint8: the dofs on each foot's chain), 0 elsewhere; limit entries <= 0: none."""
+    n, nd = stance_efforts.shape
+    F = stance.shape[1]
+    assert tuple(swing_efforts.shape) == (n, nd) and tuple(stance.shape) == (n, F) and tuple(chain_mask.shape) == (F, nd)
+    assert stance.dtype in (torch.uint8, torch.bool) and chain_mask.dtype == torch.uint8 and stance.is_cuda and chain_mask.is_cuda
+    assert effort_limit is None or effort_limit.numel() == nd
+    a, b = stance_efforts.contiguous(), swing_efforts.contiguous()
+    st, cm = stance.contiguous().view(torch.uint8), chain_mask.contiguous()
+    lim = None if effort_limit is None else effort_limit.contiguous()
+    out = torch.empty(n, nd, device=a.device, dtype=torch.float32)
+    with torch.cuda.device(a.device):
+        check(lib().shf_leg_effort_mix(_f32c(a), _f32c(b), _vp(st.data_ptr()), _vp(cm.data_ptr()), None if lim is None else _f32c(lim),
+                                       n, F, nd, _f32c(out), _stream(a.device)))
+    return out
+
+
+_CONSTANTS = {}
+
+
+def _constant(values, device):
+    """A small float32 device tensor of python numbers, made once per value and device."""
+    key = (str(device), tuple(float(v) for v in values))
+    if key not in _CONSTANTS:
+        _CONSTANTS[key] = torch.tensor(key[1], dtype=torch.float32, device=device)
+    return _CONSTANTS[key]
+
+
+def _vec3(g):
+    g = [float(x) for x in (g.reshape(-1).tolist() if torch.is_tensor(g) else (g if hasattr(g, "__len__") else [g]))]
+    return g * 3 if len(g) == 1 else g
+
+
+def locomotion_control(j_feet, dof_state, root_state, foot_pos, contact_z, shape_friction, ground_friction, mass_matrix, bias,
+                       effort_limit, chain_mask, nominal, state, command, gait, dt, height=0.30, touchdown_z=0.01, swing_kp=400.,
+                       swing_kd=10., reset=None, kp_lin=100., kd_lin=None, kp_ang=400., kd_ang=None, mu=None, fz_min=5., fz_max=None,
+                       weights=(1, 1, 1, 10, 10, 10), alpha=1e-2, gravity_compensation=True):
+    """What LeggedRobot.locomotion_control and FusedA1Env.locomotion_control share, four launches: the gait plan (base target
+    and stance from `gait`'s schedule gated by contact_z, swing targets), foot_force_qp on that target and stance (as
+    balance_control: kd None = 2 sqrt(kp), mu None = (shape_friction + ground_friction) / 2), foot_impedance towards the swing
+    targets with the explicit swing_kp / swing_kd and no bias, and leg_effort_mix.  state: the GaitState, advanced by one tick;
+    reset None = the state's pending resets.  Returns (efforts (n, nd), forces (n, F, 3), stance (n, F), swing_targets (n, F, 3))."""
+    import math
+    dev = j_feet.device
+    if reset is None:
+        reset = state.take_pending()
+    stance, swing_t, _ = gait_plan(state, root_state, foot_pos, contact_z, command, nominal, reset, gait.ticks(dt),
+                                   gait_params(dt, height, touchdown_z, gait))
+    kpl, kpa = _vec3(kp_lin), _vec3(kp_ang)
+    kdl = [2.0 * math.sqrt(k) for k in kpl] if kd_lin is None else _vec3(kd_lin)
+    kda = [2.0 * math.sqrt(k) for k in kpa] if kd_ang is None else _vec3(kd_ang)
+    gains = _constant(kpl + kdl + kpa + kda, dev)
+    if mu is None:
+        mu = 0.5 * (shape_friction + float(ground_friction))
+    forces, tau_st = foot_force_qp(j_feet, root_state, foot_pos, stance, mu, _constant(weights, dev), None, mass_matrix, bias,
+                                   state.target, gains, alpha, 0.0, None, fz_min, float("inf") if fz_max is None else float(fz_max),
+                                   QP_ITERS, bias if gravity_compensation else None, effort_limit)
+    tau_sw = foot_impedance(j_feet, dof_state, root_state, foot_pos, swing_t, _constant(_vec3(swing_kp), dev),
+                            _constant(_vec3(swing_kd), dev), None, effort_limit)
+    return leg_effort_mix(tau_st, tau_sw, stance, chain_mask, effort_limit), forces, stance, swing_t

@@ -283,6 +283,37 @@ class FusedA1Env(FusedCameraHost):
         self._bal_forces = forces
         return efforts, forces
 
+    def locomotion_control(self, command, gait=None, swing_kp=400., swing_kd=10., height=0.30, touchdown_z=None, reset=None,
+                           **balance_kw):
+        """(efforts (n, nd), forces (n, 4, 3), stance (n, 4) uint8, swing_targets (n, 4, 3)) of LeggedRobot.locomotion_control
+        (csrc/shf_gait.hip: gait plan, foot-force QP, swing spring-damper and the merge, four launches) from
+        whole_body_dynamics()'s tensors and the root, body, dof and contact tensors as the last step left them; one call is one
+        gait tick of the simulation step.  command (n, 3) = (vx, vy, yaw rate); gait None = Gait.trot().  The gait state
+        (`gait_state`, a units.gait.GaitState) is allocated once; reset (n) uint8 restarts those envs' gait, and the first
+        call restarts every env's.  Not part of the fused step."""
+        from .. import glue
+        from ..units import gait as G
+        w = self.whole_body_dynamics()
+        n, nb, m = self.num_envs, self.cm.blob.nb, self.cm.blob
+        fb = [b for b, name in enumerate(self.cm.body_names) if name.endswith("_foot")]     # evenly spaced (foot_jacobians)
+        if getattr(self, "gait_state", None) is None:
+            self.gait_state = G.GaitState(n, 4, self.device)
+            self._gait_default = G.Gait.trot()
+            self._gait_chain = G.chain_mask(m, fb).to(self.device)
+            q0 = self.task_params.default_dof_pos
+            self._gait_nominal = torch.tensor(G.nominal_foot_positions(m, [float(q0[d]) for d in range(m.nd)], fb),
+                                              dtype=torch.float32, device=self.device)
+            self._gait_radius = G.foot_radius(m, fb)
+            self._gait_limit = torch.tensor([m.effort[d] for d in range(m.nd)], device=self.device)
+        rows = slice(fb[0], fb[-1] + 1, fb[1] - fb[0])
+        command = torch.as_tensor(command, dtype=torch.float32, device=self.device).expand(n, 3)
+        return glue.locomotion_control(
+            self.foot_jacobians, self.dof_state.view(n, m.nd, 2), self.root_state.view(n, 13), self.body_state.view(n, nb, 13)[:, rows, :3],
+            self.contact_state.view(n, nb, 3)[:, rows, 2], self.sim.tensors[_abi.T_FRICTION], self.sim.terrain.friction,
+            w["mass_matrix"], w["bias"], self._gait_limit, self._gait_chain, self._gait_nominal, self.gait_state, command,
+            self._gait_default if gait is None else gait, float(self.sim_params.dt), height,
+            self._gait_radius - 0.01 if touchdown_z is None else touchdown_z, swing_kp, swing_kd, reset, **balance_kw)
+
     def state_dict(self):
         """Checkpoint of the whole simulation + task state (shifu_amd/checkpoint.py)."""
         from ..checkpoint import env_state_dict

@@ -431,3 +431,109 @@ class LeggedRobot(ArmRobot):
     def _effort_cap(self):
         lim = self.torque_limits
         return torch.where(lim > 0, lim, torch.full_like(lim, float("inf")))
+
+    # -- locomotion: gait schedule, footholds and swing trajectories on top of the balance controller (not in the reference;
+    # SHIFU_AMD_FLOATING_DYNAMICS=1) ------------------------------------------------------------------------------------------
+    @property
+    def nominal_foot_positions(self):
+        """(num_ee, 3): the end bodies' origins in the base frame at the default dof positions (forward kinematics)."""
+        if getattr(self, "_gait_nominal", None) is None:
+            from .gait import nominal_foot_positions
+            q = self.default_dof_pos.reshape(-1)[:self.num_dof].detach().cpu().numpy()
+            p = nominal_foot_positions(self.sim.backend.model, q, self._ee_list)
+            self._gait_nominal = torch.tensor(p, dtype=torch.float32, device=self.device)
+        return self._gait_nominal
+
+    def _foot_radius(self):
+        from .gait import foot_radius
+        return foot_radius(self.sim.backend.model, self._ee_list)
+
+    def _gait_state(self):
+        if getattr(self, "_gait", None) is None:
+            from .gait import GaitState
+            self._gait = GaitState(self.env.num_envs, self.num_ee, self.device)
+        return self._gait
+
+    def reset_gait(self, env_ids=None):
+        """The next locomotion_control restarts these envs' gait (None: every env's): clock at 0, every foot scheduled to stand,
+        the base target over the base and heading as the base does."""
+        self._gait_state().reset(env_ids)
+
+    def locomotion_control(self, command, gait=None, swing_kp=400., swing_kd=10., height=0.30, touchdown_z=None, **balance_kw):
+        """One tick of a model-based walking controller: (efforts (num_envs, nd), forces (num_envs, num_ee, 3), stance
+        (num_envs, num_ee) uint8, swing_targets (num_envs, num_ee, 3) in the base frame).  command (n, 3) = (vx, vy, yaw
+        rate) in the heading frame of the base target.  The gait plan (csrc/shf_gait.hip) advances the base target at the
+        commanded velocity at `height`, schedules the feet by `gait` (units.gait.Gait; None = Gait.trot()) gated by the
+        contact forces, and gives every foot a target; the stance feet get balance_control's forces towards the base target
+        (**balance_kw: its gains and bounds), the legs of the others a Cartesian spring-damper swing_kp / swing_kd (an explicit,
+        light damper: at 2 sqrt(kp) the feet lag their targets) without bias; one launch merges the two and clamps to the
+        effort limits.  One call is one tick of dt = the simulation step.  touchdown_z None = 1 cm below the resting height of a
+        foot's origin on the plane z = 0.  A change of `gait` restarts the clock; reset_gait() restarts everything.  From the
+        tensors as last refreshed."""
+        from .gait import Gait
+        h = self.bias_forces                     # (refused with "fixed base" unless SHIFU_AMD_FLOATING_DYNAMICS=1)
+        M = self.mass_matrix
+        n = self.env.num_envs
+        if gait is None:
+            gait = getattr(self, "_gait_default", None) or Gait.trot()
+            self._gait_default = gait
+        st = self._gait_state()
+        if getattr(self, "_gait_last", None) is not gait:
+            st.tick.zero_()
+            self._gait_last = gait
+        if touchdown_z is None:
+            touchdown_z = self._foot_radius() - 0.01
+        dt = float(self.env.sim_params.dt)
+        jf = self.foot_jacobians
+        root = self.env.root_state.view(n, -1, 13)[:, 0]
+        feet = self._end_rows(self.env.body_state.view(n, -1, 13))[..., :3]
+        cz = self._end_rows(self.contact_forces)[..., 2]
+        if getattr(self, "_gait_chain", None) is None:
+            self._gait_chain = self._foot_dof_mask().to(torch.uint8)
+        command = torch.as_tensor(command, dtype=torch.float32, device=self.device).expand(n, 3)
+        if jf.is_cuda and jf.dtype == torch.float32:
+            from shifu_amd import _abi, glue
+            be = self.sim.backend
+            efforts, forces, stance, swing = glue.locomotion_control(
+                jf, self.env.dof_state.view(n, self.num_dof, 2), root, feet, cz, be.tensors[_abi.T_FRICTION], be.terrain.friction, M, h,
+                self.torque_limits.contiguous(), self._gait_chain, self.nominal_foot_positions, st, command, gait, dt, height,
+                touchdown_z, swing_kp, swing_kd, **balance_kw)
+        else:
+            from shifu_amd.utils import torch_utils as TU
+            kw = dict(kp_lin=100., kd_lin=None, kp_ang=400., kd_ang=None, mu=None, fz_min=5., fz_max=None, weights=(1, 1, 1, 10, 10, 10),
+                      alpha=1e-2, gravity_compensation=True)
+            kw.update(balance_kw)
+            stance, swing, _, _ = TU.gait_plan(st, root, feet, cz, command, self.nominal_foot_positions, st.take_pending(), gait.ticks(dt),
+                                               dt, height, gait.apex, touchdown_z, gait.late_depth, gait.k_fb, gait.max_step, gait.leash,
+                                               gait.contact_threshold)
+            kpl, kpa = self._gain3(kw["kp_lin"]), self._gain3(kw["kp_ang"])
+            gains = torch.cat([kpl, 2.0 * torch.sqrt(kpl) if kw["kd_lin"] is None else self._gain3(kw["kd_lin"]),
+                               kpa, 2.0 * torch.sqrt(kpa) if kw["kd_ang"] is None else self._gain3(kw["kd_ang"])])
+            S = torch.as_tensor(kw["weights"], dtype=torch.float32, device=self.device).reshape(6)
+            forces, tau_st = TU.foot_force_qp(jf, root[:, :3], feet, TU.balance_wrench(M, h, root, st.target, gains), stance,
+                                              self._contact_friction() if kw["mu"] is None else kw["mu"], S, kw["alpha"], 0.0, None,
+                                              kw["fz_min"], float("inf") if kw["fz_max"] is None else float(kw["fz_max"]), 100,
+                                              h if kw["gravity_compensation"] else None, self.torque_limits)
+            tau_sw = TU.foot_impedance_control(jf, self.dof_vel, root[:, :3], root[:, 3:7], feet, swing, self._gain3(swing_kp),
+                                               self._gain3(swing_kd), None, self.torque_limits)
+            efforts = TU.leg_effort_mix(tau_st, tau_sw, stance, self._gait_chain, self.torque_limits)
+        return efforts, forces, stance, swing
+
+    def apply_locomotion_control(self, command, **kw):
+        """decimation x {refresh the state, Jacobian, mass-matrix and bias tensors, locomotion_control (one gait tick), set the
+        efforts, simulate, refresh the dof state}.  The asset must be in DOF_MODE_EFFORT.  Returns the last (efforts, forces,
+        stance, swing_targets)."""
+        if self.asset_options.default_dof_drive_mode != gymapi.DOF_MODE_EFFORT:
+            raise RuntimeError("apply_locomotion_control: the asset's default_dof_drive_mode must be DOF_MODE_EFFORT")
+        self.mass_matrix, self.bias_forces      # acquired before the first refresh
+        out = None
+        for _ in range(int(self.env.decimation)):
+            self.gym.refresh_all_state_tensors(self.sim)
+            self.gym.refresh_mass_matrix_tensors(self.sim)
+            out = self.locomotion_control(command, **kw)
+            self.gym.set_dof_actuation_force_tensor(self.sim, gymtorch.unwrap_tensor(out[0]))
+            self.gym.simulate(self.sim)
+            if self.device == 'cpu':
+                self.gym.fetch_results(self.sim, True)
+            self.gym.refresh_dof_state_tensor(self.sim)
+        return out

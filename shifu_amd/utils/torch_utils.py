@@ -194,3 +194,101 @@ def foot_force_qp(j_feet, root_pos, foot_pos, wrench, stance, mu, weights6, alph
         lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
         tau = torch.maximum(torch.minimum(tau, lim), -lim)
     return forces, tau
+
+
+def gait_plan(state, root_state, foot_pos, contact_z, command, nominal, reset, ticks, dt, height, apex, touchdown_z, late_depth, k_fb,
+              max_step, leash=float("inf"), contact_threshold=1.0):
+    """One tick of the gait planner: (stance (n, F) uint8, swing_target (n, F, 3) base frame, phase (n, F)), plus the dict
+    {"foothold" (n, F, 2), "world_target" (n, F, 3)}.  The algorithm of csrc/shf_gait.hip's shf_gait_plan (its header states
+    it step by step) as batched torch expressions, in the dtype of root_state (its CPU fallback); tests/gait_ref.py holds the
+    NumPy twin.  state: an object with tick (n) int32, sched (n, F) uint8, anchor (n, F, 3), target (n, 13), yaw (n)
+    (units.gait.GaitState), updated in place.  ticks = (period_ticks, offset_ticks, stance_ticks)."""
+    P, offsets, stance_ticks = ticks
+    n, F = foot_pos.shape[:2]
+    dt_, dev = root_state.dtype, root_state.device
+    p, q, v = root_state[:, :3], root_state[:, 3:7], root_state[:, 7:10]
+    off = torch.as_tensor(list(offsets), dtype=torch.int64, device=dev)
+    S = torch.as_tensor(list(stance_ticks), dtype=torch.int64, device=dev)
+    assert P >= 1 and bool(((S >= 1) & (S <= P)).all()) and bool(((off >= 0) & (off < P)).all()) and dt > 0 and max_step >= 0
+    tick = state.tick.to(torch.int64)
+    was = state.sched != 0
+    anchor = state.anchor.clone()
+    yaw = state.yaw.clone()
+    txy = state.target[:, :2].clone()
+    # 1. reset
+    if reset is not None:
+        r = reset.reshape(n) != 0
+        tick = torch.where(r, torch.zeros_like(tick), tick)
+        was = was | r.unsqueeze(1)
+        under = torch.cat([foot_pos[..., :2].to(dt_), torch.full((n, F, 1), touchdown_z - late_depth, dtype=dt_, device=dev)], -1)
+        anchor = torch.where(r.view(n, 1, 1), under, anchor)
+        heading = torch.atan2(2.0 * (q[:, 0] * q[:, 1] + q[:, 3] * q[:, 2]), 1.0 - 2.0 * (q[:, 1] * q[:, 1] + q[:, 2] * q[:, 2]))
+        yaw = torch.where(r, heading, yaw)
+        txy = torch.where(r.unsqueeze(1), p[:, :2], txy)
+    # 2. the base target
+    cvx, cvy, wz = command[:, 0], command[:, 1], command[:, 2]
+    cy, sy = torch.cos(yaw), torch.sin(yaw)
+    vw = torch.stack([cy * cvx - sy * cvy, sy * cvx + cy * cvy], 1)
+    txy = txy + vw * dt
+    d = txy - p[:, :2]
+    rr = torch.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
+    txy = torch.where((rr > leash).unsqueeze(1), p[:, :2] + d * (leash / rr).unsqueeze(1), txy)
+    yaw = yaw + wz * dt
+    hy = yaw * 0.5
+    tg = state.target
+    tg[:, :2], tg[:, 2] = txy, height
+    tg[:, 3], tg[:, 4], tg[:, 5], tg[:, 6] = 0.0, 0.0, torch.sin(hy), torch.cos(hy)
+    tg[:, 7:9], tg[:, 9] = vw, 0.0
+    tg[:, 10], tg[:, 11], tg[:, 12] = 0.0, 0.0, wz
+    R = quat_to_matrix(q)
+    # 3. the schedule
+    phi = (torch.remainder(tick, P).unsqueeze(1) + off.unsqueeze(0)) % P
+    s = phi < S.unsqueeze(0)
+    # 4. the foothold
+    nfx, nfy = nominal[:, 0].to(dt_).unsqueeze(0), nominal[:, 1].to(dt_).unsqueeze(0)
+    nwx = R[:, 0, 0].unsqueeze(1) * nfx + R[:, 0, 1].unsqueeze(1) * nfy
+    nwy = R[:, 1, 0].unsqueeze(1) * nfx + R[:, 1, 1].unsqueeze(1) * nfy
+    hx, hyp = p[:, 0:1] + nwx, p[:, 1:2] + nwy
+    vdx, vdy = vw[:, 0:1] - wz.unsqueeze(1) * nwy, vw[:, 1:2] + wz.unsqueeze(1) * nwx
+    half = (S.to(dt_).unsqueeze(0) * dt) * 0.5
+    gx = vdx * half + k_fb * (v[:, 0:1] - vw[:, 0:1])
+    gy = vdy * half + k_fb * (v[:, 1:2] - vw[:, 1:2])
+    m = torch.sqrt(gx * gx + gy * gy)
+    big = m > max_step
+    km = max_step / m
+    gx, gy = torch.where(big, gx * km, gx), torch.where(big, gy * km, gy)
+    fx, fy = hx + gx, hyp + gy
+    # 5. events
+    lift, down = was & ~s, ~was & s
+    anchor = torch.where(lift.unsqueeze(-1), foot_pos.to(dt_), anchor)
+    td = torch.stack([fx, fy, torch.full_like(fx, touchdown_z - late_depth)], -1)
+    anchor = torch.where(down.unsqueeze(-1), td, anchor)
+    # 6. the feet's targets
+    touching = torch.ones(n, F, dtype=torch.bool, device=dev) if contact_z is None else contact_z > contact_threshold
+    u = (phi - S.unsqueeze(0) + 1).to(dt_) / (P - S).clamp(min=1).to(dt_).unsqueeze(0)
+    b = (u * u) * (3.0 - 2.0 * u)
+    a1 = 1.0 - b
+    ys = torch.stack([a1 * anchor[..., 0] + b * fx, a1 * anchor[..., 1] + b * fy,
+                      (a1 * anchor[..., 2] + b * touchdown_z) + ((4.0 * apex) * u) * (1.0 - u)], -1)
+    y = torch.where((~s).unsqueeze(-1), ys, torch.where((~touching).unsqueeze(-1), anchor, foot_pos.to(dt_)))
+    dl = y - p.unsqueeze(1)
+    swing = torch.stack([(R[:, 0, k].unsqueeze(1) * dl[..., 0] + R[:, 1, k].unsqueeze(1) * dl[..., 1]) + R[:, 2, k].unsqueeze(1) * dl[..., 2]
+                         for k in range(3)], -1)
+    # 7. outputs
+    state.tick.copy_((tick + 1).to(torch.int32))
+    state.sched.copy_(s.to(torch.uint8))
+    state.anchor.copy_(anchor)
+    state.yaw.copy_(yaw)
+    return (s & touching).to(torch.uint8), swing, phi.to(dt_) / float(P), {"foothold": torch.stack([fx, fy], -1), "world_target": y}
+
+
+def leg_effort_mix(stance_efforts, swing_efforts, stance, chain_mask, effort_limit=None):
+    """clamp(stance_efforts + m swing_efforts, +-effort_limit): m (n, nd) = 1 where a foot with stance == 0 has the dof on its
+    chain (chain_mask (F, nd)), else 0; limit entries <= 0 or None: no clamp.  The torch expression of csrc/shf_gait.hip's
+    shf_leg_effort_mix."""
+    m = ((stance == 0).unsqueeze(-1) & (chain_mask != 0).unsqueeze(0)).any(1).to(stance_efforts.dtype)
+    tau = stance_efforts + m * swing_efforts
+    if effort_limit is not None:
+        lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
+        tau = torch.maximum(torch.minimum(tau, lim), -lim)
+    return tau

@@ -821,26 +821,48 @@ DEV void a1_chain_step_body(const A1Args& A) {
   PHASE_BEGIN();
   float* stats_lds = smem + CHAIN_MODEL_WORDS + TASK_WORDS;
   stats_block_init(stats_lds);
-  const unsigned long long stats_step = stats_step_load(A.stats);
   const int epb = 256 / G, es = threadIdx.x / G, l = threadIdx.x % G;
   const int e = blockIdx.x * epb + es;
   const int n = A.S.n;
-  // the env's state and action loads go out before the model is staged: their round trip overlaps the staging copy
+  // One memory round trip for everything the prologue reads: the step counter (first, so that it can be waited for alone), the
+  // env's state and action, the task parameters and the model are all requested before the first wait, each into registers
+  // of its own.  The random actions' Philox rounds need the counter only and run while the rest is in flight; then one wait,
+  // the LDS writes, the barrier.
+  const unsigned long long stats_req = stats_step_request(A.stats);
+  const uint64_t seed = A.tp->seed;       // (a scalar load, here so that the generator below does not start another round trip)
+  __builtin_amdgcn_sched_barrier(0);      // (the counter's load stays the oldest)
   constexpr int NW = (2 * nd + G - 1) / G;
   float pre_dof[NW], pre_root = 0.0f, pre_act = 0.0f;
 #pragma unroll
   for (int k = 0; k < NW; k++) pre_dof[k] = 0.0f;
   static_assert(G >= 13 && G > nd, "one root word and one action per lane");
+  const bool given = A.raw_actions != nullptr;      // the caller's actions, or (null) the generator: run_policy('random')
   if (e < n) {
 #pragma unroll
     for (int k = 0; k < NW; k++)
       if (l + k * G < 2 * nd) pre_dof[k] = A.S.dof[(size_t)e * nd * 2 + l + k * G];
     if (l < 13) pre_root = A.S.root[(size_t)e * 13 + l];
-    if (l < nd) pre_act = raw_action(A, e, l, nd, stats_step);
+    if (l < nd && given) pre_act = A.raw_actions[(size_t)e * nd + l];
   }
-  stage_block<(int)sizeof(ShfA1TaskParams)>(A.tp, smem + CHAIN_MODEL_WORDS);
-  stage_block<CHAIN_MODEL_BYTES>(A.S.model, smem);   // the model without its link-contact records (CHAIN_MODEL_BYTES)
+  StagedBlock<(int)sizeof(ShfA1TaskParams)> tp_words;
+  StagedBlock<CHAIN_MODEL_BYTES> model_words;       // the model without its link-contact records (CHAIN_MODEL_BYTES)
+  tp_words.load(A.tp);
+  model_words.load(A.S.model);
+  const unsigned long long stats_step = stats_step_take(stats_req);
+  // a1_post_step on constant dimensions, with the statistics row computed here (the division runs under the loads still in
+  // flight): in every form but the PGS ones, where the same source measured 1.8 % slower (profiles/r22_step_edges.md)
+  constexpr bool POSTFIX = !(HARD && !TGS);
+  const unsigned stats_row_index = POSTFIX ? stats_slot(A.stats, stats_step) : 0u;
+  if (e < n && l < nd && !given) pre_act = random_action(seed, A.env_off + e, stats_step, l);
+#pragma unroll
+  for (int k = 0; k < NW; k++) asm volatile("" : "+v"(pre_dof[k]));
+  asm volatile("" : "+v"(pre_root), "+v"(pre_act));
+  tp_words.pin();
+  model_words.pin();
+  tp_words.store(smem + CHAIN_MODEL_WORDS);
+  model_words.store(smem);
   __syncthreads();
+  PHASE_MARK(23);
   const ShfModel* m = reinterpret_cast<const ShfModel*>(smem);
   const ShfA1TaskParams& tp = *reinterpret_cast<const ShfA1TaskParams*>(smem + CHAIN_MODEL_WORDS);
   if (e >= n) return;
@@ -906,18 +928,22 @@ DEV void a1_chain_step_body(const A1Args& A) {
                                      (it == nsub - 1) ? L.xch : nullptr);
   }
   PHASE_RESET();
+  // what the rest of the kernel reads of its arguments comes from the kernarg segment here (scalar loads whose latency lies
+  // under the copy-out and the body states), not out of VGPR lanes where it would have sat through the sub-steps
+  const A1Args AE = a1_args_again();
   if (l < nd) {
     float* D = L.dofb + l * DOF_STRIDE;
     D[0] = X.q; D[1] = X.qd; D[5] = X.tau;
-    A.torques[(size_t)e * nd + l] = X.tau;
+    AE.torques[(size_t)e * nd + l] = X.tau;
     scr[SCR_ACT + l] = act;
   }
-  for (int i = l; i < 3 * nb; i += G) A.S.contact[(size_t)e * nb * 3 + i] = L.xch[i];
+  for (int i = l; i < 3 * nb; i += G) AE.S.contact[(size_t)e * nb * 3 + i] = L.xch[i];
   // the contact-point region is idle from here on: it becomes scratch
-  for (int i = l; i < nd * H; i += G) scr[SCR_HIST + i] = A.history[(size_t)e * nd * H + i];
+  for (int i = l; i < nd * H; i += G) scr[SCR_HIST + i] = AE.history[(size_t)e * nd * H + i];
   PHASE_MARK(12);
   chain_body_states<G, CD>(m, L, l, X, scr + SCR_BODY);
-  for (int i = l; i < 13 * nb; i += G) A.body_state[(size_t)e * nb * 13 + i] = scr[SCR_BODY + i];
-  PHASE_RESET();
-  a1_post_step<G>(A, m, tp, L, scr, e, l, stats_lds, stats_step);
+  for (int i = l; i < 13 * nb; i += G) AE.body_state[(size_t)e * nb * 13 + i] = scr[SCR_BODY + i];
+  PHASE_MARK(13);
+  if constexpr (POSTFIX) a1_post_step<G, nd, nb>(AE, m, tp, L, scr, e, l, stats_lds, stats_step, stats_row_index);
+  else a1_post_step<G>(AE, m, tp, L, scr, e, l, stats_lds, stats_step);
 }

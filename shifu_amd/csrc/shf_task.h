@@ -52,6 +52,39 @@ DEV void stage_block(const void* gsrc, float* ldst) {
   }
   if (NT > 0 && (int)threadIdx.x < NT) reinterpret_cast<uint32_t*>(ldst)[NV * 4 + threadIdx.x] = tail;
 }
+// stage_block in two halves, for a caller that issues the loads of several blocks (and other loads) before it waits for any
+// of them: load() sends the requests, pin() is the one place where the words must have arrived, store() writes them to LDS.
+// Left to itself the compiler sinks each load into the conditional block of its store, one round trip per 4 KB; pin() uses
+// the words unconditionally, so the loads stay above it.
+template <int NBYTES, int THREADS = 256>
+struct StagedBlock {
+  static constexpr int NV = NBYTES / 16, NT = (NBYTES % 16) / 4, IV = (NV + THREADS - 1) / THREADS;
+  uint4 v[IV > 0 ? IV : 1];
+  uint32_t tail = 0;
+  DEV void load(const void* gsrc) {
+    const uint4* src = reinterpret_cast<const uint4*>(gsrc);
+#pragma unroll
+    for (int k = 0; k < IV; k++) {
+      const int i = (int)threadIdx.x + k * THREADS;
+      v[k] = src[i < NV ? i : 0];
+    }
+    if (NT > 0 && (int)threadIdx.x < NT) tail = reinterpret_cast<const uint32_t*>(gsrc)[NV * 4 + threadIdx.x];
+  }
+  DEV void pin() {
+#pragma unroll
+    for (int k = 0; k < IV; k++) asm volatile("" : "+v"(v[k].x), "+v"(v[k].y), "+v"(v[k].z), "+v"(v[k].w));
+    if (NT > 0) asm volatile("" : "+v"(tail));
+  }
+  DEV void store(float* ldst) const {
+    uint4* dst = reinterpret_cast<uint4*>(ldst);
+#pragma unroll
+    for (int k = 0; k < IV; k++) {
+      const int i = (int)threadIdx.x + k * THREADS;
+      if (i < NV) dst[i] = v[k];
+    }
+    if (NT > 0 && (int)threadIdx.x < NT) reinterpret_cast<uint32_t*>(ldst)[NV * 4 + threadIdx.x] = tail;
+  }
+};
 // the flattened articulation
 template <int THREADS = 256>
 DEV const ShfModel* stage_model(const ShfModel* gm, float* smem) {
@@ -106,9 +139,24 @@ DEV unsigned long long stats_step_load(const StatsArgs& S) {
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
   return ((unsigned long long)hi << 32) | lo;
 }
-template <int NK>
-DEV unsigned long long* stats_contribute(const StatsArgs& S, float* lds_words, const long long* v, int envs_in_block,
-                                         unsigned long long step) {
+// The same in two halves for a prologue that requests everything it reads before it waits: stats_step_request is its first
+// (oldest) load, and stats_step_take, behind the other requests, is where that load alone must have arrived -- loads return in
+// order, so the wait leaves the younger ones in flight.
+DEV unsigned long long stats_step_request(const StatsArgs& S) {
+  return __hip_atomic_load(S.acc + (size_t)S.ring * STATS_COLS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+DEV unsigned long long stats_step_take(unsigned long long v) {
+  unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
+  asm volatile("" : "+v"(lo), "+v"(hi));
+  lo = __builtin_amdgcn_readfirstlane(lo); hi = __builtin_amdgcn_readfirstlane(hi);
+  return ((unsigned long long)hi << 32) | lo;
+}
+// stats_slot: the ring row of vec-step `step`.  A caller that has the step early (the chain kernels' prologue, under its loads)
+// computes it there once and passes it to stats_contribute_at / stats_finish_at: no division where the kernel ends.  SLOT: a
+// callable that gives the row, asked only by the lane that needs it.
+DEV unsigned stats_slot(const StatsArgs& S, unsigned long long step) { return (unsigned)(step % (unsigned long long)S.ring); }
+template <int NK, class SLOT>
+DEV unsigned long long* stats_contribute_by(const StatsArgs& S, float* lds_words, const long long* v, int envs_in_block, SLOT slot) {
   unsigned long long* blk = reinterpret_cast<unsigned long long*>(lds_words);
 #pragma unroll
   for (int k = 0; k < NK; k++)
@@ -116,13 +164,22 @@ DEV unsigned long long* stats_contribute(const StatsArgs& S, float* lds_words, c
   const unsigned done = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(&blk[9]), 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
   if ((int)done != envs_in_block - 1) return nullptr;
   // last group of this block
-  unsigned long long* row = S.acc + (size_t)(step % (unsigned long long)S.ring) * STATS_COLS;
+  unsigned long long* row = S.acc + (size_t)slot() * STATS_COLS;
 #pragma unroll
   for (int k = 0; k < NK; k++) {
     const unsigned long long t = __hip_atomic_load(&blk[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (t != 0ull) __hip_atomic_fetch_add(&row[k], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   return row;
+}
+template <int NK>
+DEV unsigned long long* stats_contribute(const StatsArgs& S, float* lds_words, const long long* v, int envs_in_block,
+                                         unsigned long long step) {
+  return stats_contribute_by<NK>(S, lds_words, v, envs_in_block, [&S, step] { return step % (unsigned long long)S.ring; });
+}
+template <int NK>
+DEV unsigned long long* stats_contribute_at(const StatsArgs& S, float* lds_words, const long long* v, int envs_in_block, unsigned slot) {
+  return stats_contribute_by<NK>(S, lds_words, v, envs_in_block, [slot] { return (unsigned long long)slot; });
 }
 // stats_ticket: after the block's additions are acknowledged; the returned count is only looked at by stats_finish, at
 // the very end of the kernel, so the atomic's round trip overlaps the output stores in between.
@@ -131,8 +188,9 @@ DEV unsigned long long stats_ticket(unsigned long long* row) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      // s_waitcnt: this block's additions are acknowledged
   return __hip_atomic_fetch_add(&row[8], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-template <int NK, class FIN>
-DEV void stats_finish(const StatsArgs& S, unsigned long long* row, unsigned long long ticket, unsigned long long step, FIN finalize) {
+template <int NK, class FIN, class SLOT>
+DEV void stats_finish_by(const StatsArgs& S, unsigned long long* row, unsigned long long ticket, unsigned long long step, SLOT slot,
+                         FIN finalize) {
   if (!row) return;
   if (ticket != (unsigned long long)gridDim.x - 1ull) return;
   // last block of the launch
@@ -141,12 +199,21 @@ DEV void stats_finish(const StatsArgs& S, unsigned long long* row, unsigned long
   for (int k = 0; k < NK; k++)
     tot[k] = (long long)__hip_atomic_exchange(&row[k], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_store(&row[8], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  float* o = S.out + (size_t)(step % (unsigned long long)S.ring) * S.out_cols;
+  float* o = S.out + (size_t)slot() * S.out_cols;
   finalize(tot, o);
   float* latest = S.out + (size_t)S.ring * S.out_cols;     // row `ring`: always the step that ran last
   for (int k = 0; k < S.out_cols; k++) latest[k] = o[k];
   unsigned long long* ctl = S.acc + (size_t)S.ring * STATS_COLS;
   __hip_atomic_store(ctl, step + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <int NK, class FIN>
+DEV void stats_finish(const StatsArgs& S, unsigned long long* row, unsigned long long ticket, unsigned long long step, FIN finalize) {
+  stats_finish_by<NK>(S, row, ticket, step, [&S, step] { return step % (unsigned long long)S.ring; }, finalize);
+}
+template <int NK, class FIN>
+DEV void stats_finish_at(const StatsArgs& S, unsigned long long* row, unsigned long long ticket, unsigned long long step, unsigned slot,
+                         FIN finalize) {
+  stats_finish_by<NK>(S, row, ticket, step, [slot] { return (unsigned long long)slot; }, finalize);
 }
 
 // ------------------------------------------------------- fused A1 step --
@@ -169,6 +236,17 @@ struct A1Args {
   float* body_state;
   StatsArgs stats;
 };
+// The kernel's argument block read from the kernarg segment once more (scalar loads, only the fields the caller goes on to use):
+// for the code behind a long loop that would otherwise keep two dozen pointers parked in VGPR lanes across it and fetch each
+// back with a v_readlane.  Only for a kernel whose single parameter is the A1Args (it lies at offset 0 of the segment).
+DEV A1Args a1_args_again() {
+  typedef const A1Args __attribute__((address_space(4)))* KP;
+  KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));      // (opaque from here: not merged with the loads at the kernel's entry)
+  A1Args r;
+  __builtin_memcpy(&r, p, sizeof(A1Args));
+  return r;
+}
 
 DEV void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
 #pragma unroll
@@ -215,6 +293,19 @@ struct ResetOut {
   float root[13], cmd[3], push[3], org[3];
   int64_t level;
 };
+// x % m (m > 0) by restoring division, one bit per trip: for the one place behind the sub-step loop that divides by a run-time
+// value -- the random level of an env promoted past the top of the curriculum, a few envs per thousand resets.  A rolled loop
+// of a dozen instructions there instead of the reciprocal sequence's forty in every wavefront's instruction stream.
+DEV uint32_t umod_bitwise(uint32_t x, uint32_t m) {
+  uint64_t r = 0;
+#pragma unroll 1
+  for (int b = 31; b >= 0; b--) {
+    r = (r << 1) | ((x >> b) & 1u);
+    if (r >= m) r -= m;
+  }
+  return (uint32_t)r;
+}
+template <bool BITMOD = false>
 DEV void a1_reset_draw(const ShfA1TaskParams& tp, int64_t gid, uint32_t cnt, const float* root_pos, const float* cmd_old,
                        const float* org_old, int64_t level, int64_t type, const float* torigins, ResetOut& R) {
   uint32_t r0[4], r1[4], r2[4];
@@ -230,7 +321,8 @@ DEV void a1_reset_draw(const ShfA1TaskParams& tp, int64_t gid, uint32_t cnt, con
     const float cn = sqrtf(cmd_old[0] * cmd_old[0] + cmd_old[1] * cmd_old[1]);
     const int down = (dist < cn * tp.max_episode_length_s * 0.5f) && !up;
     level += up - down;
-    if (level >= tp.max_terrain_level) level = (int64_t)(r2[3] % (uint32_t)tp.max_terrain_level);
+    if (level >= tp.max_terrain_level)
+      level = (int64_t)(BITMOD ? umod_bitwise(r2[3], (uint32_t)tp.max_terrain_level) : r2[3] % (uint32_t)tp.max_terrain_level);
     else if (level < 0) level = 0;
     const float* to = torigins + ((size_t)level * tp.num_terrain_cols + (size_t)type) * 3;
     og[0] = to[0]; og[1] = to[1]; og[2] = to[2];
@@ -264,12 +356,19 @@ DEV void a1_reset_draw(const ShfA1TaskParams& tp, int64_t gid, uint32_t cnt, con
 // the body-mapped and the chain-mapped A1 kernels.  On entry: L.dofb / L.root hold the post-physics state, L.xch the net
 // contact forces (nb x 3), scr[SCR_HIST] the action history, scr[SCR_ACT] the clipped actions; the G lanes of the
 // env's group call it together.
-template <int G>
+// ND, NB: the articulation's dimensions as constants (the chain kernels: ChainDims::ND / NB) -- lane 0's reward loops are
+// unrolled with their LDS reads issued together, no index is divided by a run-time value, and a reset's LDS writes are
+// shared among the env's lanes.  H == 3 (the only value shf_a1_create accepts today) takes the constant-index form of the
+// history loops; any other H the nested form beside it.  stats_row_index: stats_slot(A.stats, stats_step), computed by the
+// caller where it has the time.  0 (the body-mapped kernel): the dimensions are read from the model, the row is computed here.
+template <int G, int ND = 0, int NB = 0>
 DEV void a1_post_step(const A1Args& A, const ShfModel* m, const ShfA1TaskParams& tp, const EnvLds& L, float* scr, int e,
-                      int l, float* stats_lds, unsigned long long stats_step) {
+                      int l, float* stats_lds, unsigned long long stats_step, unsigned stats_row_index = 0) {
   PHASE_BEGIN();
+  constexpr bool FIXED = ND > 0;
+  static_assert(!FIXED || (NB > 0 && ND <= G), "constant dimensions: both, one dof per lane");
   const int n = A.S.n, epb = 256 / G;
-  const int nb = m->nb, nd = m->nd, H = tp.num_history, P = tp.num_height_points;
+  const int nb = FIXED ? NB : m->nb, nd = FIXED ? ND : m->nd, H = tp.num_history, P = tp.num_height_points;
   const int nobs = 12 + 2 * nd + nd * H + P;
   float* dof = A.S.dof + (size_t)e * nd * 2;
   float* root = A.S.root + (size_t)e * 13;
@@ -347,6 +446,7 @@ DEV void a1_post_step(const A1Args& A, const ShfModel* m, const ShfA1TaskParams&
 
   // post_step (env.py:93-106): one lane runs the scalar bookkeeping
   unsigned long long* stats_row = nullptr;
+  int reset_env = 0;      // FIXED: lane 0's reset decision, for the env's lanes behind the next GROUP_SYNC
   if (l == 0) {
     const float blv[3] = {ps_bv[0], ps_bv[1], ps_bv[2]}, bav[3] = {ps_bv[3], ps_bv[4], ps_bv[5]};
     const float* cf = L.xch;
@@ -367,21 +467,65 @@ DEV void a1_post_step(const A1Args& A, const ShfModel* m, const ShfA1TaskParams&
       rterm[1] = 0.5f * exp_spec(-(e2 * e2) / 0.25f);
       rterm[2] = -2.0f * (blv[2] * blv[2]) + -0.005f * (bav[0] * bav[0] + bav[1] * bav[1]);
       float first = 0.0f, second = 0.0f;
-      for (int d = 0; d < nd; d++) {
-        const float a0 = hist[d * H + 0], a1 = hist[d * H + 1], a2 = hist[d * H + 2];
-        first += (a1 - a0) * (a1 - a0);
-        const float t = a2 - 2.0f * a1 + a0;
-        second += t * t;
+      if constexpr (FIXED) {
+        // all reads of the loop first (H == 3: at constant offsets), then the sums in index order
+        float hv[ND][3];
+        if (H == 3) {
+#pragma unroll
+          for (int d = 0; d < ND; d++) { hv[d][0] = hist[d * 3 + 0]; hv[d][1] = hist[d * 3 + 1]; hv[d][2] = hist[d * 3 + 2]; }
+        } else {
+#pragma unroll
+          for (int d = 0; d < ND; d++) { hv[d][0] = hist[d * H + 0]; hv[d][1] = hist[d * H + 1]; hv[d][2] = hist[d * H + 2]; }
+        }
+#pragma unroll
+        for (int d = 0; d < ND; d++) {
+          const float a0 = hv[d][0], a1 = hv[d][1], a2 = hv[d][2];
+          first += (a1 - a0) * (a1 - a0);
+          const float t = a2 - 2.0f * a1 + a0;
+          second += t * t;
+        }
+      } else {
+        for (int d = 0; d < nd; d++) {
+          const float a0 = hist[d * H + 0], a1 = hist[d * H + 1], a2 = hist[d * H + 2];
+          first += (a1 - a0) * (a1 - a0);
+          const float t = a2 - 2.0f * a1 + a0;
+          second += t * t;
+        }
       }
       rterm[3] = -0.005f * (first + second);
       float cnt = 0.0f;
-      for (int k = 0; k < tp.num_leg_bodies; k++) {
-        const float* f = cf + 3 * tp.leg_bodies[k];
-        if (sqrtf(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]) > 0.1f) cnt += 1.0f;
+      if constexpr (FIXED) {
+        // eight legs' body indices, then their forces, go out together: two LDS round trips per eight legs, not two per leg
+        constexpr int LC = 8;
+        const int nleg = tp.num_leg_bodies;
+        for (int k0 = 0; k0 < nleg; k0 += LC) {
+          int lb[LC];
+          float fx[LC], fy[LC], fz[LC];
+#pragma unroll
+          for (int k = 0; k < LC; k++) lb[k] = tp.leg_bodies[k0 + k < nleg ? k0 + k : 0];
+#pragma unroll
+          for (int k = 0; k < LC; k++) { const float* f = cf + 3 * lb[k]; fx[k] = f[0]; fy[k] = f[1]; fz[k] = f[2]; }
+#pragma unroll
+          for (int k = 0; k < LC; k++)
+            if (k0 + k < nleg && sqrtf(fx[k] * fx[k] + fy[k] * fy[k] + fz[k] * fz[k]) > 0.1f) cnt += 1.0f;
+        }
+      } else {
+        for (int k = 0; k < tp.num_leg_bodies; k++) {
+          const float* f = cf + 3 * tp.leg_bodies[k];
+          if (sqrtf(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]) > 0.1f) cnt += 1.0f;
+        }
       }
       rterm[4] = -1.0f * cnt;
       float t2 = 0.0f;
-      for (int d = 0; d < nd; d++) { const float t = L.dofb[d * DOF_STRIDE + 5]; t2 += t * t; }
+      if constexpr (FIXED) {
+        float tq[ND];
+#pragma unroll
+        for (int d = 0; d < ND; d++) tq[d] = L.dofb[d * DOF_STRIDE + 5];
+#pragma unroll
+        for (int d = 0; d < ND; d++) t2 += tq[d] * tq[d];
+      } else {
+        for (int d = 0; d < nd; d++) { const float t = L.dofb[d * DOF_STRIDE + 5]; t2 += t * t; }
+      }
       rterm[5] = -2e-5f * t2;
     }
     float rew = 0.0f;
@@ -396,7 +540,7 @@ DEV void a1_post_step(const A1Args& A, const ShfModel* m, const ShfA1TaskParams&
     int64_t level = ps_level;
     if (reset) {
       ResetOut R;
-      a1_reset_draw(tp, A.env_off + e, (uint32_t)ps_rc, L.root, cmd, A.origins + (size_t)e * 3, level,
+      a1_reset_draw<FIXED>(tp, A.env_off + e, (uint32_t)ps_rc, L.root, cmd, A.origins + (size_t)e * 3, level,
                     ps_type, A.torigins, R);
       level = R.level;
       A.levels[e] = level;
@@ -405,17 +549,21 @@ DEV void a1_post_step(const A1Args& A, const ShfModel* m, const ShfA1TaskParams&
 #pragma unroll
       for (int k = 0; k < 6; k++) { done[k] = sums[k]; sums[k] = 0.0f; }
       done[7] = 1.0f;
-      for (int d = 0; d < nd; d++) { L.dofb[d * DOF_STRIDE] = tp.default_dof_pos[d]; L.dofb[d * DOF_STRIDE + 1] = 0.0f; }
+      // (FIXED: the dof block and the history are reset by the env's lanes below)
+      if constexpr (!FIXED)
+        for (int d = 0; d < nd; d++) { L.dofb[d * DOF_STRIDE] = tp.default_dof_pos[d]; L.dofb[d * DOF_STRIDE + 1] = 0.0f; }
 #pragma unroll
       for (int k = 0; k < 13; k++) L.root[k] = R.root[k];
 #pragma unroll
       for (int k = 0; k < 3; k++) A.push[((size_t)e * nb + tp.base_body) * 3 + k] = R.push[k];
       ep = 0;
-      for (int k = 0; k < nd * H; k++) scr[SCR_HIST + k] = 0.0f;
+      if constexpr (!FIXED)
+        for (int k = 0; k < nd * H; k++) scr[SCR_HIST + k] = 0.0f;
 #pragma unroll
       for (int k = 0; k < 3; k++) { cmd[k] = R.cmd[k]; A.command[(size_t)e * 3 + k] = cmd[k]; }
       A.reset_count[e] = ps_rc + 1;
     }
+    reset_env = reset;
     done[6] = (float)level;
 #pragma unroll
     for (int k = 0; k < 6; k++) A.rew_sums[(size_t)k * n + e] = sums[k];
@@ -429,7 +577,8 @@ DEV void a1_post_step(const A1Args& A, const ShfModel* m, const ShfA1TaskParams&
       for (int k = 0; k < 6; k++) sv[k] = stats_fix(done[k]);
       sv[6] = (long long)level; sv[7] = reset ? 1ll : 0ll;
       const int first = (int)blockIdx.x * epb, eib = n - first < epb ? n - first : epb;
-      stats_row = stats_contribute<8>(A.stats, stats_lds, sv, eib, stats_step);
+      if constexpr (FIXED) stats_row = stats_contribute_at<8>(A.stats, stats_lds, sv, eib, stats_row_index);
+      else stats_row = stats_contribute<8>(A.stats, stats_lds, sv, eib, stats_step);
     }
     const float co = tp.clip_obs;
     float* o = scr + SCR_OBS;
@@ -442,6 +591,14 @@ DEV void a1_post_step(const A1Args& A, const ShfModel* m, const ShfA1TaskParams&
     }
   }
   GROUP_SYNC();
+  if constexpr (FIXED) {
+    // a reset's LDS writes that lane 0 used to make one by one: default dof positions, zero velocities, an empty history
+    if (__shfl(reset_env, 0, G)) {
+      if (l < ND) { L.dofb[l * DOF_STRIDE] = tp.default_dof_pos[l]; L.dofb[l * DOF_STRIDE + 1] = 0.0f; }
+      for (int i = l; i < ND * H; i += G) scr[SCR_HIST + i] = 0.0f;
+    }
+    GROUP_SYNC();
+  }
   PHASE_MARK(15);
   {
     // compute_observations (a1_conditional.py:131-144) staged in LDS, then one coalesced store
@@ -451,9 +608,21 @@ DEV void a1_post_step(const A1Args& A, const ShfModel* m, const ShfA1TaskParams&
       o[12 + l] = rclampf(L.dofb[l * DOF_STRIDE] - tp.default_dof_pos[l], -co, co);
       o[12 + nd + l] = rclampf(L.dofb[l * DOF_STRIDE + 1], -co, co);
     }
-    for (int i = l; i < nd * H; i += G) {
-      const int h = i / nd, d = i % nd;
-      o[12 + 2 * nd + i] = rclampf(scr[SCR_HIST + d * H + h], -co, co);
+    if constexpr (FIXED) {
+      if (H == 3) {
+        for (int i = l; i < ND * 3; i += G) {
+          const int h = i / ND, d = i % ND;
+          o[12 + 2 * ND + i] = rclampf(scr[SCR_HIST + d * 3 + h], -co, co);
+        }
+      } else {
+        for (int h = 0; h < H; h++)
+          for (int d = l; d < ND; d += G) o[12 + 2 * ND + h * ND + d] = rclampf(scr[SCR_HIST + d * H + h], -co, co);
+      }
+    } else {
+      for (int i = l; i < nd * H; i += G) {
+        const int h = i / nd, d = i % nd;
+        o[12 + 2 * nd + i] = rclampf(scr[SCR_HIST + d * H + h], -co, co);
+      }
     }
     const float bz = L.root[2];
     for (int i = l; i < P; i += G)
@@ -465,15 +634,28 @@ DEV void a1_post_step(const A1Args& A, const ShfModel* m, const ShfA1TaskParams&
   if (l == 0) stats_tk = stats_ticket(stats_row);
   for (int i = l; i < nobs; i += G) A.obs[(size_t)e * nobs + i] = scr[SCR_OBS + i];
   // HistoryRecorder.add (train.py:12-14), after the observation was taken (Q12)
-  for (int i = l; i < nd * H; i += G) {
-    const int d = i / H, h = i % H;
-    A.history[(size_t)e * nd * H + i] = h == 0 ? scr[SCR_ACT + d] : scr[SCR_HIST + d * H + h - 1];
+  if constexpr (FIXED) {
+    if (H == 3) {
+      for (int i = l; i < ND * 3; i += G) {
+        const int d = i / 3, h = i % 3;
+        A.history[(size_t)e * ND * 3 + i] = h == 0 ? scr[SCR_ACT + d] : scr[SCR_HIST + d * 3 + h - 1];
+      }
+    } else {
+      for (int h = 0; h < H; h++)
+        for (int d = l; d < ND; d += G)
+          A.history[(size_t)e * ND * H + d * H + h] = h == 0 ? scr[SCR_ACT + d] : scr[SCR_HIST + d * H + h - 1];
+    }
+  } else {
+    for (int i = l; i < nd * H; i += G) {
+      const int d = i / H, h = i % H;
+      A.history[(size_t)e * nd * H + i] = h == 0 ? scr[SCR_ACT + d] : scr[SCR_HIST + d * H + h - 1];
+    }
   }
   for (int i = l; i < 2 * nd; i += G) dof[i] = L.dofb[(i >> 1) * DOF_STRIDE + (i & 1)];
   if (l < 13) root[l] = L.root[l];
   if (l == 0) {
     const float Ts = tp.max_episode_length_s;
-    stats_finish<8>(A.stats, stats_row, stats_tk, stats_step, [n, Ts](const long long* t, float* o) {
+    const auto fin = [n, Ts](const long long* t, float* o) {
       const float c = (float)t[7];
 #pragma unroll
       for (int k = 0; k < 6; k++) {
@@ -483,7 +665,9 @@ DEV void a1_post_step(const A1Args& A, const ShfModel* m, const ShfA1TaskParams&
       }
       o[6] = (float)t[6]; o[7] = c;
       o[14] = o[6] / (float)n; o[15] = (float)n;
-    });
+    };
+    if constexpr (FIXED) stats_finish_at<8>(A.stats, stats_row, stats_tk, stats_step, stats_row_index, fin);
+    else stats_finish<8>(A.stats, stats_row, stats_tk, stats_step, fin);
   }
   PHASE_MARK(16);
 }

@@ -13,6 +13,8 @@ serialise the wave a little (s_memtime + waitcnt), so the total is a few % above
 launch (the first lane of every wavefront keeps its own row; read and cleared after every step here), summed over
 the steps.  All wavefronts of the fused step are resident at once, so that wavefront is the one the launch lasts as
 long as; block 0 / wave 0 is an average one.
+The chain kernels' edges have marks of their own: 23 = entry to the block's barrier, 11 = from there to the sub-step loop,
+12 = copy-out and history load, 13 = body states and their store, 14 - 16 = a1_post_step (profiles/r22_step_edges.md).
 The rows cost one 64-bit atomic add per mark and wavefront (about 115 per wavefront and env-step), which lengthens
 every wavefront a little more than the marks alone do: compare columns of one build with the same columns of another,
 not with the product kernel's time.
@@ -115,12 +117,12 @@ def main():
         if slow:
             torch.cuda.synchronize()
             assert fw(rows.ctypes.data, 1) == 0
-            worst += rows[int((rows[:, :23].sum(1) + rows[:, 30:32].sum(1)).argmax())]
+            worst += rows[int((rows[:, :24].sum(1) + rows[:, 30:32].sum(1)).argmax())]
     torch.cuda.synchronize()
     assert fn(buf, 48, 0) == 0
     tot = sum(buf[:17]) if not split else sum(buf[11:17]) + sum(buf[24:30])  # (marks 17-23: inside phase 4 for the box scene)
     if pgs and not abb:
-        tot = sum(buf[:23]) + sum(buf[30:32])     # chain kernel: the solve's parts are marks 5, 10, 17 - 22; P's first two parts 30, 31
+        tot = sum(buf[:24]) + sum(buf[30:32])     # chain kernel: the solve's parts are marks 5, 10, 17 - 22; P's first two parts 30, 31; 23 = entry to the barrier
     if pgs and abb:
         tot = sum(buf[:24]) + sum(buf[32:38]) + (sum(buf[24:29]) if link else 0)    # generic kernel: every mark is its own interval
     if pgs and abb and split:
@@ -148,6 +150,10 @@ def main():
     if pgs and not abb:
         extra_names[0:6] = ['  H3 sweeps (position + velocity iterations)', '  H4 impulse passes: behind the last barrier', '  H4 gather (body lanes)',
                             '  H4 inward pass (chain lanes)', '  H4 root substitution', '  H4 outward pass (chain lanes)']
+        # the step's edges: 23 = entry to the block's barrier (loads, the random actions' Philox rounds, staging), 11 = from there to
+        # the sub-step loop, 12 = copy-out + history load, 13 = body states + their store, 14 - 16 = a1_post_step
+        extra_names[6] = 'prologue: entry -> barrier (loads, staging)'
+        NAMES[11] = 'prologue: barrier -> sub-step loop'; NAMES[13] = 'body states + store'
         # P in three parts: marks 30 and 31 come before mark 3 in the sub-step
         extra_names += ['P: sample points -> candidate ballots', 'P: selection at the cap (+ drop counter)']
         hist = [buf[38 + k] for k in range(9)]
@@ -158,11 +164,11 @@ def main():
         hard_names = ['hard: body records + velocity rates', 'hard: gather candidates', 'hard: response matrix columns',
                       'hard: owner setup', 'hard: sweeps', 'hard: impulse passes']
     if slow:
-        wtot = worst[:23].sum() + worst[30:32].sum()
+        wtot = worst[:24].sum() + worst[30:32].sum()
         print(f"  the slowest wavefront of each launch: {wtot / steps:.0f} cycles per env-step (second pair of columns)")
     for k, nme in enumerate(NAMES + extra_names):
         print(f"  {k:2d} {nme:52s} {buf[k] / steps:9.0f}  {100.0 * buf[k] / tot:5.1f} %" +
-              (f"  {worst[k] / steps:9.0f}  {100.0 * worst[k] / wtot:5.1f} %" if slow and (k < 23 or k in (30, 31)) else ""))
+              (f"  {worst[k] / steps:9.0f}  {100.0 * worst[k] / wtot:5.1f} %" if slow and (k < 24 or k in (30, 31)) else ""))
     for k, nme in enumerate(hard_names):
         print(f"  {32 + k:2d} {nme:52s} {buf[32 + k] / steps:9.0f}  {100.0 * buf[32 + k] / tot:5.1f} %")
 

@@ -18,7 +18,7 @@ KERNEL_UNITS = ["shf_k_sim.hip", "shf_k_sim_link.hip", "shf_k_sim_hard.hip", "sh
 UNITY_SOURCES = ["shf_api.hip", "shf_a1_chain.hip", "shf_glue.hip", "shf_mlp.hip", "shf_k_hull_test.hip", "shf_k_cap_select_test.hip", "shf_render.hip", "shf_conv.hip", "shf_lstm.hip", "shf_gru.hip", "shf_dyn.hip", "shf_dyn_fb.hip", "shf_qp.hip", "shf_gait.hip"]      # with -DSHF_UNITY: shf_api.hip instantiates every kernel
 SOURCES = UNITY_SOURCES + [u for u in KERNEL_UNITS if u not in UNITY_SOURCES]
 HEADERS = ["shf_device.h", "shf_boxes.h", "shf_task.h", "shf_chain.h", "shf_chain_hard.h", "shf_hard.h", "shf_link.h", "shf_arm.h", "shf_kernels.h",
-           "shf_kernel_list.h", "shf_hull.h", "shf_dyn.h", os.path.join("..", "..", "include", "shifu_amd.h")]
+           "shf_kernel_list.h", "shf_hull.h", "shf_dyn.h", "shf_rnn_cell.h", os.path.join("..", "..", "include", "shifu_amd.h")]
 DEPS = SOURCES + HEADERS
 # -fno-slp-vectorize: the SLP vectoriser packs neighbouring scalar f32 ops into v_pk_* pairs plus the
 # v_mov shuffles that feed them -- slower for this kernel (measured -6 % at 2 envs/wave, -25 % at one
@@ -104,14 +104,14 @@ BUDGETS = [("_Z16k_a1_step_a1_g32", 256, 0),          # default: A1, two envs pe
            # accumulators, a chunk's weight fragments, the gathered rows in flight) plus a margin of 10 for compiler drift -- still
            # two waves per SIMD; nothing on the stack
            ("_ZN12_GLOBAL__N_111k_conv3x3s2", 224, 0),
-           # the LSTM cell step (csrc/shf_lstm.hip), both precisions: 178 registers in the first clean build (the four gate
-           # accumulators, a chunk's weight fragments, the gathered row values in flight) plus a margin of 10 -- two waves per
+           # the recurrent cell step (k_rnn_cell of csrc/shf_rnn_cell.h), both precisions.  The LSTM's (csrc/shf_lstm.hip): 178
+           # registers in the first clean build (the four gate accumulators, a chunk's weight fragments, the gathered row values
+           # in flight) plus a margin of 10 -- two waves per SIMD; nothing on the stack
+           ("_ZN12_GLOBAL__N_110k_rnn_cellINS_8LstmCell", 188, 0),
+           # the GRU's (csrc/shf_gru.hip): 176 registers in the first clean build (96 + 80: the r, z, n_x, n_h accumulators, a
+           # chunk's three weight fragments per k step, the gathered row values in flight) plus a margin of 10 -- two waves per
            # SIMD; nothing on the stack
-           ("_ZN12_GLOBAL__N_111k_lstm_cell", 188, 0),
-           # the GRU cell step (csrc/shf_gru.hip), both precisions: 176 registers in the first clean build (96 + 80: the r, z,
-           # n_x, n_h accumulators, a chunk's three weight fragments per k step, the gathered row values in flight) plus a
-           # margin of 10 -- two waves per SIMD; nothing on the stack
-           ("_ZN12_GLOBAL__N_110k_gru_cell", 186, 0),
+           ("_ZN12_GLOBAL__N_110k_rnn_cellINS_7GruCell", 186, 0),
            # mass matrix and bias forces (csrc/shf_dyn.hip: k_sim_dynamics at 16 / 32 / 64 lanes per env) and the operational-space
            # controller (csrc/shf_glue.hip: k_osc): 112 and 76 registers in the first clean build (a body's pose, motion subspace,
            # packed inertia and force; the packed 6x6 system and its factor) plus a margin of 10; nothing on the stack -- the

@@ -21,6 +21,56 @@ from . import mfma_linear as ml
 from .actor_critic import ActorCritic
 
 
+def _gradient_gemms(x, h_prev, reset, w_ih, w_hh, dgx, dgh, N, need_x, need_h, need_w):
+    """What both cells' backward passes do after their pointwise kernel, on the MLP layers' gradient GEMMs and the raw
+    weights: from the pre-activation gradients of the x side and of the h side ((M, N) each; the LSTM's are one tensor) to
+    (dx, dh_prev, dw_ih, dw_hh, db_ih, db_hh), None where not needed.  db_hh is computed only where dgh is a tensor of its
+    own (it equals db_ih otherwise).  `reset`: the cell step's; its rows' h_prev counted as zero, so they take no gradient
+    through it.  Called under the tensors' device."""
+    L = ml.lib()
+    M, I = x.shape
+    H = h_prev.shape[1]
+    st = ml._stream(x)
+    keep = None if reset is None else (1.0 - reset.to(torch.float32)).unsqueeze(1)
+    dx = dh_prev = dw_ih = dw_hh = db_ih = db_hh = None
+    if need_x:
+        dx = torch.empty_like(x)
+        ml._check(L.shf_mlp_linear_backward_input(ml._ptr(dgx), None, ml._ptr(w_ih), ml._ptr(dx), M, I, N, st))
+    if need_h:
+        dh_prev = torch.empty_like(h_prev)
+        ml._check(L.shf_mlp_linear_backward_input(ml._ptr(dgh), None, ml._ptr(w_hh), ml._ptr(dh_prev), M, H, N, st))
+        if keep is not None:
+            dh_prev = dh_prev * keep
+    if need_w:
+        def workspace(K):
+            n = C.c_int64()
+            ml._check(L.shf_mlp_backward_weight_workspace(M, K, N, C.byref(n)))
+            return torch.empty(n.value, device=x.device, dtype=torch.float32)
+        dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
+        db_ih = torch.empty(N, device=x.device, dtype=torch.float32)
+        db_hh = None if dgh is dgx else torch.empty_like(db_ih)
+        ml._check(L.shf_mlp_linear_backward_weight(ml._ptr(dgx), None, ml._ptr(x), ml._ptr(dw_ih), ml._ptr(db_ih), ml._ptr(workspace(I)),
+                                                   M, I, N, st))
+        h_eff = h_prev if keep is None else h_prev * keep
+        ml._check(L.shf_mlp_linear_backward_weight(ml._ptr(dgh), None, ml._ptr(h_eff), ml._ptr(dw_hh), None if db_hh is None else ml._ptr(db_hh),
+                                                   ml._ptr(workspace(H)), M, H, N, st))
+    return dx, dh_prev, dw_ih, dw_hh, db_ih, db_hh
+
+
+def _pack_weights(kind, w_ih, w_hh, out):
+    """[W_ih | W_hh] in the fragment order of the `kind` ('lstm' / 'gru') cell kernel (shf_<kind>_pack_weights); `out`: a
+    kept buffer to refill, or None."""
+    L = ml.lib()
+    H, I = w_hh.shape[1], w_ih.shape[1]
+    with torch.cuda.device(w_ih.device):
+        if out is None:
+            n = C.c_int64()
+            ml._check(getattr(L, f"shf_{kind}_pack_bytes")(I, H, C.byref(n)))
+            out = torch.empty(n.value, device=w_ih.device, dtype=torch.uint8)
+        ml._check(getattr(L, f"shf_{kind}_pack_weights")(ml._ptr(w_ih), ml._ptr(w_hh), ml._ptr(out), I, H, ml._stream(w_ih)))
+    return out
+
+
 class _LstmCellFn(torch.autograd.Function):
     """One LSTM cell step on shf_lstm_cell_forward; backward = the pointwise kernel + the MLP layers' gradient GEMMs on the
     raw weights.  `reset`: uint8 (M,), nonzero rows take h_prev = c_prev = 0 (or None)."""
@@ -53,33 +103,11 @@ class _LstmCellFn(torch.autograd.Function):
         dh, dc = dh.contiguous(), dc.contiguous()
         dgates = torch.empty_like(gates)
         dc_prev = torch.empty_like(c_prev)
-        rp = None if reset is None else ml._ptr(reset)
-        keep = None if reset is None else (1.0 - reset.to(torch.float32)).unsqueeze(1)
-        dx = dh_prev = dw_ih = dw_hh = db = None
         with torch.cuda.device(x.device):
-            st = ml._stream(x)
-            ml._check(L.shf_lstm_cell_backward_pointwise(ml._ptr(dh), ml._ptr(dc), ml._ptr(gates), ml._ptr(c_prev), rp, ml._ptr(c),
-                                                         ml._ptr(dgates), ml._ptr(dc_prev), M, H, st))
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                ml._check(L.shf_mlp_linear_backward_input(ml._ptr(dgates), None, ml._ptr(w_ih), ml._ptr(dx), M, I, 4 * H, st))
-            if ctx.needs_input_grad[1]:
-                dh_prev = torch.empty_like(h_prev)
-                ml._check(L.shf_mlp_linear_backward_input(ml._ptr(dgates), None, ml._ptr(w_hh), ml._ptr(dh_prev), M, H, 4 * H, st))
-                if keep is not None:
-                    dh_prev = dh_prev * keep
-            if any(ctx.needs_input_grad[4:8]):
-                def workspace(K):
-                    n = C.c_int64()
-                    ml._check(L.shf_mlp_backward_weight_workspace(M, K, 4 * H, C.byref(n)))
-                    return torch.empty(n.value, device=x.device, dtype=torch.float32)
-                dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
-                db = torch.empty(4 * H, device=x.device, dtype=torch.float32)
-                ml._check(L.shf_mlp_linear_backward_weight(ml._ptr(dgates), None, ml._ptr(x), ml._ptr(dw_ih), ml._ptr(db), ml._ptr(workspace(I)),
-                                                           M, I, 4 * H, st))
-                h_eff = h_prev if keep is None else h_prev * keep
-                ml._check(L.shf_mlp_linear_backward_weight(ml._ptr(dgates), None, ml._ptr(h_eff), ml._ptr(dw_hh), None, ml._ptr(workspace(H)),
-                                                           M, H, 4 * H, st))
+            ml._check(L.shf_lstm_cell_backward_pointwise(ml._ptr(dh), ml._ptr(dc), ml._ptr(gates), ml._ptr(c_prev), None if reset is None else ml._ptr(reset), ml._ptr(c),
+                                                         ml._ptr(dgates), ml._ptr(dc_prev), M, H, ml._stream(x)))
+            dx, dh_prev, dw_ih, dw_hh, db, _ = _gradient_gemms(x, h_prev, reset, w_ih, w_hh, dgates, dgates, 4 * H, ctx.needs_input_grad[0],
+                                                               ctx.needs_input_grad[1], any(ctx.needs_input_grad[4:8]))
         if not ctx.needs_input_grad[2]:
             dc_prev = None
         return dx, dh_prev, dc_prev, None, dw_ih, dw_hh, db, (None if db is None else db.clone()), None
@@ -87,14 +115,7 @@ class _LstmCellFn(torch.autograd.Function):
 
 def pack_lstm_weights(w_ih, w_hh, out=None):
     """[W_ih | W_hh] in the cell kernel's fragment order (shf_lstm_pack_weights); `out`: a kept buffer to refill."""
-    H, I = w_hh.shape[1], w_ih.shape[1]
-    with torch.cuda.device(w_ih.device):
-        if out is None:
-            n = C.c_int64()
-            ml._check(ml.lib().shf_lstm_pack_bytes(I, H, C.byref(n)))
-            out = torch.empty(n.value, device=w_ih.device, dtype=torch.uint8)
-        ml._check(ml.lib().shf_lstm_pack_weights(ml._ptr(w_ih), ml._ptr(w_hh), ml._ptr(out), I, H, ml._stream(w_ih)))
-    return out
+    return _pack_weights("lstm", w_ih, w_hh, out)
 
 
 def lstm_cell(x, h_prev, c_prev, reset, w_ih, w_hh, b_ih, b_hh, pack=None):
@@ -136,48 +157,19 @@ class _GruCellFn(torch.autograd.Function):
         dgx = torch.empty(M, 3 * H, device=x.device, dtype=torch.float32)
         dgh = torch.empty_like(dgx)
         dh_direct = torch.empty_like(h_prev)
-        rp = None if reset is None else ml._ptr(reset)
-        keep = None if reset is None else (1.0 - reset.to(torch.float32)).unsqueeze(1)
-        dx = dh_prev = dw_ih = dw_hh = db_ih = db_hh = None
         with torch.cuda.device(x.device):
-            st = ml._stream(x)
-            ml._check(L.shf_gru_cell_backward_pointwise(ml._ptr(dh), ml._ptr(gates), ml._ptr(h_prev), rp, ml._ptr(dgx), ml._ptr(dgh),
-                                                        ml._ptr(dh_direct), M, H, st))
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                ml._check(L.shf_mlp_linear_backward_input(ml._ptr(dgx), None, ml._ptr(w_ih), ml._ptr(dx), M, I, 3 * H, st))
-            if ctx.needs_input_grad[1]:
-                dh_prev = torch.empty_like(h_prev)
-                ml._check(L.shf_mlp_linear_backward_input(ml._ptr(dgh), None, ml._ptr(w_hh), ml._ptr(dh_prev), M, H, 3 * H, st))
-                if keep is not None:
-                    dh_prev = dh_prev * keep
+            ml._check(L.shf_gru_cell_backward_pointwise(ml._ptr(dh), ml._ptr(gates), ml._ptr(h_prev), None if reset is None else ml._ptr(reset), ml._ptr(dgx), ml._ptr(dgh),
+                                                        ml._ptr(dh_direct), M, H, ml._stream(x)))
+            dx, dh_prev, dw_ih, dw_hh, db_ih, db_hh = _gradient_gemms(x, h_prev, reset, w_ih, w_hh, dgx, dgh, 3 * H, ctx.needs_input_grad[0],
+                                                                      ctx.needs_input_grad[1], any(ctx.needs_input_grad[3:7]))
+            if dh_prev is not None:
                 dh_prev = dh_prev + dh_direct
-            if any(ctx.needs_input_grad[3:7]):
-                def workspace(K):
-                    n = C.c_int64()
-                    ml._check(L.shf_mlp_backward_weight_workspace(M, K, 3 * H, C.byref(n)))
-                    return torch.empty(n.value, device=x.device, dtype=torch.float32)
-                dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
-                db_ih = torch.empty(3 * H, device=x.device, dtype=torch.float32)
-                db_hh = torch.empty_like(db_ih)
-                ml._check(L.shf_mlp_linear_backward_weight(ml._ptr(dgx), None, ml._ptr(x), ml._ptr(dw_ih), ml._ptr(db_ih), ml._ptr(workspace(I)),
-                                                           M, I, 3 * H, st))
-                h_eff = h_prev if keep is None else h_prev * keep
-                ml._check(L.shf_mlp_linear_backward_weight(ml._ptr(dgh), None, ml._ptr(h_eff), ml._ptr(dw_hh), ml._ptr(db_hh), ml._ptr(workspace(H)),
-                                                           M, H, 3 * H, st))
         return dx, dh_prev, None, dw_ih, dw_hh, db_ih, db_hh, None
 
 
 def pack_gru_weights(w_ih, w_hh, out=None):
     """[W_ih | W_hh] in the GRU cell kernel's fragment order (shf_gru_pack_weights); `out`: a kept buffer to refill."""
-    H, I = w_hh.shape[1], w_ih.shape[1]
-    with torch.cuda.device(w_ih.device):
-        if out is None:
-            n = C.c_int64()
-            ml._check(ml.lib().shf_gru_pack_bytes(I, H, C.byref(n)))
-            out = torch.empty(n.value, device=w_ih.device, dtype=torch.uint8)
-        ml._check(ml.lib().shf_gru_pack_weights(ml._ptr(w_ih), ml._ptr(w_hh), ml._ptr(out), I, H, ml._stream(w_ih)))
-    return out
+    return _pack_weights("gru", w_ih, w_hh, out)
 
 
 def gru_cell(x, h_prev, reset, w_ih, w_hh, b_ih, b_hh, pack=None):
@@ -215,9 +207,8 @@ class Memory(nn.Module):
         with torch.no_grad():
             if self._pack is None or self._pack[0].device != w.device:
                 self._pack = [None] * self.rnn.num_layers
-            pack_weights = pack_lstm_weights if self.kind == "lstm" else pack_gru_weights
             for l in range(self.rnn.num_layers):
-                self._pack[l] = pack_weights(getattr(self.rnn, f"weight_ih_l{l}"), getattr(self.rnn, f"weight_hh_l{l}"), self._pack[l])
+                self._pack[l] = _pack_weights(self.kind, getattr(self.rnn, f"weight_ih_l{l}"), getattr(self.rnn, f"weight_hh_l{l}"), self._pack[l])
         self._pack_valid = True
 
     def invalidate_pack(self):
@@ -266,6 +257,12 @@ class Memory(nn.Module):
     def _use_kernel(self, x):
         return self.fused and x.is_cuda and x.dtype == torch.float32 and self.rnn.bias
 
+    def _cell(self, l, inp, state, reset, pack=None):
+        """One fused cell step of layer l from its `state` -- (h, c) for LSTM, (h,) for GRU -- to its new state, same form."""
+        if self.kind == "lstm":
+            return lstm_cell(inp, state[0], state[1], reset, *self._layer_params(l), pack)
+        return (gru_cell(inp, state[0], reset, *self._layer_params(l), pack),)
+
     # ------------------------------------------------------------------ step mode
     def forward(self, x, masks=None, hidden_states=None, advance=True):
         """x (N, D) -> (N, H), advancing the module's hidden state (advance=False: the output only, state untouched)."""
@@ -278,16 +275,11 @@ class Memory(nn.Module):
             inp = x
             packs = self._pack if (self._pack_valid and not torch.is_grad_enabled()) else None
             for l in range(self.rnn.num_layers):
-                pack = None if packs is None else packs[l]
-                if self.kind == "lstm":
-                    h, c = lstm_cell(inp, state[0][l], state[1][l], None, *self._layer_params(l), pack)
-                else:
-                    h, c = gru_cell(inp, state[0][l], None, *self._layer_params(l), pack), None
+                new = self._cell(l, inp, [s[l] for s in state], None, None if packs is None else packs[l])
                 with torch.no_grad():
-                    nxt[0][l].copy_(h)
-                    if c is not None:
-                        nxt[1][l].copy_(c)
-                inp = h
+                    for d, s in zip(nxt, new):
+                        d[l].copy_(s)
+                inp = new[0]
             out = inp
         else:
             out, new = self.rnn(x.unsqueeze(0), state if self.kind == "lstm" else state[0])
@@ -311,17 +303,13 @@ class Memory(nn.Module):
         outs = []
         if self._use_kernel(obs):
             rb = dones.to(torch.uint8)
-            h = [init[0][l] for l in range(self.rnn.num_layers)]
-            c = [init[1][l] for l in range(self.rnn.num_layers)] if self.kind == "lstm" else None
+            state = [[s[l] for s in init] for l in range(self.rnn.num_layers)]
             for t in range(T):
                 reset = None if t == 0 else rb[t - 1].contiguous()
                 inp = obs[t]
                 for l in range(self.rnn.num_layers):
-                    if self.kind == "lstm":
-                        h[l], c[l] = lstm_cell(inp, h[l], c[l], reset, *self._layer_params(l))
-                    else:
-                        h[l] = gru_cell(inp, h[l], reset, *self._layer_params(l))
-                    inp = h[l]
+                    state[l] = self._cell(l, inp, state[l], reset)
+                    inp = state[l][0]
                 outs.append(inp)
             return torch.cat(outs, dim=0)
         state = [s for s in init]

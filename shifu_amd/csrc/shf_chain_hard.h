@@ -25,6 +25,15 @@
 #include "shf_chain.h"
 
 #define UF_STRIDE 8     /* U[6] invD . per link */
+// chain_substep_hard's SLOTS (the sweep of the fused KC = 8 forms):
+#define SLOT_ROW 1      /* the register row of W resident before the sweeps: no staged s_waitcnt inside the visits */
+#define SLOT_COUNT 2    /* no test of the visit's number against the wavefront's constraint count: the skip rule covers it */
+#define SLOT_COUNT4 4   /* (with SLOT_COUNT) the count test kept at one place, in front of visit 4 */
+#define SLOT_MAX 8      /* the sliding step's floor under lim^2 as one v_max_f32 (hard_max_lit) */
+#define SLOT_TAKE 16    /* TGS: the taking lanes' mask by one s_bfe_i32 per half (hard_bit_mask) */
+#ifndef SHF_SWEEP_SLOTS  /* (measurement builds set it: profiles/r24_sweep_slots.md) */
+#define SHF_SWEEP_SLOTS (SLOT_ROW | SLOT_COUNT | SLOT_MAX | SLOT_TAKE)
+#endif
 // LDS of the solve, KC = the constraints it holds (ShfSimParams.max_contacts <= KC):
 //   KC = 8  everything inside the contact-slot region: constraint records | W, KC x KC blocks of 9 words | U, 1/D per link
 //   KC = 16 W is symmetric (block (j, i) = block (i, j)^T: oracle hard_solve), so only its upper triangle is kept -- KC (KC + 1) / 2
@@ -466,6 +475,9 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
   // with its wait: the fused KC = 8 forms under PGS (+2.7 %); under TGS it measured slower (-0.4 %), the KC = 16 forms and the
   // hook path's sub-step were not measured and keep the read-modify-write (profiles/r12_cap_select.md)
   constexpr bool DROPATOM = WR > 0 && !TGS;
+  // the issue slots of a sweep visit that compute nothing (H3, KC = 8 with the register row; profiles/r24_sweep_slots.md), a
+  // set of SLOT_* bits.  A form without a bit keeps the code it had.
+  constexpr int SLOTS = WR > 0 ? SHF_SWEEP_SLOTS : 0;
   const ShfModel* m = C.m;
   const float dt = C.sp.dt, idt = 1.0f / dt;
   const float gon = (float)m->gravity_on;
@@ -1073,7 +1085,11 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
         float q1 = fmaf(-O.rt, ut1, O.p[1]), q2 = fmaf(-O.rt, ut2, O.p[2]);
         const float nt2 = fmaf(q2, q2, q1 * q1);
         const float rs = lim * rsqrt_spec(nt2);
-        const float sc1 = nt2 > rmaxf(lim2, 1e-30f) ? rs : 1.0f;   // (1e-30: a subnormal |p_t|^2 over a zero cone would make 0 * inf)
+        // (1e-30: a subnormal |p_t|^2 over a zero cone would make 0 * inf.  SLOT_MAX: lim2 is a product, hard_max_lit's case)
+        float floor2;
+        if constexpr ((SLOTS & SLOT_MAX) != 0) floor2 = hard_max_lit<__builtin_bit_cast(unsigned, 1e-30f)>(lim2);
+        else floor2 = rmaxf(lim2, 1e-30f);
+        const float sc1 = nt2 > floor2 ? rs : 1.0f;
         q1 *= sc1; q2 *= sc1;
         ps1 = slide ? q1 : ps1; ps2 = slide ? q2 : ps2;
       }
@@ -1081,12 +1097,18 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
       // wave lanes c and 32 + c) is its change, pn - pn0 = dn, ... as that lane computed it
       float d0 = dn, d1 = ps1 - O.p[1], d2 = ps2 - O.p[2];
       bool take;
+      // (SLOT_TAKE: the impulses are taken before the mask below is derived from cm's halves -- cm is dead behind them, and
+      // hard_bit_mask's words stay in cm's registers instead of going through copies)
+      constexpr bool TAKE1 = TGS && (SLOTS & SLOT_TAKE) != 0;
+      if constexpr (TAKE1) { hard_take(O.p[0], pn, cm); hard_take(O.p[1], ps1, cm); hard_take(O.p[2], ps2, cm); }
       if constexpr (TGS) {
         // ... as it stands, and only the lanes of the envs whose contact c commits take it (bit c of cm: env A's half of the
         // wavefront, bit 32 + c: env B's).  The other env's lanes keep u bit for bit -- its -0.0 too, and W's blocks of the columns
         // c >= K are uninitialised LDS.  (A committing env has c < K; its lanes l >= K own nothing, and nothing reads their u.)
         const unsigned ca = (unsigned)cm, cb = (unsigned)(cm >> 32);
-        const unsigned ta = (unsigned)((int)(ca << (31 - c)) >> 31), tb = (unsigned)((int)(cb << (31 - c)) >> 31);
+        unsigned ta, tb;
+        if constexpr ((SLOTS & SLOT_TAKE) != 0) { ta = hard_bit_mask<c>(ca); tb = hard_bit_mask<c>(cb); }
+        else { ta = (unsigned)((int)(ca << (31 - c)) >> 31); tb = (unsigned)((int)(cb << (31 - c)) >> 31); }
         take = __builtin_amdgcn_inverse_ballot_w64((unsigned long long)ta | ((unsigned long long)tb << 32));
       } else {
         // ... or exactly 0 from a lane that does not commit, to the owner lanes.  (PGS: gated as above, k_a1_chain_pgs<0,0> is
@@ -1095,7 +1117,7 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
         d0 = commit ? d0 : 0.0f; d1 = commit ? d1 : 0.0f; d2 = commit ? d2 : 0.0f;
         take = own && c < K;
       }
-      hard_take(O.p[0], pn, cm); hard_take(O.p[1], ps1, cm); hard_take(O.p[2], ps2, cm);
+      if constexpr (!TAKE1) { hard_take(O.p[0], pn, cm); hard_take(O.p[1], ps1, cm); hard_take(O.p[2], ps2, cm); }
       const float b0 = hard_row_bcast<c>(d0), b1 = hard_row_bcast<c>(d1), b2 = hard_row_bcast<c>(d2);
 #pragma unroll
       for (int r = 0; r < 3; r++) {
@@ -1157,6 +1179,15 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
     };
     const HardTgs TG = hard_tgs(C.sp, npos);      // SHF_SOLVER_TGS: sub-stepped sweeps (csrc/shf_hard.h); compiled in when TGS
     float psum[3] = {0.0f, 0.0f, 0.0f};
+    // SLOT_ROW: the whole register row resident here (the idiom of StagedBlock::pin), so that the waits for it stand in front of
+    // the sweeps.  Left to the compiler each block's wait stands in front of its first use, inside the visit, and every one of
+    // the sub-step's npos + nvel sweeps issues all of them although only the first can ever wait.
+    if constexpr ((SLOTS & SLOT_ROW) != 0) {
+#pragma unroll
+      for (int c = 0; c < WR; c++)
+        asm volatile("" : "+v"(Wrow[c][0]), "+v"(Wrow[c][1]), "+v"(Wrow[c][2]), "+v"(Wrow[c][3]), "+v"(Wrow[c][4]), "+v"(Wrow[c][5]),
+                     "+v"(Wrow[c][6]), "+v"(Wrow[c][7]), "+v"(Wrow[c][8]));
+    }
 #pragma unroll 1
     for (int phase = 0; phase < 2; phase++) {
       const int sweeps = phase == 0 ? npos : nvel;
@@ -1176,7 +1207,12 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
           const unsigned long long pnz = __ballot(O.p[0] != 0.0f) | __ballot(O.p[1] != 0.0f) | __ballot(O.p[2] != 0.0f);
           hard_static_while<0, KC>([&](auto cc) {
             constexpr int c = decltype(cc)::value;
-            if (c >= Kw) return false;
+            // SLOT_COUNT: no count test.  ownm has no bit for a contact c >= K of either env, so a visit c >= Kw finds cm == 0
+            // and returns by the skip rule; the test spared the wavefronts with few contacts, which are not the ones the
+            // launch waits for, and cost every visit of the full ones two slots.  (SLOT_COUNT4: kept in front of visit 4)
+            if constexpr ((SLOTS & SLOT_COUNT) == 0 || ((SLOTS & SLOT_COUNT4) != 0 && c == 4)) {
+              if (c >= Kw) return false;
+            }
             if constexpr (c + 1 < KC && c + 1 >= WR) wload8(c + 1, Wb[c + 1]);
             if constexpr (c < WR) visit8(cc, tg, pnz, Wrow[c]); else visit8(cc, tg, pnz, Wb[c]);
             return true;

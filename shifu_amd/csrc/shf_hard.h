@@ -76,6 +76,26 @@ DEV float hard_row_bcast(float x) {
 DEV void hard_take(float& x, float a, unsigned long long lanes) {
   asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(x) : "v"(a), "s"(lanes));
 }
+// max(x, the constant with the bits BITS) as one v_max_f32 with a literal operand.  rmaxf(x, b) = x > b ? x : b compiles to
+// the same v_max_f32 behind a canonicalising v_max_f32 x, x, x, which is there for a signalling NaN.  The two agree bit for bit
+// when x is the result of an arithmetic instruction (never a signalling NaN; a quiet NaN gives the constant either way) and the
+// kernel keeps f32 denormals, as these do: x is then canonical already.  For the contact sweep only (x = lim * lim).
+template <unsigned BITS>
+DEV float hard_max_lit(float x) {
+  float r;
+  asm("v_max_f32 %0, %2, %1" : "=v"(r) : "v"(x), "i"(BITS));
+  return r;
+}
+// bit c of the wave-uniform word x sign-extended, 0 or ~0u: one s_bfe_i32.  x goes through an empty asm, so that the compiler
+// does not see which 64-bit mask it is a half of: for the high half it otherwise shifts the whole mask right and sign-extends the
+// result (s_lshr_b64, s_ashr_i32).  (s_bfe_i32 itself in an asm, or __builtin_amdgcn_sbfe, does not do: behind an asm that
+// writes an SGPR the compiler pads with s_nop, and the builtin is rewritten into the same shifts.)
+template <int c>
+DEV unsigned hard_bit_mask(unsigned x) {
+  static_assert(c >= 0 && c < 32, "a bit of a 32-bit word");
+  asm("" : "+s"(x));
+  return (unsigned)((int)(x << (31 - c)) >> 31);
+}
 // hard_static_while<C, N>(f): f(HardIdx<C>()), .. f(HardIdx<N - 1>()) while f returns true -- an unrolled loop whose index is a
 // constant expression in every copy, each copy nested in the one before (what one copy computes is there for the next, no copies)
 template <int N>

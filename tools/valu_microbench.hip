@@ -142,6 +142,19 @@ __global__ void k_bench(Out* out, float seed, int lanes) {
         asm volatile(R16("v_addc_co_u32 %0, vcc, %0, %4, vcc\n v_addc_co_u32 %1, vcc, %1, %4, vcc\n v_addc_co_u32 %2, vcc, %2, %4, vcc\n v_addc_co_u32 %3, vcc, %3, %4, vcc\n")
                      : "+v"(u0), "+v"(u1), "+v"(u2), "+v"(u3) : "v"(idx) : "vcc");
         idx = u0 + u1 + u2 + u3;
+      } else if constexpr (TEST >= 29 && TEST <= 34) {
+        // one non-arithmetic instruction per four dependent v_fma_f32 (16 such groups per iteration): what the slot adds to the
+        // stream.  The wait is satisfied (nothing is outstanding), the branches are never taken (vcc = 0, scc = 0).
+#define SLOT_STREAM(x) asm volatile("s_mov_b64 vcc, 0\n s_mov_b64 s[22:23], -1\n s_mov_b64 s[24:25], 5\n s_cmp_lg_u32 0, 0\n" \
+                                    R16("v_fma_f32 %0, %0, %1, %2\n v_fma_f32 %0, %0, %1, %2\n v_fma_f32 %0, %0, %1, %2\n v_fma_f32 %0, %0, %1, %2\n" x) \
+                                    : "+v"(a0) : "v"(b), "v"(c) : "vcc", "scc", "s20", "s21", "s22", "s23", "s24", "s25")
+        if constexpr (TEST == 29) SLOT_STREAM("s_waitcnt lgkmcnt(7)\n");
+        else if constexpr (TEST == 30) SLOT_STREAM("s_and_b64 s[20:21], s[22:23], s[24:25]\n");
+        else if constexpr (TEST == 31) SLOT_STREAM("s_bfe_i32 s20, s24, 0x10002\n");
+        else if constexpr (TEST == 32) SLOT_STREAM("s_cbranch_vccnz 1f\n1:\n");
+        else if constexpr (TEST == 33) SLOT_STREAM("s_cmp_lg_u32 0, 0\n s_cbranch_scc1 1f\n1:\n");
+        else SLOT_STREAM("v_max_f32 %0, %0, %0\n");
+#undef SLOT_STREAM
       } else if constexpr (TEST == 17) { // SALU dependent chain
         unsigned s = (unsigned)it;
         asm volatile(R64("s_add_u32 %0, %0, 3\n") : "+s"(s));
@@ -170,13 +183,19 @@ static const Test TESTS[] = {
     {21, "v_max_f32 / v_min_f32, 4 independent", 64}, {22, "ds_write_b128 + ds_read_b128 round trip", 64},
     {23, "7 x ds_read_b128 in flight + wait (per 7 reads)", 64}, {24, "global_load_dword pointer chase (L2)", 64},
     {25, "v_cndmask_b32_e64 with vcc as mask, 8 independent", 128}, {26, "v_cmp (vcc) + v_cndmask_e32 pair", 32},
-    {27, "v_cmp_e64 (sgpr) + v_cndmask_e64 pair", 32}, {28, "v_addc_co_u32 (vcc in/out), 4 independent", 64}};
+    {27, "v_cmp_e64 (sgpr) + v_cndmask_e64 pair", 32}, {28, "v_addc_co_u32 (vcc in/out), 4 independent", 64},
+    // (per group of four dependent v_fma_f32 and the one slot: the `slots` table below subtracts the four)
+    {29, "4 dep. v_fma_f32 + s_waitcnt lgkmcnt(7), satisfied", 16}, {30, "4 dep. v_fma_f32 + s_and_b64", 16},
+    {31, "4 dep. v_fma_f32 + s_bfe_i32", 16}, {32, "4 dep. v_fma_f32 + s_cbranch_vccnz, not taken", 16},
+    {33, "4 dep. v_fma_f32 + s_cmp_lg_u32 + s_cbranch_scc1, not taken", 16}, {34, "4 dep. v_fma_f32 + v_max_f32 v, v, v", 16}};
+constexpr int SLOT_FIRST = 29, SLOT_LAST = 34;
 
 template <int T> static void launch(Out* d, int blocks, int threads, int lanes) { hipLaunchKernelGGL(k_bench<T>, dim3(blocks), dim3(threads), 0, 0, d, 1.0f, lanes); }
 typedef void (*Launcher)(Out*, int, int, int);
 static const Launcher LAUNCH[] = {launch<0>, launch<1>, launch<2>, launch<3>, launch<4>, launch<5>, launch<6>, launch<7>, launch<8>, launch<9>,
                                   launch<10>, launch<11>, launch<12>, launch<13>, launch<14>, launch<15>, launch<16>, launch<17>, launch<18>,
-                                  launch<19>, launch<20>, launch<21>, launch<22>, launch<23>, launch<24>, launch<25>, launch<26>, launch<27>, launch<28>};
+                                  launch<19>, launch<20>, launch<21>, launch<22>, launch<23>, launch<24>, launch<25>, launch<26>, launch<27>, launch<28>,
+                                  launch<29>, launch<30>, launch<31>, launch<32>, launch<33>, launch<34>};
 
 int main(int argc, char** argv) {
   hipDeviceProp_t p;
@@ -200,6 +219,7 @@ int main(int argc, char** argv) {
   hipEvent_t e0, e1;
   CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
   const int WS[] = {1, 2, 4};
+  double wave_clk[64][2] = {};       // clocks per pattern as one wave sees them, all lanes: [test][W - 1]
   printf("| pattern | lanes | W=1 wave | W=1 SIMD | W=2 wave | W=2 SIMD | W=4 wave | W=4 SIMD | GHz (W=1) |\n|---|---:|---:|---:|---:|---:|---:|---:|---:|\n");
   for (const Test& t : TESTS) {
     if (argc > 1) { bool want = false; for (int a = 1; a < argc; a++) want |= atoi(argv[a]) == t.id; if (!want) continue; }
@@ -225,8 +245,19 @@ int main(int argc, char** argv) {
         const double med = (double)tk[nw / 2], n = (double)ITER * t.per_iter;
         printf(" %.2f | %.2f |", med / n, med / n / W);
         if (W == 1) ghz1 = (double)tk[nw - 1] / (ms * 1e6);
+        if (lanes == 64 && W <= 2) wave_clk[t.id][W - 1] = med / n;
       }
       printf(" %.2f |\n", ghz1);
+    }
+  }
+  // the slot rows against the plain stream: clocks per added instruction as the wave sees them (the scc row adds two)
+  if (wave_clk[0][0] > 0.0) {
+    bool head = false;
+    for (const Test& t : TESTS) {
+      if (t.id < SLOT_FIRST || t.id > SLOT_LAST || wave_clk[t.id][0] <= 0.0) continue;
+      if (!head) printf("\n| slots: clocks the group of four v_fma_f32 gains | W=1 wave | W=2 wave |\n|---|---:|---:|\n");
+      head = true;
+      printf("| %s | %.2f | %.2f |\n", t.name, wave_clk[t.id][0] - 4.0 * wave_clk[0][0], wave_clk[t.id][1] - 4.0 * wave_clk[0][1]);
     }
   }
   printf("\nNotes: a pattern instance of the round-trip / branch rows is several instructions (see the source); "

@@ -1018,6 +1018,55 @@ int shf_gait_plan(const float* root_pose, int64_t root_env_stride, const float* 
 int shf_leg_effort_mix(const float* stance_efforts, const float* swing_efforts, const uint8_t* stance, const uint8_t* chain_mask,
                        const float* effort_limit_or_null, int32_t n, int32_t num_feet, int32_t num_dof, float* efforts_out,
                        void* stream);
+/* ---- the horizon form of the stance forces: convex MPC over the gait schedule (csrc/shf_mpc.hip, whose header states the
+ * three algorithms step by step).  State x = (Theta (roll, pitch, yaw), p, omega, v), horizon H in 1..SHF_MPC_MAX_HORIZON
+ * steps of delta = ticks_per_step * dt seconds, unknowns u (n, H, num_feet, 3).  Additive: no new SHF_ABI_VERSION. */
+#define SHF_MPC_MAX_HORIZON 10
+/* The MPC's three tables, one thread per env, from the GaitState as shf_gait_plan left it THIS tick (the stored tick has
+ * already been advanced: this tick's clock is tick - 1) -- tick (n) int32, target (n, 13), yaw (n) -- the gait's HOST arrays
+ * as for shf_gait_plan, this tick's stance (n, num_feet) uint8 (shf_gait_plan's stance_out), foot f's world origin at
+ * foot_pos + e * foot_env_stride + f * foot_stride, command (n, 3), nominal (num_feet, 3) and the planner's scalars:
+ *   contact_out (n, H, num_feet) uint8: row 0 = stance; row k >= 1 = ((tick - 1) + k ticks_per_step + offset_f) mod P <
+ *     stance_ticks_f (integers only);
+ *   xref_out (n, H + 1, 12): the base target rolled forward by k delta (row 0 is "now");
+ *   pos_out (n, H, num_feet, 3) world: foot_pos while the contact of step 0 lasts, the foothold predicted at its first step
+ *     (hip + clamp_norm(v_des T_stance / 2, max_step) on the reference path, z = touchdown_z) for every later contact run,
+ *     +0.0 where contact is 0.
+ * Refused with a message: horizon outside 1..SHF_MPC_MAX_HORIZON, ticks_per_step < 1, num_feet outside 1..4, the schedule
+ * checks of shf_gait_plan, dt <= 0, max_step < 0, a null tensor. */
+int shf_mpc_horizon(const int32_t* tick, const float* target, const float* yaw, int32_t period_ticks, const int32_t* offset_ticks,
+                    const int32_t* stance_ticks, const uint8_t* stance, const float* foot_pos, int64_t foot_env_stride,
+                    int64_t foot_stride, const float* command, const float* nominal, ShfGaitParams params, int32_t horizon,
+                    int32_t ticks_per_step, int32_t n, int32_t num_feet, uint8_t* contact_out, float* xref_out, float* pos_out,
+                    void* stream);
+/* The solve, one workgroup per env: with M6 = mass_matrix[0:6, 0:6] and h6 = dyn_bias[0:6] frozen over the horizon,
+ *   (v', omega')_k = M6^-1 (sum_f c_kf (u_kf; r_kf x u_kf) - h6),  r_kf = pos_kf - (p_root + p_ref,k - p_ref,0),
+ *   Theta_k+1 = Theta_k + delta Rz(psi_ref,k)^T omega_k,  p_k+1 = p_k + delta v_k,  (v, omega)_k+1 = (v, omega)_k + delta (v', omega')_k,
+ *   minimise 1/2 sum_k=1..H (x_k - xref_k)^T diag(weights12) (x_k - xref_k) + 1/2 alpha |u|^2,
+ *   contact: fz_min <= u_z <= fz_max, |u_x|, |u_y| <= mu u_z;  no contact: u = 0,
+ * condensed to 3 num_feet H variables and solved by `iters` sweeps of shf_foot_force_qp's ADMM on an explicit inverse kept in
+ * LDS (a fixed trip count).  forces_out (n, num_feet, 3) is step 0, clamped per foot as shf_foot_force_qp clamps, so that
+ * every inequality holds exactly; efforts_out (n, num_dof) as shf_foot_force_qp's.  u_io (n, H, num_feet, 3) or NULL: read as
+ * the starting point, shifted by warm_shift steps (the last row repeated), and overwritten with the clamped solution.  Tables
+ * of shf_mpc_horizon, contiguous; the root's 13-float row at root_pose + e * root_env_stride; mass_matrix (n, D, D), dyn_bias
+ * (n, D), D = num_dof + 6, contiguous; j_feet as for shf_foot_force_qp; mu (n) or NULL for mu_scalar; weights12 (12); bias (n,
+ * D) and effort_limit (num_dof) or NULL.  Refused with a message: horizon outside 1..SHF_MPC_MAX_HORIZON, num_feet outside
+ * 1..4, num_dof outside 1..SHF_MAX_DOFS, alpha <= 0, fz_min > fz_max, mu_scalar < 0, iters < 1, step_dt <= 0, warm_shift < 0,
+ * a null required tensor. */
+int shf_foot_force_mpc(const uint8_t* contact, const float* xref, const float* pos, const float* root_pose,
+                       int64_t root_env_stride, const float* mass_matrix, const float* dyn_bias, const float* j_feet,
+                       int64_t j_env_stride, int64_t j_foot_stride, const float* mu_or_null, float mu_scalar,
+                       const float* weights12, float alpha, float fz_min, float fz_max, int32_t iters, float step_dt,
+                       const float* bias_or_null, const float* effort_limit_or_null, float* u_io_or_null, int32_t warm_shift,
+                       int32_t n, int32_t horizon, int32_t num_feet, int32_t num_dof, float* forces_out, float* efforts_out,
+                       void* stream);
+/* The effort step of the two solvers on its own, one thread per env: efforts_out (n, num_dof) = -sum_f Jl_f^T f_f over the feet
+ * with stance[e, f] != 0 (the others' forces count as zero), + bias[e, 6 + d], the clamp to +-effort_limit[d] last -- bit-equal
+ * to what shf_foot_force_mpc writes for the same forces, so that held forces can ride the current Jacobian between two solves.
+ * forces (n, num_feet, 3), stance (n, num_feet) uint8: contiguous; j_feet, bias, effort_limit as above. */
+int shf_foot_force_efforts(const float* forces, const uint8_t* stance, const float* j_feet, int64_t j_env_stride,
+                           int64_t j_foot_stride, const float* bias_or_null, const float* effort_limit_or_null, int32_t n,
+                           int32_t num_feet, int32_t num_dof, float* efforts_out, void* stream);
 /* ShifuVecEnv.compute_reward's accumulation (env.py:180-185): rew = terms[0] + terms[1] + ... in that order,
  * sums[k] += terms[k]; HOST arrays of num_keys <= 16 device pointers to (num_envs) fp32 tensors. */
 int shf_reward_accumulate(const float* const* terms, float* const* sums, int32_t num_keys, int64_t num_envs, float* rew,

@@ -127,6 +127,9 @@ class ShfGaitParams(C.Structure):      # shf_gait_plan's scalars, passed by valu
                 ("max_step", f32), ("leash", f32), ("contact_threshold", f32)]
 
 
+MPC_MAX_HORIZON = 10                   # SHF_MPC_MAX_HORIZON: steps of shf_mpc_horizon / shf_foot_force_mpc (csrc/shf_mpc.hip)
+
+
 class ShfA1TaskParams(C.Structure):
     _fields_ = [
         ("decimation", i32), ("extra_substep", i32), ("num_history", i32), ("num_height_points", i32),

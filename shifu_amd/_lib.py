@@ -105,6 +105,18 @@ _SIGS = {
                        vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp], i32),
     # stance_efforts, swing_efforts, stance, chain_mask, effort_limit, n, num_feet, num_dof, efforts_out, stream
     "shf_leg_effort_mix": ([vp, vp, vp, vp, vp, i32, i32, i32, vp, vp], i32),
+    # the horizon MPC (csrc/shf_mpc.hip).  tick, target, yaw, period_ticks, offset_ticks (host), stance_ticks (host), stance,
+    # foot_pos, foot_env_stride, foot_stride, command, nominal, params (by value), horizon, ticks_per_step, n, num_feet,
+    # contact_out, xref_out, pos_out, stream
+    "shf_mpc_horizon": ([vp, vp, vp, i32, C.POINTER(i32), C.POINTER(i32), vp, vp, i64, i64, vp, vp, _abi.ShfGaitParams, i32, i32, i32,
+                         i32, vp, vp, vp, vp], i32),
+    # contact, xref, pos, root_pose, root_env_stride, mass_matrix, dyn_bias, j_feet, j_env_stride, j_foot_stride, mu, mu_scalar,
+    # weights12, alpha, fz_min, fz_max, iters, step_dt, bias, effort_limit, u_io, warm_shift, n, horizon, num_feet, num_dof,
+    # forces_out, efforts_out, stream
+    "shf_foot_force_mpc": ([vp, vp, vp, vp, i64, vp, vp, vp, i64, i64, vp, C.c_float, vp, C.c_float, C.c_float, C.c_float, i32,
+                            C.c_float, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp], i32),
+    # forces, stance, j_feet, j_env_stride, j_foot_stride, bias, effort_limit, n, num_feet, num_dof, efforts_out, stream
+    "shf_foot_force_efforts": ([vp, vp, vp, i64, i64, vp, vp, i32, i32, i32, vp, vp], i32),
     "shf_reward_accumulate": ([C.POINTER(vp), C.POINTER(vp), i32, i64, vp, vp], i32),
     "shf_gae": ([vp, vp, vp, vp, i32, i64, C.c_float, C.c_float, vp, vp], i32),
     "shf_ppo_loss_workspace": ([i64, i32, C.POINTER(i64)], i32),

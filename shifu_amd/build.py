@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "libshifu_amd.so")
 # (csrc/shf_kernel_list.h) so that they compile side by side -- as one unit the library took 4.5 minutes to build.
 KERNEL_UNITS = ["shf_k_sim.hip", "shf_k_sim_link.hip", "shf_k_sim_hard.hip", "shf_k_sim_hard_wide.hip", "shf_k_a1.hip", "shf_k_abb.hip",
                 "shf_k_abb_link.hip", "shf_k_abb_hard.hip", "shf_k_abb_ws.hip", "shf_k_abb_ws_hard.hip", "shf_k_sim_ext.hip", "shf_k_abb_ext.hip", "shf_k_hull_test.hip", "shf_k_cap_select_test.hip"]
-UNITY_SOURCES = ["shf_api.hip", "shf_a1_chain.hip", "shf_glue.hip", "shf_mlp.hip", "shf_k_hull_test.hip", "shf_k_cap_select_test.hip", "shf_render.hip", "shf_conv.hip", "shf_lstm.hip", "shf_gru.hip", "shf_dyn.hip", "shf_dyn_fb.hip", "shf_qp.hip", "shf_gait.hip"]      # with -DSHF_UNITY: shf_api.hip instantiates every kernel
+UNITY_SOURCES = ["shf_api.hip", "shf_a1_chain.hip", "shf_glue.hip", "shf_mlp.hip", "shf_k_hull_test.hip", "shf_k_cap_select_test.hip", "shf_render.hip", "shf_conv.hip", "shf_lstm.hip", "shf_gru.hip", "shf_dyn.hip", "shf_dyn_fb.hip", "shf_qp.hip", "shf_gait.hip", "shf_mpc.hip"]      # with -DSHF_UNITY: shf_api.hip instantiates every kernel
 SOURCES = UNITY_SOURCES + [u for u in KERNEL_UNITS if u not in UNITY_SOURCES]
 HEADERS = ["shf_device.h", "shf_boxes.h", "shf_task.h", "shf_chain.h", "shf_chain_hard.h", "shf_hard.h", "shf_link.h", "shf_arm.h", "shf_kernels.h",
            "shf_kernel_list.h", "shf_hull.h", "shf_dyn.h", "shf_rnn_cell.h", os.path.join("..", "..", "include", "shifu_amd.h")]
@@ -128,7 +128,13 @@ BUDGETS = [("_Z16k_a1_step_a1_g32", 256, 0),          # default: A1, two envs pe
            # the gait planner and the stance / swing effort merge (csrc/shf_gait.hip: k_gait_plan, k_leg_effort_mix): 74 and 14
            # registers in the first clean build (four feet's positions and anchors, the base rotation, the command and the
            # target in flight) plus a margin of 10; nothing on the stack (the foot loop is unrolled so that it stays that way)
-           ("_ZN12_GLOBAL__N_111k_gait_plan", 84, 0), ("_ZN12_GLOBAL__N_116k_leg_effort_mix", 24, 0)]
+           ("_ZN12_GLOBAL__N_111k_gait_plan", 84, 0), ("_ZN12_GLOBAL__N_116k_leg_effort_mix", 24, 0),
+           # the horizon MPC (csrc/shf_mpc.hip: k_mpc_horizon, k_foot_force_mpc, k_foot_force_efforts): 53, 106 and 43 registers in
+           # the first clean build (the solve: the 6 x 6 base inertia while it is inverted, then a variable's x, z, y and a
+           # 16-byte word of its Kinv row and of the right-hand side; Kinv itself sits in LDS) plus a margin of 10; nothing on
+           # the stack
+           ("_ZN12_GLOBAL__N_113k_mpc_horizon", 63, 0), ("_ZN12_GLOBAL__N_116k_foot_force_mpc", 116, 0),
+           ("_ZN12_GLOBAL__N_120k_foot_force_efforts", 53, 0)]
 
 
 def parse_resources(remarks: str) -> dict:

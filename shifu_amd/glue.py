@@ -338,6 +338,108 @@ def leg_effort_mix(stance_efforts, swing_efforts, stance, chain_mask, effort_lim
     return out
 
 
+# -- the horizon MPC: tables over the gait schedule -> condensed QP -> efforts (csrc/shf_mpc.hip) ---------------------------------
+# The defaults (DESIGN.md 8h "Horizon MPC" says where each comes from): horizon steps, sweeps, force weight, ticks between two
+# solves, and the weights of (roll, pitch, yaw, x, y, z, omega, v)
+MPC_HORIZON, MPC_ITERS, MPC_ALPHA, MPC_EVERY = 10, 100, 1e-5, 1
+MPC_WEIGHTS = (25.0, 25.0, 10.0, 2.0, 2.0, 50.0, 0.0, 0.0, 0.3, 0.2, 0.2, 0.2)
+
+
+def mpc_step_dt(steps_per_tick, dt):
+    """delta, the length of a horizon step, as shf_mpc_horizon forms it: the float32 product of the two."""
+    import numpy as np
+    return float(np.float32(steps_per_tick) * np.float32(dt))
+
+
+def mpc_horizon(state, stance, foot_pos, command, nominal, ticks, params, horizon=MPC_HORIZON, steps_per_tick=1):
+    """The MPC's tables in one launch (shf_mpc_horizon): (contact (n, H, F) uint8, xref (n, H + 1, 12), pos (n, H, F, 3)), from
+    the GaitState as gait_plan left it this tick, gait_plan's stance (n, F), foot_pos (n, F, 3) (a view as for foot_impedance),
+    command (n, 3), nominal (F, 3), ticks = Gait.ticks(dt), params = gait_params(...)."""
+    n, F = foot_pos.shape[:2]
+    P, offsets, stance_ticks = ticks
+    H = int(horizon)
+    assert foot_pos.is_cuda and foot_pos.dtype == torch.float32 and foot_pos.shape == (n, F, 3) and foot_pos.stride(2) == 1
+    assert tuple(stance.shape) == (n, F) and stance.dtype in (torch.uint8, torch.bool) and stance.is_cuda
+    assert tuple(command.shape) == (n, 3) and tuple(nominal.shape) == (F, 3) and len(offsets) == F and len(stance_ticks) == F
+    tick, _, _, target, yaw = state.tensors()
+    assert tick.dtype == torch.int32 and tuple(target.shape) == (n, 13) and yaw.numel() == n
+    dev = foot_pos.device
+    st, cmd, nom = stance.contiguous().view(torch.uint8), command.contiguous(), nominal.contiguous()
+    contact = torch.empty(n, max(H, 0), F, dtype=torch.uint8, device=dev)
+    xref = torch.empty(n, max(H, 0) + 1, 12, dtype=torch.float32, device=dev)
+    pos = torch.empty(n, max(H, 0), F, 3, dtype=torch.float32, device=dev)
+    ia = C.c_int32 * F
+    with torch.cuda.device(dev):
+        check(lib().shf_mpc_horizon(_vp(tick.data_ptr()), _f32c(target), _f32c(yaw), int(P), ia(*[int(o) for o in offsets]),
+                                    ia(*[int(s) for s in stance_ticks]), _vp(st.data_ptr()), _vp(foot_pos.data_ptr()),
+                                    foot_pos.stride(0), foot_pos.stride(1), _f32c(cmd), _f32c(nom), params, H, int(steps_per_tick), n, F,
+                                    _vp(contact.data_ptr()), _f32c(xref), _f32c(pos), _stream(dev)))
+    return contact, xref, pos
+
+
+def foot_force_mpc(contact, xref, pos, root_state, mass_matrix, dyn_bias, j_feet, mu, weights12, alpha=MPC_ALPHA, fz_min=5.0,
+                   fz_max=float("inf"), iters=MPC_ITERS, step_dt=0.03, bias=None, effort_limit=None, u_io=None, warm_shift=0,
+                   forces_out=None):
+    """The horizon MPC's solve in one launch (shf_foot_force_mpc): (forces (n, F, 3) = step 0 of the solution, efforts (n, nd)).
+    contact, xref, pos: mpc_horizon's tables; root_state (n, >= 13) rows and j_feet (n, F, 6, nd + 6): views as for
+    foot_force_qp; mass_matrix (n, nd + 6, nd + 6), dyn_bias (n, nd + 6); mu a float or a (n) tensor; weights12 (12); step_dt:
+    mpc_step_dt(S, dt); bias (n, nd + 6) or None: added to the efforts; effort_limit (nd) or None; u_io (n, H, F, 3)
+    contiguous or None: the warm start, read shifted by warm_shift steps and overwritten with the solution."""
+    n, F, six, D = j_feet.shape
+    nd = D - 6
+    H = contact.shape[1]
+    assert six == 6 and j_feet.stride(3) == 1 and j_feet.stride(2) == D
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in (j_feet, root_state, xref, pos)), "float32 CUDA tensors expected"
+    assert root_state.shape[0] == n and root_state.shape[1] >= 13 and root_state.stride(1) == 1
+    assert tuple(contact.shape) == (n, H, F) and contact.dtype == torch.uint8 and contact.is_cuda
+    assert tuple(xref.shape) == (n, H + 1, 12) and tuple(pos.shape) == (n, H, F, 3)
+    assert tuple(mass_matrix.shape) == (n, D, D) and tuple(dyn_bias.shape) == (n, D) and weights12.numel() == 12
+    assert bias is None or tuple(bias.shape) == (n, D)
+    assert effort_limit is None or effort_limit.numel() == nd
+    assert u_io is None or (tuple(u_io.shape) == (n, H, F, 3) and u_io.is_contiguous() and u_io.is_cuda and u_io.dtype == torch.float32)
+    per_env = torch.is_tensor(mu) and mu.numel() > 1
+    assert not per_env or mu.numel() == n
+    keep = []                 # contiguous copies stay referenced until the launch is enqueued
+
+    def o(t):
+        if t is None:
+            return None
+        keep.append(t.contiguous())
+        return _f32c(keep[-1])
+
+    ct = contact.contiguous()
+    forces = torch.empty(n, F, 3, device=j_feet.device, dtype=torch.float32) if forces_out is None else forces_out
+    out = torch.empty(n, nd, device=j_feet.device, dtype=torch.float32)
+    with torch.cuda.device(j_feet.device):
+        check(lib().shf_foot_force_mpc(_vp(ct.data_ptr()), o(xref), o(pos), _vp(root_state.data_ptr()), root_state.stride(0),
+                                       o(mass_matrix), o(dyn_bias), _vp(j_feet.data_ptr()), j_feet.stride(0), j_feet.stride(1),
+                                       o(mu.reshape(n)) if per_env else None, 0.0 if per_env else float(mu), o(weights12),
+                                       float(alpha), float(fz_min), float(fz_max), int(iters), float(step_dt), o(bias),
+                                       o(effort_limit), None if u_io is None else _f32c(u_io), int(warm_shift), n, H, F, nd,
+                                       _f32c(forces), _f32c(out), _stream(j_feet.device)))
+    return forces, out
+
+
+def foot_force_efforts(forces, stance, j_feet, bias=None, effort_limit=None):
+    """efforts (n, nd) = -sum over the feet with stance != 0 of Jl_f^T f_f, + bias[:, 6:], clamped to +-effort_limit, in one launch
+    (shf_foot_force_efforts): the effort step of foot_force_qp / foot_force_mpc on its own, bit-equal to theirs."""
+    n, F, six, D = j_feet.shape
+    nd = D - 6
+    assert six == 6 and j_feet.stride(3) == 1 and j_feet.stride(2) == D and j_feet.is_cuda and j_feet.dtype == torch.float32
+    assert tuple(forces.shape) == (n, F, 3) and tuple(stance.shape) == (n, F) and stance.dtype in (torch.uint8, torch.bool)
+    assert bias is None or tuple(bias.shape) == (n, D)
+    assert effort_limit is None or effort_limit.numel() == nd
+    f, st = forces.contiguous(), stance.contiguous().view(torch.uint8)
+    b = None if bias is None else bias.contiguous()
+    lim = None if effort_limit is None else effort_limit.contiguous()
+    out = torch.empty(n, nd, device=j_feet.device, dtype=torch.float32)
+    with torch.cuda.device(j_feet.device):
+        check(lib().shf_foot_force_efforts(_f32c(f), _vp(st.data_ptr()), _vp(j_feet.data_ptr()), j_feet.stride(0), j_feet.stride(1),
+                                           None if b is None else _f32c(b), None if lim is None else _f32c(lim), n, F, nd,
+                                           _f32c(out), _stream(j_feet.device)))
+    return out
+
+
 _CONSTANTS = {}
 
 
@@ -357,12 +459,18 @@ def _vec3(g):
 def locomotion_control(j_feet, dof_state, root_state, foot_pos, contact_z, shape_friction, ground_friction, mass_matrix, bias,
                        effort_limit, chain_mask, nominal, state, command, gait, dt, height=0.30, touchdown_z=0.01, swing_kp=400.,
                        swing_kd=10., reset=None, kp_lin=100., kd_lin=None, kp_ang=400., kd_ang=None, mu=None, fz_min=5., fz_max=None,
-                       weights=(1, 1, 1, 10, 10, 10), alpha=1e-2, gravity_compensation=True):
+                       weights=(1, 1, 1, 10, 10, 10), alpha=1e-2, gravity_compensation=True, controller="qp", horizon=MPC_HORIZON,
+                       mpc_steps_per_tick=None, mpc_every=MPC_EVERY, mpc_weights=MPC_WEIGHTS, mpc_alpha=MPC_ALPHA, mpc_iters=MPC_ITERS):
     """What LeggedRobot.locomotion_control and FusedA1Env.locomotion_control share, four launches: the gait plan (base target
     and stance from `gait`'s schedule gated by contact_z, swing targets), foot_force_qp on that target and stance (as
     balance_control: kd None = 2 sqrt(kp), mu None = (shape_friction + ground_friction) / 2), foot_impedance towards the swing
     targets with the explicit swing_kp / swing_kd and no bias, and leg_effort_mix.  state: the GaitState, advanced by one tick;
-    reset None = the state's pending resets.  Returns (efforts (n, nd), forces (n, F, 3), stance (n, F), swing_targets (n, F, 3))."""
+    reset None = the state's pending resets.  controller="mpc": the stance forces come from the horizon MPC instead
+    (csrc/shf_mpc.hip) -- mpc_horizon and foot_force_mpc in place of foot_force_qp every `mpc_every` ticks (and on the tick
+    after a reset), `horizon` steps of mpc_steps_per_tick gait ticks (None = ceil(period_ticks / horizon): the horizon covers
+    one gait period), warm-started from the last solve; on the ticks in between foot_force_efforts holds the last solve's forces
+    on the current Jacobian (a foot that has lifted since counts as zero; `forces` is then the held solve's).  The QP's gains
+    and weights are not read by the MPC.  Returns (efforts (n, nd), forces (n, F, 3), stance (n, F), swing_targets (n, F, 3))."""
     import math
     dev = j_feet.device
     if reset is None:
@@ -375,9 +483,31 @@ def locomotion_control(j_feet, dof_state, root_state, foot_pos, contact_z, shape
     gains = _constant(kpl + kdl + kpa + kda, dev)
     if mu is None:
         mu = 0.5 * (shape_friction + float(ground_friction))
-    forces, tau_st = foot_force_qp(j_feet, root_state, foot_pos, stance, mu, _constant(weights, dev), None, mass_matrix, bias,
-                                   state.target, gains, alpha, 0.0, None, fz_min, float("inf") if fz_max is None else float(fz_max),
-                                   QP_ITERS, bias if gravity_compensation else None, effort_limit)
+    if controller == "mpc":
+        ticks = gait.ticks(dt)
+        S = int(mpc_steps_per_tick) if mpc_steps_per_tick else -(-ticks[0] // int(horizon))
+        u_io, held = state.mpc_buffers(horizon)
+        if reset is not None:                        # a reset env starts cold, and everybody solves on this tick
+            keep = (1 - reset.view(torch.uint8).to(torch.float32))
+            u_io.mul_(keep.view(-1, 1, 1, 1))
+            state.mpc_count = 0
+        if state.mpc_count % max(int(mpc_every), 1) == 0:
+            params = gait_params(dt, height, touchdown_z, gait)
+            contact, xref, pos = mpc_horizon(state, stance, foot_pos, command, nominal, ticks, params, horizon, S)
+            forces, tau_st = foot_force_mpc(contact, xref, pos, root_state, mass_matrix, bias, j_feet, mu, _constant(mpc_weights, dev),
+                                            mpc_alpha, fz_min, float("inf") if fz_max is None else float(fz_max), mpc_iters,
+                                            mpc_step_dt(S, dt), bias if gravity_compensation else None, effort_limit, u_io,
+                                            int(mpc_every) // S, forces_out=held)
+        else:
+            forces = held
+            tau_st = foot_force_efforts(held, stance, j_feet, bias if gravity_compensation else None, effort_limit)
+        state.mpc_count += 1
+    elif controller == "qp":
+        forces, tau_st = foot_force_qp(j_feet, root_state, foot_pos, stance, mu, _constant(weights, dev), None, mass_matrix, bias,
+                                       state.target, gains, alpha, 0.0, None, fz_min, float("inf") if fz_max is None else float(fz_max),
+                                       QP_ITERS, bias if gravity_compensation else None, effort_limit)
+    else:
+        raise ValueError(f"locomotion_control: controller {controller!r} (\"qp\" or \"mpc\")")
     tau_sw = foot_impedance(j_feet, dof_state, root_state, foot_pos, swing_t, _constant(_vec3(swing_kp), dev),
                             _constant(_vec3(swing_kd), dev), None, effort_limit)
     return leg_effort_mix(tau_st, tau_sw, stance, chain_mask, effort_limit), forces, stance, swing_t

@@ -290,7 +290,8 @@ class FusedA1Env(FusedCameraHost):
         whole_body_dynamics()'s tensors and the root, body, dof and contact tensors as the last step left them; one call is one
         gait tick of the simulation step.  command (n, 3) = (vx, vy, yaw rate); gait None = Gait.trot().  The gait state
         (`gait_state`, a units.gait.GaitState) is allocated once; reset (n) uint8 restarts those envs' gait, and the first
-        call restarts every env's.  Not part of the fused step."""
+        call restarts every env's.  controller="mpc" among **balance_kw: the stance forces from the horizon MPC (csrc/shf_mpc.hip;
+        glue.locomotion_control names its settings).  Not part of the fused step."""
         from .. import glue
         from ..units import gait as G
         w = self.whole_body_dynamics()

@@ -62,7 +62,8 @@ class Gait:
 
 class GaitState:
     """tick (n) int32, sched (n, F) uint8, anchor (n, F, 3), target (n, 13), yaw (n): shf_gait_plan's per-env state.  A new state
-    has `pending` set for every env: the next plan resets those envs (clock at 0, anchors at the feet, target over the base)."""
+    has `pending` set for every env: the next plan resets those envs (clock at 0, anchors at the feet, target over the base).
+    It also carries what the horizon MPC keeps between ticks (mpc_u, mpc_forces, mpc_count); reset() clears them too."""
 
     def __init__(self, n, F, device, dtype=torch.float32):
         self.n, self.F = int(n), int(F)
@@ -74,6 +75,11 @@ class GaitState:
         self.yaw = torch.zeros(n, dtype=dtype, device=device)
         self.pending = torch.ones(n, dtype=torch.uint8, device=device)
         self.any_pending = True
+        # the horizon MPC's (controller="mpc"): the last solution u (n, H, F, 3), the forces held between two solves, and the
+        # ticks since the state was made or reset (a solve falls on every mpc_every-th)
+        self.mpc_u = None
+        self.mpc_forces = torch.zeros(n, F, 3, dtype=dtype, device=device)
+        self.mpc_count = 0
 
     def reset(self, env_ids=None):
         if env_ids is None:
@@ -81,6 +87,19 @@ class GaitState:
         else:
             self.pending[env_ids] = 1
         self.any_pending = True
+        ids = slice(None) if env_ids is None else env_ids
+        if self.mpc_u is not None:
+            self.mpc_u[ids] = 0.0
+        self.mpc_forces[ids] = 0.0
+        self.mpc_count = 0                          # the next tick solves
+
+    def mpc_buffers(self, horizon):
+        """(u (n, horizon, F, 3), held forces (n, F, 3)) of the horizon MPC; u is made (zero: a cold start) on first use and
+        whenever the horizon changes."""
+        if self.mpc_u is None or self.mpc_u.shape[1] != int(horizon):
+            self.mpc_u = torch.zeros(self.n, int(horizon), self.F, 3, dtype=self.mpc_forces.dtype, device=self.mpc_forces.device)
+            self.mpc_count = 0
+        return self.mpc_u, self.mpc_forces
 
     def take_pending(self):
         """The reset flags for the next plan (None when nothing is pending); a copy, the flags themselves are cleared."""

@@ -469,7 +469,9 @@ class LeggedRobot(ArmRobot):
         light damper: at 2 sqrt(kp) the feet lag their targets) without bias; one launch merges the two and clamps to the
         effort limits.  One call is one tick of dt = the simulation step.  touchdown_z None = 1 cm below the resting height of a
         foot's origin on the plane z = 0.  A change of `gait` restarts the clock; reset_gait() restarts everything.  From the
-        tensors as last refreshed."""
+        tensors as last refreshed.  controller="mpc" (among **balance_kw, with horizon, mpc_steps_per_tick, mpc_every,
+        mpc_weights, mpc_alpha, mpc_iters: glue.locomotion_control says what each is) takes the stance forces from the horizon
+        MPC over the gait's schedule (csrc/shf_mpc.hip) instead of the QP of this instant."""
         from .gait import Gait
         h = self.bias_forces                     # (refused with "fixed base" unless SHIFU_AMD_FLOATING_DYNAMICS=1)
         M = self.mass_matrix
@@ -480,6 +482,9 @@ class LeggedRobot(ArmRobot):
         st = self._gait_state()
         if getattr(self, "_gait_last", None) is not gait:
             st.tick.zero_()
+            st.mpc_count = 0                         # the horizon MPC starts cold on the new schedule
+            if st.mpc_u is not None:
+                st.mpc_u.zero_()
             self._gait_last = gait
         if touchdown_z is None:
             touchdown_z = self._foot_radius() - 0.01
@@ -500,20 +505,46 @@ class LeggedRobot(ArmRobot):
                 touchdown_z, swing_kp, swing_kd, **balance_kw)
         else:
             from shifu_amd.utils import torch_utils as TU
+            from shifu_amd import glue as G_
             kw = dict(kp_lin=100., kd_lin=None, kp_ang=400., kd_ang=None, mu=None, fz_min=5., fz_max=None, weights=(1, 1, 1, 10, 10, 10),
-                      alpha=1e-2, gravity_compensation=True)
+                      alpha=1e-2, gravity_compensation=True, controller="qp", horizon=G_.MPC_HORIZON, mpc_steps_per_tick=None,
+                      mpc_every=G_.MPC_EVERY, mpc_weights=G_.MPC_WEIGHTS, mpc_alpha=G_.MPC_ALPHA, mpc_iters=G_.MPC_ITERS)
             kw.update(balance_kw)
-            stance, swing, _, _ = TU.gait_plan(st, root, feet, cz, command, self.nominal_foot_positions, st.take_pending(), gait.ticks(dt),
+            pending = st.take_pending()
+            stance, swing, _, _ = TU.gait_plan(st, root, feet, cz, command, self.nominal_foot_positions, pending, gait.ticks(dt),
                                                dt, height, gait.apex, touchdown_z, gait.late_depth, gait.k_fb, gait.max_step, gait.leash,
                                                gait.contact_threshold)
             kpl, kpa = self._gain3(kw["kp_lin"]), self._gain3(kw["kp_ang"])
             gains = torch.cat([kpl, 2.0 * torch.sqrt(kpl) if kw["kd_lin"] is None else self._gain3(kw["kd_lin"]),
                                kpa, 2.0 * torch.sqrt(kpa) if kw["kd_ang"] is None else self._gain3(kw["kd_ang"])])
             S = torch.as_tensor(kw["weights"], dtype=torch.float32, device=self.device).reshape(6)
-            forces, tau_st = TU.foot_force_qp(jf, root[:, :3], feet, TU.balance_wrench(M, h, root, st.target, gains), stance,
-                                              self._contact_friction() if kw["mu"] is None else kw["mu"], S, kw["alpha"], 0.0, None,
-                                              kw["fz_min"], float("inf") if kw["fz_max"] is None else float(kw["fz_max"]), 100,
-                                              h if kw["gravity_compensation"] else None, self.torque_limits)
+            mu_, fz_max_ = self._contact_friction() if kw["mu"] is None else kw["mu"], float("inf") if kw["fz_max"] is None else float(kw["fz_max"])
+            if kw["controller"] == "mpc":
+                # the torch expressions of glue.locomotion_control's "mpc" branch (csrc/shf_mpc.hip)
+                tk, Hn, every = gait.ticks(dt), int(kw["horizon"]), max(int(kw["mpc_every"]), 1)
+                Sx = int(kw["mpc_steps_per_tick"]) if kw["mpc_steps_per_tick"] else -(-tk[0] // Hn)
+                u_io, held = st.mpc_buffers(Hn)
+                if pending is not None:
+                    u_io[pending.bool()] = 0.0
+                    st.mpc_count = 0
+                if st.mpc_count % every == 0:
+                    contact, xref, pos = TU.mpc_horizon(st, stance, feet, command, self.nominal_foot_positions, tk, dt, touchdown_z,
+                                                        gait.max_step, Hn, Sx)
+                    L12 = torch.as_tensor(kw["mpc_weights"], dtype=torch.float32, device=self.device).reshape(12)
+                    forces, tau_st = TU.foot_force_mpc(contact, xref, pos, root, M, h, jf, mu_, L12, kw["mpc_alpha"], kw["fz_min"], fz_max_,
+                                                       kw["mpc_iters"], G_.mpc_step_dt(Sx, dt), h if kw["gravity_compensation"] else None,
+                                                       self.torque_limits, u_io, every // Sx)
+                    held.copy_(forces)
+                else:
+                    forces = held
+                    tau_st = TU.foot_force_efforts(held, stance, jf, h if kw["gravity_compensation"] else None, self.torque_limits)
+                st.mpc_count += 1
+            elif kw["controller"] == "qp":
+                forces, tau_st = TU.foot_force_qp(jf, root[:, :3], feet, TU.balance_wrench(M, h, root, st.target, gains), stance, mu_, S,
+                                                  kw["alpha"], 0.0, None, kw["fz_min"], fz_max_, 100,
+                                                  h if kw["gravity_compensation"] else None, self.torque_limits)
+            else:
+                raise ValueError(f"locomotion_control: controller {kw['controller']!r} (\"qp\" or \"mpc\")")
             tau_sw = TU.foot_impedance_control(jf, self.dof_vel, root[:, :3], root[:, 3:7], feet, swing, self._gain3(swing_kp),
                                                self._gain3(swing_kd), None, self.torque_limits)
             efforts = TU.leg_effort_mix(tau_st, tau_sw, stance, self._gait_chain, self.torque_limits)

@@ -292,3 +292,206 @@ def leg_effort_mix(stance_efforts, swing_efforts, stance, chain_mask, effort_lim
         lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
         tau = torch.maximum(torch.minimum(tau, lim), -lim)
     return tau
+
+
+# -- the horizon MPC (csrc/shf_mpc.hip, whose header states the three algorithms step by step; tests/mpc_ref.py holds the NumPy twins)
+def mpc_horizon(state, stance, foot_pos, command, nominal, ticks, dt, touchdown_z, max_step, horizon, steps_per_tick):
+    """The MPC's tables: (contact (n, H, F) uint8, xref (n, H + 1, 12), pos (n, H, F, 3)).  The algorithm of shf_mpc_horizon as
+    batched torch expressions, in the dtype of state.target (its CPU fallback).  state: tick / target / yaw as gait_plan left
+    them this tick (the stored tick already advanced); stance (n, F): gait_plan's; ticks = (period_ticks, offset_ticks,
+    stance_ticks)."""
+    P, offsets, stance_ticks = ticks
+    n, F = foot_pos.shape[:2]
+    H, S = int(horizon), int(steps_per_tick)
+    tg, yaw = state.target, state.yaw
+    T, dev = tg.dtype, tg.device
+    delta = float(S) * dt
+    k = torch.arange(H + 1, device=dev, dtype=T)
+    kd = (k * delta).unsqueeze(0)                                           # (1, H + 1)
+    xref = torch.zeros(n, H + 1, 12, dtype=T, device=dev)
+    xref[:, :, 2] = yaw.unsqueeze(1) + kd * tg[:, 12:13]
+    xref[:, :, 3], xref[:, :, 4], xref[:, :, 5] = tg[:, 0:1] + kd * tg[:, 7:8], tg[:, 1:2] + kd * tg[:, 8:9], tg[:, 2:3].expand(n, H + 1)
+    xref[:, :, 6:9], xref[:, :, 9:12] = tg[:, None, 10:13], tg[:, None, 7:10]
+    tm = torch.remainder(state.tick.to(torch.int64) - 1, P)
+    off = torch.as_tensor(list(offsets), dtype=torch.int64, device=dev)
+    stt = torch.as_tensor(list(stance_ticks), dtype=torch.int64, device=dev)
+    ks = torch.remainder(torch.arange(H, device=dev, dtype=torch.int64) * S, P)
+    phi = torch.remainder(tm.view(n, 1, 1) + ks.view(1, H, 1) + off.view(1, 1, F), P)
+    contact = phi < stt.view(1, 1, F)
+    contact[:, 0] = stance != 0
+    psi = xref[:, :H, 2].unsqueeze(-1)                                      # (n, H, 1)
+    cs, sn = torch.cos(psi), torch.sin(psi)
+    nfx, nfy = nominal[:, 0].to(T).view(1, 1, F), nominal[:, 1].to(T).view(1, 1, F)
+    nwx, nwy = cs * nfx - sn * nfy, sn * nfx + cs * nfy
+    hx, hy = xref[:, :H, 3:4] + nwx, xref[:, :H, 4:5] + nwy
+    cvx, cvy, cwz = (command[:, i].to(T).view(n, 1, 1) for i in range(3))
+    vdx, vdy = (cs * cvx - sn * cvy) - cwz * nwy, (sn * cvx + cs * cvy) + cwz * nwx
+    half = ((stt.to(T) * dt) * 0.5).view(1, 1, F)
+    gx, gy = vdx * half, vdy * half
+    m = torch.sqrt(gx * gx + gy * gy)
+    q = max_step / m
+    big = m > max_step
+    gx, gy = torch.where(big, gx * q, gx), torch.where(big, gy * q, gy)
+    new = torch.stack([hx + gx, hy + gy, torch.full_like(gx, touchdown_z)], -1)          # (n, H, F, 3)
+    pos = torch.zeros(n, H, F, 3, dtype=T, device=dev)
+    hold = torch.where(contact[:, 0].unsqueeze(-1), foot_pos.to(T), torch.zeros(n, F, 3, dtype=T, device=dev))
+    pos[:, 0] = hold
+    for j in range(1, H):
+        start = contact[:, j] & ~contact[:, j - 1]
+        hold = torch.where(start.unsqueeze(-1), new[:, j], hold)
+        pos[:, j] = torch.where(contact[:, j].unsqueeze(-1), hold, torch.zeros_like(hold))
+    return contact.to(torch.uint8), xref, pos
+
+
+def _gauss_jordan_inverse(A):
+    """A^-1 of a batch (n, N, N) by the in-place Gauss-Jordan sweep without pivoting, as csrc/shf_mpc.hip inverts."""
+    A = A.clone()
+    for k in range(A.shape[-1]):
+        p = 1.0 / A[:, k, k]
+        row = A[:, k, :] * p.unsqueeze(1)
+        f = A[:, :, k].clone()
+        A = A - f.unsqueeze(2) * row.unsqueeze(1)
+        A[:, :, k] = -(f * p.unsqueeze(1))
+        A[:, k, :] = row
+        A[:, k, k] = p
+    return A
+
+
+def _mpc_state(root_state, psi0):
+    x, y, z, w = (root_state[:, 3 + k] for k in range(4))
+    R20, R21, R22 = 2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)
+    R10, R00 = 2.0 * (x * y + w * z), 1.0 - 2.0 * (y * y + z * z)
+    yaw = torch.atan2(R10, R00)
+    yaw = yaw + torch.round((psi0 - yaw) * 0.15915494309189535) * 6.283185307179586
+    return torch.cat([torch.atan2(R21, R22).unsqueeze(1), torch.asin((-R20).clamp(-1.0, 1.0)).unsqueeze(1), yaw.unsqueeze(1),
+                      root_state[:, 0:3], root_state[:, 10:13], root_state[:, 7:10]], 1)
+
+
+def foot_force_mpc(contact, xref, pos, root_state, mass_matrix, dyn_bias, j_feet, mu, weights12, alpha=1e-5, fz_min=5.0,
+                   fz_max=float("inf"), iters=100, step_dt=0.03, bias=None, effort_limit=None, u_io=None, warm_shift=0):
+    """The horizon MPC's solve: (forces (n, F, 3), efforts (n, nd)); u_io (n, H, F, 3) or None is the warm start and receives
+    the solution.  The algorithm of csrc/shf_mpc.hip's shf_foot_force_mpc as batched torch expressions in the dtype of xref
+    (its CPU fallback): the condensed P and q in closed form, K^-1 formed once (Gauss-Jordan) and multiplied by in every sweep."""
+    n, H, F = contact.shape
+    F3, N = 3 * F, 3 * F * H
+    T, dev = xref.dtype, xref.device
+    L = weights12.to(T)
+    d = float(step_dt)
+    Mi = _gauss_jordan_inverse(mass_matrix[:, :6, :6].to(T))
+    g = -(Mi @ dyn_bias[:, :6].to(T).unsqueeze(-1)).squeeze(-1)
+    root = root_state.to(T)
+    x = _mpc_state(root, xref[:, 0, 2])
+    CA, CB = torch.zeros(n, H + 1, dtype=T, device=dev), torch.zeros(n, H + 1, dtype=T, device=dev)
+    E = torch.zeros(n, H, 12, dtype=T, device=dev)
+    for s in range(H):
+        psi = xref[:, s, 2]
+        cs, sn = torch.cos(psi), torch.sin(psi)
+        th = torch.stack([cs * x[:, 6] + sn * x[:, 7], cs * x[:, 7] - sn * x[:, 6], x[:, 8]], 1)
+        x = torch.cat([x[:, 0:3] + d * th, x[:, 3:6] + d * x[:, 9:12], x[:, 6:9] + d * g[:, 3:6], x[:, 9:12] + d * g[:, 0:3]], 1)
+        CA[:, s + 1], CB[:, s + 1] = CA[:, s] + cs, CB[:, s] + sn
+        E[:, s] = x - xref[:, s + 1]
+    ar = torch.arange(N, device=dev)
+    ki, fi, ci = ar // F3, (ar % F3) // 3, ar % 3
+    cf = contact[:, ki, fi].to(T)
+    r = pos[:, ki, fi].to(T) - (root[:, None, :3] + (xref[:, ki, 3:6] - xref[:, :1, 3:6]))
+    zero = torch.zeros(n, N, dtype=T, device=dev)
+    c0, c1 = (ci == 0).unsqueeze(0), (ci == 1).unsqueeze(0)
+    a0 = torch.where(c0, zero, torch.where(c1, -r[..., 2], r[..., 1]))
+    a1 = torch.where(c0, r[..., 2], torch.where(c1, zero, -r[..., 0]))
+    a2 = torch.where(c0, -r[..., 1], torch.where(c1, r[..., 0], zero))
+    W = torch.stack([(d * (Mi[:, q, :3][:, ci] + ((Mi[:, q, 3:4] * a0 + Mi[:, q, 4:5] * a1) + Mi[:, q, 5:6] * a2))) * cf for q in range(6)], 1)
+    TX, TY = torch.zeros(n, H + 1, N, dtype=T, device=dev), torch.zeros(n, H + 1, N, dtype=T, device=dev)
+    for s in range(1, H + 1):
+        a, b = CA[:, s, None] - CA[:, ki + 1], CB[:, s, None] - CB[:, ki + 1]
+        on = (s > ki + 1).unsqueeze(0)
+        TX[:, s] = torch.where(on, a * W[:, 3] + b * W[:, 4], zero)
+        TY[:, s] = torch.where(on, a * W[:, 4] - b * W[:, 3], zero)
+    dd = d * d
+    o = lambda u, v: u.unsqueeze(2) * v.unsqueeze(1)
+    wLv = [W[:, k] * L[9 + k] for k in range(3)]
+    wLw = [W[:, 3 + k] * L[6 + k] for k in range(3)]
+    wLp = [W[:, k] * L[3 + k] for k in range(3)]
+    wLz = W[:, 5] * L[2]
+    m = torch.maximum(ki.unsqueeze(1), ki.unsqueeze(0))
+    s2 = torch.zeros(N, N, dtype=torch.int64, device=dev)
+    for s in range(1, H + 1):
+        s2 += torch.where(s > m, (s - 1 - ki.unsqueeze(1)) * (s - 1 - ki.unsqueeze(0)), torch.zeros_like(m))
+    dv = (o(wLv[0], W[:, 0]) + o(wLv[1], W[:, 1])) + o(wLv[2], W[:, 2])
+    dw = (o(wLw[0], W[:, 3]) + o(wLw[1], W[:, 4])) + o(wLw[2], W[:, 5])
+    dp = (o(wLp[0], W[:, 0]) + o(wLp[1], W[:, 1])) + o(wLp[2], W[:, 2])
+    dz = o(wLz, W[:, 5])
+    th = torch.zeros(n, N, N, dtype=T, device=dev)
+    for s in range(1, H + 1):
+        th = th + (o(L[0] * TX[:, s], TX[:, s]) + o(L[1] * TY[:, s], TY[:, s]))
+    P = ((H - m).to(T).unsqueeze(0) * (dw + dv) + (dd * s2.to(T)).unsqueeze(0) * (dp + dz)) + dd * th
+    eye = torch.eye(N, dtype=T, device=dev)
+    P = P + float(alpha) * eye
+    q = torch.zeros(n, N, dtype=T, device=dev)
+    for s in range(1, H + 1):
+        nn = (s - 1 - ki).to(T).unsqueeze(0)
+        Es = E[:, s - 1]
+        pa = d * (((L[0] * TX[:, s]) * Es[:, 0:1] + (L[1] * TY[:, s]) * Es[:, 1:2]) + nn * (wLz * Es[:, 2:3]))
+        pb = (d * nn) * ((wLp[0] * Es[:, 3:4] + wLp[1] * Es[:, 4:5]) + wLp[2] * Es[:, 5:6])
+        pc = ((wLw[0] * Es[:, 6:7] + wLw[1] * Es[:, 7:8]) + wLw[2] * Es[:, 8:9]) \
+            + ((wLv[0] * Es[:, 9:10] + wLv[1] * Es[:, 10:11]) + wLv[2] * Es[:, 11:12])
+        q = torch.where((s > ki).unsqueeze(0), q + ((pa + pb) + pc), q)
+    mu = torch.as_tensor(mu, dtype=T, device=dev).expand(n).clamp(min=0.0)
+    dgl = torch.diagonal(P, dim1=1, dim2=2)
+    nc = cf.sum(1)
+    mean = (dgl * cf).sum(1) / nc.clamp(min=1.0)
+    mean = torch.where(nc > 0, mean, torch.ones_like(mean))
+    rho, sigma = torch.sqrt(float(alpha) * mean).view(n, 1), (1e-6 * mean).view(n, 1)
+    ata = torch.where((ci == 2).unsqueeze(0), (1.0 + 4.0 * (mu * mu)).view(n, 1), torch.full((n, N), 2.0, dtype=T, device=dev))
+    Kinv = _gauss_jordan_inverse(P + torch.diag_embed(sigma + rho * ata))
+    con = cf != 0
+    x = torch.zeros(n, N, dtype=T, device=dev)
+    if u_io is not None:
+        kk = (torch.arange(H, device=dev) + int(warm_shift)).clamp(max=H - 1)
+        x = torch.where(con, u_io[:, kk].reshape(n, N).to(T), x)
+    mu_ = mu.view(n, 1)
+
+    def rows(v):
+        v = v.reshape(n, H * F, 3)
+        mz = mu_ * v[..., 2]
+        return torch.stack([v[..., 2], mz - v[..., 0], mz + v[..., 0], mz - v[..., 1], mz + v[..., 1]], -1)
+
+    z, y = rows(x), torch.zeros(n, H * F, 5, dtype=T, device=dev)
+    cfoot = con.reshape(n, H * F, 3)[..., 0]
+    lo, hi = torch.zeros(n, H * F, 5, dtype=T, device=dev), torch.zeros(n, H * F, 5, dtype=T, device=dev)
+    lo[..., 0] = torch.where(cfoot, torch.full_like(lo[..., 0], fz_min), lo[..., 0])
+    hi[..., 0] = torch.where(cfoot, torch.full_like(hi[..., 0], fz_max), hi[..., 0])
+    hi[..., 1:] = torch.where(cfoot, torch.full_like(hi[..., 0], float("inf")), hi[..., 0]).unsqueeze(-1)
+    rho3 = rho.unsqueeze(-1)
+    for _ in range(int(iters)):
+        v = rho3 * z - y
+        add = torch.stack([v[..., 2] - v[..., 1], v[..., 4] - v[..., 3],
+                           v[..., 0] + mu_ * (((v[..., 1] + v[..., 2]) + v[..., 3]) + v[..., 4])], -1).reshape(n, N)
+        xt = (Kinv @ ((sigma * x - q) + add).unsqueeze(-1)).squeeze(-1)
+        zt = rows(xt)
+        x = 1.6 * xt + (1.0 - 1.6) * x
+        zr = 1.6 * zt + (1.0 - 1.6) * z
+        zn = torch.minimum(torch.maximum(zr + y / rho3, lo), hi)
+        y = y + rho3 * (zr - zn)
+        z = zn
+    xv = x.reshape(n, H * F, 3)
+    fz = xv[..., 2].clamp(fz_min, fz_max)
+    bnd = mu_ * fz
+    u = torch.stack([torch.minimum(torch.maximum(xv[..., 0], -bnd), bnd), torch.minimum(torch.maximum(xv[..., 1], -bnd), bnd), fz], -1)
+    u = torch.where(cfoot.unsqueeze(-1), u, torch.zeros_like(u)).reshape(n, H, F, 3)
+    if u_io is not None:
+        u_io.copy_(u)
+    forces = u[:, 0]
+    return forces, foot_force_efforts(forces, contact[:, 0], j_feet, bias, effort_limit)
+
+
+def foot_force_efforts(forces, stance, j_feet, bias=None, effort_limit=None):
+    """efforts (n, nd) = -sum over the feet with stance != 0 of Jl_f^T f_f, + bias[:, 6:], clamped to +-effort_limit (entries <=
+    0: no limit): the torch expression of csrc/shf_mpc.hip's shf_foot_force_efforts."""
+    f = torch.where((stance != 0).unsqueeze(-1), forces, torch.zeros_like(forces)).to(j_feet.dtype)
+    tau = -(torch.transpose(j_feet[:, :, :3, 6:], 2, 3) @ f.unsqueeze(-1)).squeeze(-1).sum(1)
+    if bias is not None:
+        tau = tau + bias[:, 6:]
+    if effort_limit is not None:
+        lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
+        tau = torch.maximum(torch.minimum(tau, lim), -lim)
+    return tau

@@ -1,11 +1,12 @@
 """The A1 walks at a commanded velocity without a policy: LeggedRobot.apply_locomotion_control through the gym facade in effort
 mode (gait plan, foot-force QP, swing spring-damper and the merge: csrc/shf_gait.hip, csrc/shf_qp.hip, csrc/shf_glue.hip).
 
-    python tools/walk_a1.py --command 0.3 0 0 --gait trot --envs 8 --steps 600 [--settle 100] [--video DIR]
+    python tools/walk_a1.py --command 0.3 0 0 --gait trot --envs 8 --steps 600 [--settle 100] [--controller mpc] [--video DIR]
 
 The robots are reset to their default pose, land during `--settle` ticks of Gait.stand() and then follow `--command vx vy wz`
 (m/s, m/s, rad/s in the heading frame) under `--gait` for `--steps` ticks of the simulation step.  Prints one JSON line: the
-mean velocity over the walk in the world frame, the yaw rate, the lowest base height and the largest tilt.  --video DIR writes
+mean velocity over the walk in the world frame, the yaw rate, the lowest base height and the largest tilt.  --controller mpc takes
+the stance forces from the horizon MPC (csrc/shf_mpc.hip; --mpc-every ticks between two solves) instead of the QP.  --video DIR writes
 the headless viewer's frames (frame_%06d.png, one per `--video-every` ticks) into DIR."""
 import argparse
 import json
@@ -22,6 +23,8 @@ def main():
     ap.add_argument("--envs", type=int, default=8)
     ap.add_argument("--steps", type=int, default=600)
     ap.add_argument("--settle", type=int, default=100)
+    ap.add_argument("--controller", choices=["qp", "mpc"], default="qp")
+    ap.add_argument("--mpc-every", type=int, default=None)
     ap.add_argument("--video", default=None, metavar="DIR")
     ap.add_argument("--video-every", type=int, default=4)
     a = ap.parse_args()
@@ -58,11 +61,12 @@ def main():
     stand, gait = Gait.stand(), PRESETS[a.gait]()
     zero = torch.zeros(3, device=robot.device)
     command = torch.tensor(a.command, dtype=torch.float32, device=robot.device)
+    mpc_kw = {} if a.mpc_every is None else {"mpc_every": a.mpc_every}
     zmin, tilt = float("inf"), 0.0
     start = None
     for s in range(a.settle + a.steps):
         walking = s >= a.settle
-        robot.apply_locomotion_control(command if walking else zero, gait=gait if walking else stand)
+        robot.apply_locomotion_control(command if walking else zero, gait=gait if walking else stand, controller=a.controller, **mpc_kw)
         env.gym.refresh_actor_root_state_tensor(env.sim)
         if s == a.settle - 1 or (a.settle == 0 and s == 0):
             start = root[:, :7].clone()
@@ -76,7 +80,7 @@ def main():
     dyaw = yaw(root) - yaw(start)
     dyaw = dyaw - 2.0 * math.pi * torch.round(dyaw / (2.0 * math.pi))
     vel = (root[:, :2] - start[:, :2]) / T
-    print(json.dumps({"gait": a.gait, "command": a.command, "envs": n, "steps": a.steps, "dt": dt,
+    print(json.dumps({"gait": a.gait, "controller": a.controller, "command": a.command, "envs": n, "steps": a.steps, "dt": dt,
                       "mean_world_velocity_m_s": [float(vel[:, 0].mean()), float(vel[:, 1].mean())],
                       "mean_yaw_rate_rad_s_mod_turns": float((dyaw / T).mean()), "lowest_base_z_m": zmin, "largest_tilt_rad": tilt,
                       "finite": bool(torch.isfinite(env.root_state).all() and torch.isfinite(env.dof_state).all())}))

@@ -312,8 +312,14 @@ class HardContactStepper:
                         psum += pimp
                 if phase == 0:
                     vpos = vfree + Minv @ (J.T @ (psum / self.npos if tgs else pimp))
-            vnew = vfree + Minv @ (J.T @ pimp)
-            imp_n = float(sum(pimp[3 * c] for c in range(narm))) / dt
+            # no velocity iterations: the velocities take the impulse set of the position iterations (under TGS their mean), and
+            # the force returned is that set's -- the impulses the velocities took (oracle/shf_oracle.c hard_solve).  This is
+            # the oracle's convention, adopted here: as first written this solver advanced the velocities with the final sweep's
+            # impulses in that case, so at nvel == 0 under TGS it checks the oracle's arithmetic, not that choice (the choice is
+            # pinned by the momentum law, tests/test_contact_force_law.py)
+            ptook = pimp if self.nvel > 0 or not tgs else psum / self.npos
+            vnew = vfree + Minv @ (J.T @ ptook)
+            imp_n = float(sum(ptook[3 * c] for c in range(narm))) / dt
         # semi-implicit Euler: poses with the velocities of the position iterations, state velocities from the velocity iterations
         if A.fixed:
             qd[:] = vnew[:A.nd]

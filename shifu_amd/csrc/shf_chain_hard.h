@@ -1229,9 +1229,9 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
           }
         }
       }
-      // (no velocity iterations: the impulses after the position iterations are the final ones -- but under TGS the passes through
-      // the tree took their mean, and the forces reported are those of the final impulses: oracle, hard_solve)
-      if (phase == 1 && nvel == 0 && !TGS) break;
+      // (no velocity iterations: the velocities take the impulses of the position iterations -- under TGS their mean -- and the
+      // forces reported are those of the same set, HC_P: oracle, hard_solve.  No HC_PV word is written or read then)
+      if (phase == 1 && nvel == 0) break;
       if (own) {
         // the impulses of this phase in world axes, for the pass through the tree
         float* h = tail + T::HC + l * HC_STRIDE;
@@ -1311,7 +1311,7 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
     Rt[3] = nx * inv; Rt[4] = ny * inv; Rt[5] = nz * inv; Rt[6] = nw * inv;
   }
 
-  // ---- net contact force per reported body: the final impulses / dt, constraint order (oracle: hc_forces)
+  // ---- net contact force per reported body: the impulses the velocities took / dt, constraint order (oracle: hc_forces)
   if (contact_out) {
     GROUP_SYNC();
     if (isbody && half == 0) {
@@ -1321,7 +1321,7 @@ DEV void chain_substep_hard(const StepCtx& C, const ChainLds& L, int l, DofLane&
       for (int c = 0; c < KC; c++) {      // (unrolled: the records of all constraints in flight at once)
         const float* h = tail + T::HC + c * HC_STRIDE;
         const int rep = c < K ? __float_as_int(h[HC_REP]) : -9, repb = c < K ? __float_as_int(h[HC_REPB]) : -9;
-        const bool fin = nvel > 0 || TGS;      // (the final impulses are in HC_PV)
+        const bool fin = nvel > 0;      // (the set the velocities took: HC_PV after velocity iterations, else HC_P)
         const float pf[3] = {(fin ? h[HC_PV0] : h[HC_P]) * idt, (fin ? h[HC_PV1] : h[HC_P + 1]) * idt, (fin ? h[HC_PV2] : h[HC_P + 2]) * idt};
         if (rep == myb) { f[0] += pf[0]; f[1] += pf[1]; f[2] += pf[2]; }
         else if (last && rep == myb + 1) { fw[0] += pf[0]; fw[1] += pf[1]; fw[2] += pf[2]; }

@@ -20,7 +20,7 @@ class FusedAbbEnv(FusedCameraHost):
     def __init__(self, num_envs: int = 4096, device="cuda:0", seed: int = 42, rank: int = 0, world_size: int = 1,
                  group: int = None, dt: float = 0.02, decimation: int = 5, episode_length_s: float = 20.0,
                  extra_boxes=(), link_contacts: bool = None, mapping: str = None, solver: str = None,
-                 link_shapes: str = "box", face_manifold: bool = None):
+                 link_shapes: str = "box", face_manifold: bool = None, solver_kw: dict = None):
         self.device = torch.device(device)
         self.num_envs = num_envs
         self.env_id_offset = rank * num_envs
@@ -76,7 +76,9 @@ class FusedAbbEnv(FusedCameraHost):
             raise ValueError("FusedAbbEnv: mapping='chain' is compiled for the rod-only scene; with link_contacts=True use "
                              "mapping='split' (16 lanes per env) or 'body'")
         self.mapping = mapping
-        self.sim_params = default_sim_params(dt=dt, solver=solver)
+        # solver_kw: the velocity-level solve's settings away from the reference's (backend.set_solver: pos_iters, vel_iters,
+        # max_contacts, ...), as FusedA1Env takes them
+        self.sim_params = default_sim_params(dt=dt, solver=solver, **(solver_kw or {}))
         self.sim = Sim(self.sim_params, self.device)
         self.sim.set_plane(1.0)
         self.sim.set_articulation(self.cm.blob)

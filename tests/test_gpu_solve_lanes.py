@@ -28,24 +28,31 @@ SEED, STEPS = 5, 6
 ENVS = [(0.40, 1.2, -2.4), (0.18, 1.2, -2.4), (0.22, 1.0, -2.2)]      # trunk height over the env's origin, thigh, calf
 
 
-def _setup(n, solver, vel_iters):
+def _inputs(n, solver, vel_iters, pos_iters=8, max_contacts=8, cm=None):
+    """The case's inputs, nothing on the GPU yet: the near-ground states of ENVS (reused in turn beyond the third env) on the seeded
+    terrain.  tests/test_gpu_solve_settings.py runs the same states at other solver settings."""
     from shifu_amd.a1_task import a1_task_params
-    from shifu_amd.backend import A1Task
     rng = np.random.default_rng(SEED)
-    cm = H.a1_model()
+    cm = cm or H.a1_model()
     nd = cm.blob.nd
-    sp = H.sim_params(angular_damping=0.5, solver=solver, max_contacts=8, vel_iters=vel_iters)
-    assert sp.vel_iters == vel_iters and sp.pos_iters == 8
+    sp = H.sim_params(angular_damping=0.5, solver=solver, max_contacts=max_contacts, vel_iters=vel_iters, pos_iters=pos_iters)
+    assert sp.vel_iters == vel_iters and sp.pos_iters == pos_iters
     tp = a1_task_params(cm, num_rows=4, num_cols=5, env_length=0.8)
     terr, hs = _terrain(rng, 60, 70)
     bufs = _a1_buffers(cm, tp, n, rng, terr.rows, terr.cols)
     bufs["ep_len"][:] = 0                                    # no time-outs in six steps
     for e in range(n):
-        z, thigh, calf = ENVS[e]
+        z, thigh, calf = ENVS[e % len(ENVS)]
         q = np.array(H_DEFAULT_Q, np.float32)
         q[1::3], q[2::3] = thigh, calf
         bufs["root_state"][e, 2] = bufs["origins"][e, 2] + z
         bufs["dof_state"][e * nd:(e + 1) * nd, 0] = q
+    return cm, sp, tp, terr, hs, bufs, rng
+
+
+def _setup(n, solver, vel_iters, **kw):
+    from shifu_amd.backend import A1Task
+    cm, sp, tp, terr, hs, bufs, rng = _inputs(n, solver, vel_iters, **kw)
     sim = _make_sim(cm, sp, n, terr, hs, group="chain32")
     task = A1Task(sim, tp)
     _upload(sim, task, bufs)

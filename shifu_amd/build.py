@@ -18,7 +18,7 @@ KERNEL_UNITS = ["shf_k_sim.hip", "shf_k_sim_link.hip", "shf_k_sim_hard.hip", "sh
 UNITY_SOURCES = ["shf_api.hip", "shf_a1_chain.hip", "shf_glue.hip", "shf_mlp.hip", "shf_k_hull_test.hip", "shf_k_cap_select_test.hip", "shf_render.hip", "shf_conv.hip", "shf_lstm.hip", "shf_gru.hip", "shf_dyn.hip", "shf_dyn_fb.hip", "shf_qp.hip", "shf_gait.hip", "shf_mpc.hip"]      # with -DSHF_UNITY: shf_api.hip instantiates every kernel
 SOURCES = UNITY_SOURCES + [u for u in KERNEL_UNITS if u not in UNITY_SOURCES]
 HEADERS = ["shf_device.h", "shf_boxes.h", "shf_task.h", "shf_chain.h", "shf_chain_hard.h", "shf_hard.h", "shf_link.h", "shf_arm.h", "shf_kernels.h",
-           "shf_kernel_list.h", "shf_hull.h", "shf_dyn.h", "shf_rnn_cell.h", os.path.join("..", "..", "include", "shifu_amd.h")]
+           "shf_kernel_list.h", "shf_hull.h", "shf_dyn.h", "shf_rnn_cell.h", "shf_cone.h", "shf_quat.h", os.path.join("..", "..", "include", "shifu_amd.h")]
 DEPS = SOURCES + HEADERS
 # -fno-slp-vectorize: the SLP vectoriser packs neighbouring scalar f32 ops into v_pk_* pairs plus the
 # v_mov shuffles that feed them -- slower for this kernel (measured -6 % at 2 envs/wave, -25 % at one

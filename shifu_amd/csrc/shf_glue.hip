@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../include/shifu_amd.h"
+#include "shf_quat.h"
 
 int shf_set_error(const std::string& msg);   // shf_api.hip: the message shf_last_error() returns
 #define GLUE_LAUNCH_OK(who) (hipGetLastError() == hipSuccess ? 0 : shf_set_error(std::string(who) + ": launch failed"))
@@ -181,18 +182,6 @@ extern "C" int shf_reset_dof_rows(float* dof_state, float* dof_targets, const fl
 // squares u = J^T (J J^T + lambda^2 I)^-1 dpose on the end effector's (6, nd) Jacobian block, dof_pos + u; the 6x6
 // system by LDL^T in packed storage -- the arithmetic of the fused ABB step and of the oracle's glue_ik_dls
 #define GSYM(i, j) ((i) * 6 - ((i) * ((i) - 1)) / 2 + ((j) - (i)))
-static __device__ __forceinline__ void glue_quat_mul(const float* a, const float* b, float* o) {   // torch_utils.py:12-33 (xyzw)
-  const float x1 = a[0], y1 = a[1], z1 = a[2], w1 = a[3], x2 = b[0], y2 = b[1], z2 = b[2], w2 = b[3];
-  const float ww = (z1 + x1) * (x2 + y2);
-  const float yy = (w1 - y1) * (w2 + z2);
-  const float zz = (w1 + y1) * (w2 - z2);
-  const float xx = ww + yy + zz;
-  const float qq = 0.5f * (xx + (z1 - x1) * (x2 - y2));
-  o[3] = qq - ww + (z1 - y1) * (y2 - z2);
-  o[0] = qq - xx + (x1 + w1) * (x2 + w2);
-  o[1] = qq - yy + (w1 - x1) * (y2 + z2);
-  o[2] = qq - zz + (z1 + y1) * (w2 - x2);
-}
 static __device__ __forceinline__ float glue_rcp_spec(float x) {   // the oracle's rcp_spec (csrc/shf_device.h has the same)
   float y = __uint_as_float(0x7EF311C7u - __float_as_uint(x));
 #pragma unroll
@@ -246,7 +235,7 @@ __global__ void k_ik_dls(const float* j_ee, long long j_stride, const float* dof
   for (int k = 0; k < 3; k++) dpose[k] = gp[k] - ee[k];
   cc[0] = -ee[3]; cc[1] = -ee[4]; cc[2] = -ee[5]; cc[3] = ee[6];
   const float tq[4] = {gp[3], gp[4], gp[5], gp[6]};
-  glue_quat_mul(tq, cc, qr);
+  shf_quat_mul(tq, cc, qr);
   const float sg = qr[3] > 0.0f ? 1.0f : (qr[3] < 0.0f ? -1.0f : 0.0f);
 #pragma unroll
   for (int k = 0; k < 3; k++) dpose[3 + k] = qr[k] * sg;
@@ -327,7 +316,7 @@ __global__ void k_osc(OscArgs A) {
   for (int k = 0; k < 3; k++) a[k] = gp[k] - ee[k];
   cc[0] = -ee[3]; cc[1] = -ee[4]; cc[2] = -ee[5]; cc[3] = ee[6];
   const float tq[4] = {gp[3], gp[4], gp[5], gp[6]};
-  glue_quat_mul(tq, cc, qr);
+  shf_quat_mul(tq, cc, qr);
   const float sg = qr[3] > 0.0f ? 1.0f : (qr[3] < 0.0f ? -1.0f : 0.0f);
 #pragma unroll
   for (int k = 0; k < 3; k++) a[3 + k] = qr[k] * sg;

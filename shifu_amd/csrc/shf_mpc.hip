@@ -63,17 +63,14 @@
 //                 + (((W_i[0] L_9) E_s[9] + (W_i[1] L_10) E_s[10]) + (W_i[2] L_11) E_s[11])).
 //   5. m = (sum of P_ii over the contact variables, i ascending) / max(their number, 1)  (1 when nothing ever stands);
 //      rho = sqrt(alpha m),  sigma = 1e-6 m.
-//   6. Constraint rows per (k, f) as shf_foot_force_qp's per foot, A = [(0, 0, 1); (-1, 0, mu); (1, 0, mu); (0, -1, mu); (0, 1, mu)],
-//      bounds [fz_min, fz_max], [0, inf) x 4 with contact, [0, 0] x 5 without.  A^T A is diagonal: (2, 2, 1 + 4 mu^2).
+//   6. The cone's rows and bounds (csrc/shf_cone.h, which states them and the sweep) per (k, f): a foot stands where c_{k,f} = 1.
 //      Kinv = invert(P + (sigma + rho A^T A) on the diagonal), once.
 //   7. x = u_io shifted by warm_shift steps (row min(k + warm_shift, H - 1); 0 without contact), or 0; z = A x; y = 0.
-//      `iters` times:  b = (sigma x - q) + A^T (rho z - y)  (the three forms of shf_foot_force_qp);
-//        xt_i = (a_0 + a_1) + (a_2 + a_3),  a_l = sum over j = l, l + 4, .. of Kinv_ij b_j  (four running sums, j ascending);
-//        zt = A xt;  x = 1.6 xt - 0.6 x;  zr = 1.6 zt - 0.6 z;  z' = clip(zr + y / rho, lo, hi);  y = y + rho (zr - z');  z = z'.
-//   8. Every (k, f): u_z = clip(x_z, fz_min, fz_max), then u_x, u_y = clip(., -mu u_z, mu u_z); +0.0 without contact.  These
-//      go back to u_io; step 0 is forces_out, which therefore satisfies every inequality exactly.
-//   9. efforts_d = -sum_f (Jl_f^T f_f)_d from forces_out, + bias[e, 6 + d], the clamp to +-effort_limit[d] last: the
-//      expression of shf_foot_force_qp's step 8, which k_foot_force_efforts repeats bit for bit.
+//      `iters` of the cone's sweeps with
+//        xt_i = (a_0 + a_1) + (a_2 + a_3),  a_l = sum over j = l, l + 4, .. of Kinv_ij b_j  (four running sums, j ascending).
+//   8. Every (k, f): the cone's exact clamp of x.  These go back to u_io; step 0 is forces_out, which therefore satisfies every
+//      inequality exactly.
+//   9. The efforts: the cone's effort step on forces_out -- the same functions k_foot_force_qp and k_foot_force_efforts call.
 //
 // The mapping.  An env's system is 120 x 120: too large for a thread's registers, too small for a CU, so a workgroup of one
 // wavefront (N <= 64) or two solves one env, thread i owning variable i and row i of P, K and Kinv.  Kinv stays in LDS (57.6
@@ -91,6 +88,7 @@
 #include <string>
 
 #include "../../include/shifu_amd.h"
+#include "shf_cone.h"
 
 int shf_set_error(const std::string& msg);   // shf_api.hip: the message shf_last_error() returns
 
@@ -104,8 +102,6 @@ constexpr int MPC_MAX_N = 3 * MPC_MAX_FEET * MPC_MAX_H;
 // floats of LDS one env's solve takes: Kinv, five vectors (b, pivot row, xt, diagonal, contact flags), W, TX, TY, E, C, S, the forces
 constexpr int mpc_lds_floats(int N4, int H) { return N4 * N4 + 5 * N4 + 6 * N4 + 2 * H * N4 + 12 * H + 2 * (H + 1) + 3 * MPC_MAX_FEET; }
 static_assert(mpc_lds_floats(MPC_MAX_N, MPC_MAX_H) * 4 <= 80 * 1024, "two envs' solves fit the 160 KiB of a CU");
-
-__device__ __forceinline__ float mpc_clip(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
 // ------------------------------------------------------------------------------------------------------ the horizon --
 struct HorizonArgs {
@@ -191,19 +187,17 @@ struct MpcArgs {
   float* forces; float* efforts;
 };
 
-// efforts_d = -sum_f (Jl_f^T f_f)_d + bias, clamped: shf_foot_force_qp's step 8 on forces fo (F x 3, zero where nothing stands)
+// the cone's effort step for dof d of env e on forces fo (F x 3, zero where nothing stands).  A function of its own: written out
+// inside the kernel the solve measured 0.4 % slower, on the same loops (profiles/r25_legged_core.md)
 __device__ __forceinline__ float mpc_effort(const float* j, long long j_env, long long j_foot, const float* bias, const float* limit,
                                             int e, int d, int F, int nd, const float* fo) {
   const int D = nd + 6;
   float tau = 0.0f;
   for (int f = 0; f < F; f++) {
     const float* J = j + (long long)e * j_env + (long long)f * j_foot + 6;   // linear rows, dof columns
-    tau = tau - ((J[d] * fo[3 * f] + J[D + d] * fo[3 * f + 1]) + J[2 * D + d] * fo[3 * f + 2]);
+    tau = tau - cone::effort_term(J, D, d, fo[3 * f], fo[3 * f + 1], fo[3 * f + 2]);
   }
-  if (bias) tau += bias[(long long)e * D + 6 + d];
-  const float lim = limit ? limit[d] : 0.0f;
-  if (lim > 0.0f) tau = tau > lim ? lim : (tau < -lim ? -lim : tau);
-  return tau;
+  return cone::effort_finish(tau, bias, limit, e, D, d);
 }
 
 __global__ void __launch_bounds__(2 * MPC_T) k_foot_force_mpc(MpcArgs A) {
@@ -272,7 +266,7 @@ __global__ void __launch_bounds__(2 * MPC_T) k_foot_force_mpc(MpcArgs A) {
     const float R10 = 2.0f * (qx * qy + qw * qz), R00 = 1.0f - 2.0f * (qy * qy + qz * qz);
     float x[12];
     x[0] = atan2f(R21, R22);
-    x[1] = asinf(mpc_clip(-R20, -1.0f, 1.0f));
+    x[1] = asinf(cone::clip(-R20, -1.0f, 1.0f));
     x[2] = atan2f(R10, R00);
     x[2] = x[2] + rintf((xr[2] - x[2]) * 0.15915494309189535f) * 6.283185307179586f;
 #pragma unroll
@@ -388,7 +382,7 @@ __global__ void __launch_bounds__(2 * MPC_T) k_foot_force_mpc(MpcArgs A) {
   for (int j = 0; j < N; j++) { tr = tr + dg[j] * cf[j]; nc = nc + cf[j]; }
   float mean = tr / fmaxf(nc, 1.0f);
   mean = nc > 0.0f ? mean : 1.0f;
-  const float rho = sqrtf(A.alpha * mean), sigma = 1e-6f * mean;
+  const float rho = sqrtf(A.alpha * mean), sigma = cone::SIGMA * mean;
   if (var) MPC_K(i, i) = dg[i] + (sigma + rho * (ci == 2 ? 1.0f + 4.0f * (mu * mu) : 2.0f));
   for (int k = 0; k < N; k++) {
     __syncthreads();
@@ -417,7 +411,6 @@ __global__ void __launch_bounds__(2 * MPC_T) k_foot_force_mpc(MpcArgs A) {
     }
   }
   // 7. the sweeps
-  const float inf = __builtin_huge_valf();
   const int i0 = i - ci;                         // the foot's x component
   float x = 0.0f, z[5], y[5];
   if (A.u_io && var && con) {
@@ -429,14 +422,12 @@ __global__ void __launch_bounds__(2 * MPC_T) k_foot_force_mpc(MpcArgs A) {
   if (i < N4) xt[i] = x;
   __syncthreads();
   {
-    const float tx = var ? xt[i0] : 0.0f, ty = var ? xt[i0 + 1] : 0.0f, tz = var ? xt[i0 + 2] : 0.0f;
-    const float mz = mu * tz;
-    z[0] = tz; z[1] = mz - tx; z[2] = mz + tx; z[3] = mz - ty; z[4] = mz + ty;
+    cone::rows(mu, var ? xt[i0] : 0.0f, var ? xt[i0 + 1] : 0.0f, var ? xt[i0 + 2] : 0.0f, z);
 #pragma unroll
     for (int m = 0; m < 5; m++) y[m] = 0.0f;
   }
-  const float lo0 = con ? A.fz_min : 0.0f, hi0 = con ? A.fz_max : 0.0f, hic = con ? inf : 0.0f;
-  const float ar = 1.6f, a1 = 1.0f - 1.6f;
+  float lo0, hi0, hic;
+  cone::bounds(con, A.fz_min, A.fz_max, lo0, hi0, hic);
   const float irho = 1.0f / rho;
 #pragma nounroll
   for (int it = 0; it < A.iters; it++) {
@@ -444,9 +435,8 @@ __global__ void __launch_bounds__(2 * MPC_T) k_foot_force_mpc(MpcArgs A) {
       float bi = 0.0f;
       if (var) {
         float v[5];
-#pragma unroll
-        for (int m = 0; m < 5; m++) v[m] = rho * z[m] - y[m];
-        const float add = ci == 0 ? (v[2] - v[1]) : (ci == 1 ? (v[4] - v[3]) : (v[0] + mu * (((v[1] + v[2]) + v[3]) + v[4])));
+        cone::dual(rho, z, y, v);
+        const float add = ci == 0 ? cone::at_x(v) : (ci == 1 ? cone::at_y(v) : cone::at_z(mu, v));
         bi = (sigma * x - qi) + add;
       }
       bv[i] = bi;
@@ -466,17 +456,10 @@ __global__ void __launch_bounds__(2 * MPC_T) k_foot_force_mpc(MpcArgs A) {
     }
     __syncthreads();
     if (var) {
-      const float tx = xt[i0], ty = xt[i0 + 1], tz = xt[i0 + 2];
-      const float mz = mu * tz;
-      const float zt[5] = {tz, mz - tx, mz + tx, mz - ty, mz + ty};
-      x = ar * xi + a1 * x;
-#pragma unroll
-      for (int m = 0; m < 5; m++) {
-        const float zr = ar * zt[m] + a1 * z[m];
-        const float zn = mpc_clip(zr + y[m] * irho, m == 0 ? lo0 : 0.0f, m == 0 ? hi0 : hic);
-        y[m] = y[m] + rho * (zr - zn);
-        z[m] = zn;
-      }
+      float zt[5];
+      cone::rows(mu, xt[i0], xt[i0 + 1], xt[i0 + 2], zt);
+      x = cone::relax(xi, x);
+      cone::project(rho, irho, zt, lo0, hi0, hic, z, y);
     }
   }
   // 8. the forces, exactly feasible
@@ -484,9 +467,7 @@ __global__ void __launch_bounds__(2 * MPC_T) k_foot_force_mpc(MpcArgs A) {
   if (i < N4) xt[i] = x;
   __syncthreads();
   if (var) {
-    const float fz = mpc_clip(xt[i0 + 2], A.fz_min, A.fz_max);
-    const float bnd = mu * fz;
-    const float u = con ? (ci == 2 ? fz : mpc_clip(x, -bnd, bnd)) : 0.0f;
+    const float u = cone::feasible(con, ci, x, xt[i0 + 2], mu, A.fz_min, A.fz_max);
     if (A.u_io) A.u_io[(long long)e * N + i] = u;
     if (i < F3) { fo[i] = u; A.forces[(long long)e * F3 + i] = u; }
   }
@@ -516,13 +497,10 @@ __global__ void __launch_bounds__(MPC_T) k_foot_force_efforts(const float* force
     for (int f = 0; f < MPC_MAX_FEET; f++) {
       if (f < nf) {
         const float* J = j + (long long)e * j_env + (long long)f * j_foot + 6;
-        tau = tau - ((J[d] * fo[3 * f] + J[D + d] * fo[3 * f + 1]) + J[2 * D + d] * fo[3 * f + 2]);
+        tau = tau - cone::effort_term(J, D, d, fo[3 * f], fo[3 * f + 1], fo[3 * f + 2]);
       }
     }
-    if (bias) tau += bias[(long long)e * D + 6 + d];
-    const float lim = limit ? limit[d] : 0.0f;
-    if (lim > 0.0f) tau = tau > lim ? lim : (tau < -lim ? -lim : tau);
-    efforts[(long long)e * nd + d] = tau;
+    efforts[(long long)e * nd + d] = cone::effort_finish(tau, bias, limit, e, D, d);
   }
 }
 

@@ -11,23 +11,20 @@
 //     w = M[0:6, 0:6] (a_lin, a_ang) + h[0:6]              (orientation_error as in shf_ik_dls; the coupling M[0:6, 6:] qdd is neglected).
 //
 // The algorithm: ADMM in OSQP form with a fixed number of sweeps -- no data-dependent trip count, every lane of a wave runs the
-// same instructions.  tests/qp_ref.py `twin` is this text in NumPy, operation by operation.
+// same instructions.  The constraint rows, the sweep around the linear solve, the exact clamp and the effort step are
+// csrc/shf_cone.h's, which states them; what is this kernel's own is below.  tests/qp_ref.py `twin` is this text in NumPy,
+// operation by operation.
 //   1. s_f = 1 for a stance foot, 0 for a swing foot.  Column 3 f + k of G is s_f (e_k, r_f x e_k): a swing foot's columns are
 //      zero, so it decouples.  be = beta if f_prev is given, else 0.
 //   2. P = G^T S G + (alpha + be) I  (P_ij = sum over c = 0..5 of G_ci S_c G_cj, in that order),
 //      q = -G^T (S w) - be s_f f_prev.
 //   3. m = (sum of P_ii over the stance feet's variables) / (3 max(#stance, 1))  (1 when nothing stands);
 //      rho = sqrt((alpha + be) m),  sigma = 1e-6 m.
-//   4. Constraint rows per foot, A_f = [(0, 0, 1); (-1, 0, mu); (1, 0, mu); (0, -1, mu); (0, 1, mu)], bounds
-//      [fz_min, fz_max], [0, inf) x 4 for a stance foot, [0, 0] x 5 for a swing foot.  A^T A is diagonal: (2, 2, 1 + 4 mu^2).
+//   4. The cone's rows and bounds per foot: a stance foot stands, a swing foot does not.
 //   5. K = P + sigma I + rho A^T A = L D L^T once (left-looking, in place, 1 / D kept).
-//   6. x = z = y = 0; `iters` times:
-//        b = sigma x - q + A^T (rho z - y);  xt = K^-1 b (forward, scale, backward);  zt = A xt;
-//        x = 1.6 xt - 0.6 x;  zr = 1.6 zt - 0.6 z;  z' = clip(zr + y / rho, lo, hi);  y = y + rho (zr - z');  z = z'.
-//   7. Output: a swing foot gets 0; a stance foot f_z = clip(x_z, fz_min, fz_max), then f_x, f_y = clip(., -mu f_z, mu f_z), so the
-//      forces written satisfy every constraint exactly.
-//   8. efforts_d = -sum_f (Jl_f^T f_f)_d over the dof columns (6:) of each foot's linear Jacobian rows, from those clamped forces;
-//      + bias[e, 6 + d] when given; the clamp to +-effort_limit[d] last (entries <= 0: no limit), as shf_foot_impedance.
+//   6. x = z = y = 0; `iters` of the cone's sweeps with xt = K^-1 b by forward substitution, scaling, backward substitution.
+//   7. The forces: the cone's exact clamp of x.
+//   8. The efforts: the cone's effort step on those forces.
 // Measured convergence (tests/test_foot_force_qp_host.py, DESIGN.md 8h "Balance controller").
 //
 // Storage: the packed factor (1 / D on its diagonal) and q live in LDS, word k of thread t at [k * 64 + t] as k_osc's arrays (a
@@ -40,6 +37,8 @@
 #include <string>
 
 #include "../../include/shifu_amd.h"
+#include "shf_cone.h"
+#include "shf_quat.h"
 
 int shf_set_error(const std::string& msg);   // shf_api.hip: the message shf_last_error() returns
 
@@ -67,21 +66,6 @@ struct QpArgs {
   float* forces; float* efforts;
 };
 
-__device__ __forceinline__ void qp_quat_mul(const float* a, const float* b, float* o) {   // shf_glue.hip's glue_quat_mul (xyzw)
-  const float x1 = a[0], y1 = a[1], z1 = a[2], w1 = a[3], x2 = b[0], y2 = b[1], z2 = b[2], w2 = b[3];
-  const float ww = (z1 + x1) * (x2 + y2);
-  const float yy = (w1 - y1) * (w2 + z2);
-  const float zz = (w1 + y1) * (w2 - z2);
-  const float xx = ww + yy + zz;
-  const float qq = 0.5f * (xx + (z1 - x1) * (x2 - y2));
-  o[3] = qq - ww + (z1 - y1) * (y2 - z2);
-  o[0] = qq - xx + (x1 + w1) * (x2 + w2);
-  o[1] = qq - yy + (w1 - x1) * (y2 + z2);
-  o[2] = qq - zz + (z1 + y1) * (w2 - x2);
-}
-
-__device__ __forceinline__ float qp_clip(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
-
 template <int NF>
 __global__ void __launch_bounds__(QP_T) k_foot_force_qp(QpArgs A) {
   constexpr int N = 3 * NF, T = QP_T;
@@ -107,7 +91,7 @@ __global__ void __launch_bounds__(QP_T) k_foot_force_qp(QpArgs A) {
     for (int k = 0; k < 3; k++) a[k] = A.gains[k] * (tg[k] - rp[k]) + A.gains[3 + k] * (tg[7 + k] - rp[7 + k]);
     cc[0] = -rp[3]; cc[1] = -rp[4]; cc[2] = -rp[5]; cc[3] = rp[6];
     const float tq[4] = {tg[3], tg[4], tg[5], tg[6]};
-    qp_quat_mul(tq, cc, qr);
+    shf_quat_mul(tq, cc, qr);
     const float sg = qr[3] > 0.0f ? 1.0f : (qr[3] < 0.0f ? -1.0f : 0.0f);
 #pragma unroll
     for (int k = 0; k < 3; k++) a[3 + k] = A.gains[6 + k] * (qr[k] * sg) + A.gains[9 + k] * (tg[10 + k] - rp[10 + k]);
@@ -168,7 +152,7 @@ __global__ void __launch_bounds__(QP_T) k_foot_force_qp(QpArgs A) {
   for (int f = 0; f < NF; f++) ns = ns + s[f];
   float mean = tr / (3.0f * fmaxf(ns, 1.0f));
   mean = ns > 0.0f ? mean : 1.0f;
-  const float rho = sqrtf(ab * mean), sigma = 1e-6f * mean;
+  const float rho = sqrtf(ab * mean), sigma = cone::SIGMA * mean;
   // 5. K = L D L^T in place
   const float dz = 1.0f + 4.0f * (mu * mu);
   float Dg[N];
@@ -189,19 +173,15 @@ __global__ void __launch_bounds__(QP_T) k_foot_force_qp(QpArgs A) {
     }
   }
   // 6. the sweeps
-  const float inf = __builtin_huge_valf();
   float x[N], z[NF][5], y[NF][5], lo0[NF], hi0[NF], hic[NF];
 #pragma unroll
   for (int i = 0; i < N; i++) x[i] = 0.0f;
 #pragma unroll
   for (int f = 0; f < NF; f++) {
-    lo0[f] = st[f] ? A.fz_min : 0.0f;
-    hi0[f] = st[f] ? A.fz_max : 0.0f;
-    hic[f] = st[f] ? inf : 0.0f;
+    cone::bounds(st[f], A.fz_min, A.fz_max, lo0[f], hi0[f], hic[f]);
 #pragma unroll
     for (int m = 0; m < 5; m++) { z[f][m] = 0.0f; y[f][m] = 0.0f; }
   }
-  const float ar = 1.6f, a1 = 1.0f - 1.6f;
   const float irho = 1.0f / rho;
 #pragma nounroll
   for (int it = 0; it < A.iters; it++) {
@@ -209,11 +189,10 @@ __global__ void __launch_bounds__(QP_T) k_foot_force_qp(QpArgs A) {
 #pragma unroll
     for (int f = 0; f < NF; f++) {
       float v[5];
-#pragma unroll
-      for (int m = 0; m < 5; m++) v[m] = rho * z[f][m] - y[f][m];
-      b[3 * f + 0] = (sigma * x[3 * f + 0] - qw[(3 * f + 0) * T]) + (v[2] - v[1]);
-      b[3 * f + 1] = (sigma * x[3 * f + 1] - qw[(3 * f + 1) * T]) + (v[4] - v[3]);
-      b[3 * f + 2] = (sigma * x[3 * f + 2] - qw[(3 * f + 2) * T]) + (v[0] + mu * (((v[1] + v[2]) + v[3]) + v[4]));
+      cone::dual(rho, z[f], y[f], v);
+      b[3 * f + 0] = (sigma * x[3 * f + 0] - qw[(3 * f + 0) * T]) + cone::at_x(v);
+      b[3 * f + 1] = (sigma * x[3 * f + 1] - qw[(3 * f + 1) * T]) + cone::at_y(v);
+      b[3 * f + 2] = (sigma * x[3 * f + 2] - qw[(3 * f + 2) * T]) + cone::at_z(mu, v);
     }
 #pragma unroll
     for (int i = 0; i < N; i++)
@@ -227,31 +206,22 @@ __global__ void __launch_bounds__(QP_T) k_foot_force_qp(QpArgs A) {
       for (int k = i + 1; k < N; k++) b[i] = b[i] - QP_L(k, i) * b[k];
 #pragma unroll
     for (int f = 0; f < NF; f++) {
-      const float tx = b[3 * f], ty = b[3 * f + 1], tz = b[3 * f + 2];
-      const float mz = mu * tz;
-      const float zt[5] = {tz, mz - tx, mz + tx, mz - ty, mz + ty};
+      float zt[5];
+      cone::rows(mu, b[3 * f], b[3 * f + 1], b[3 * f + 2], zt);
 #pragma unroll
-      for (int k = 0; k < 3; k++) x[3 * f + k] = ar * b[3 * f + k] + a1 * x[3 * f + k];
-#pragma unroll
-      for (int m = 0; m < 5; m++) {
-        const float zr = ar * zt[m] + a1 * z[f][m];
-        const float zn = qp_clip(zr + y[f][m] * irho, m == 0 ? lo0[f] : 0.0f, m == 0 ? hi0[f] : hic[f]);
-        y[f][m] = y[f][m] + rho * (zr - zn);
-        z[f][m] = zn;
-      }
+      for (int k = 0; k < 3; k++) x[3 * f + k] = cone::relax(b[3 * f + k], x[3 * f + k]);
+      cone::project(rho, irho, zt, lo0[f], hi0[f], hic[f], z[f], y[f]);
     }
   }
   // 7. the forces, exactly feasible
   float fo[NF][3];
 #pragma unroll
   for (int f = 0; f < NF; f++) {
-    const float fz = qp_clip(x[3 * f + 2], A.fz_min, A.fz_max);
-    const float bnd = mu * fz;
-    fo[f][0] = st[f] ? qp_clip(x[3 * f + 0], -bnd, bnd) : 0.0f;
-    fo[f][1] = st[f] ? qp_clip(x[3 * f + 1], -bnd, bnd) : 0.0f;
-    fo[f][2] = st[f] ? fz : 0.0f;
 #pragma unroll
-    for (int k = 0; k < 3; k++) A.forces[((long long)e * NF + f) * 3 + k] = fo[f][k];
+    for (int k = 0; k < 3; k++) {
+      fo[f][k] = cone::feasible(st[f], k, x[3 * f + k], x[3 * f + 2], mu, A.fz_min, A.fz_max);
+      A.forces[((long long)e * NF + f) * 3 + k] = fo[f][k];
+    }
   }
   // 8. the efforts
   const int nd = A.nd, D = A.nd + 6;
@@ -260,12 +230,9 @@ __global__ void __launch_bounds__(QP_T) k_foot_force_qp(QpArgs A) {
 #pragma unroll
     for (int f = 0; f < NF; f++) {
       const float* J = A.j + (long long)e * A.j_env + (long long)f * A.j_foot + 6;   // linear rows, dof columns
-      tau = tau - ((J[d] * fo[f][0] + J[D + d] * fo[f][1]) + J[2 * D + d] * fo[f][2]);
+      tau = tau - cone::effort_term(J, D, d, fo[f][0], fo[f][1], fo[f][2]);
     }
-    if (A.bias) tau += A.bias[(long long)e * D + 6 + d];
-    const float lim = A.limit ? A.limit[d] : 0.0f;
-    if (lim > 0.0f) tau = tau > lim ? lim : (tau < -lim ? -lim : tau);
-    A.efforts[(long long)e * nd + d] = tau;
+    A.efforts[(long long)e * nd + d] = cone::effort_finish(tau, A.bias, A.limit, e, D, d);
   }
 #undef QP_L
 }

@@ -6,7 +6,8 @@ shifu/units/robot.py:222-229), TerrainGymEnv.get_heights (shifu/gym/isaac_gym.py
 (shifu/utils/train.py:12-35), ShifuVecEnv.log_info / compute_reward (shifu/gym/env.py:149-185).  Each function below is
 that piece as one kernel, used by the mirror classes whenever their tensors live on the GPU.  Results equal the oracle's
 glue_* functions bit for bit (tests/test_gpu_glue.py); there is no CPU path here -- CPU tensors (golden-vector tests of
-the Python mirror) keep the reference's torch expressions in the classes themselves."""
+the Python mirror) keep the reference's torch expressions in the classes themselves.  The two control sequences of the legged
+robots (balance_control, locomotion_control) are the exception: they exist here alone and take the primitives they run on."""
 import ctypes as C
 
 import torch
@@ -167,28 +168,46 @@ def osc(j_ee, mass_matrix, bias, dof_state, ee_pose, goal_pose, kp6, kd6, dampin
     return out
 
 
+def _foot_args(j_feet, bias, effort_limit, mu=None):
+    """What the foot controllers' wrappers check and prepare alike: j_feet (n, F, 6, nd + 6) is a float32 CUDA view with a
+    foot's rows packed (any stride between feet and envs), bias (n, nd + 6) or None, effort_limit (nd) or None, mu a float or a
+    (n) tensor.  Returns (n, F, nd, o, mu_args): o(t) is the pointer of a contiguous float32 copy of an optional tensor (None
+    for None), kept referenced by o until the launch is enqueued; mu_args the (per-env pointer or None, scalar) pair."""
+    n, F, six, D = j_feet.shape
+    assert six == 6 and j_feet.stride(3) == 1 and j_feet.stride(2) == D
+    assert j_feet.is_cuda and j_feet.dtype == torch.float32, "float32 CUDA tensors expected"
+    assert bias is None or tuple(bias.shape) == (n, D)
+    assert effort_limit is None or effort_limit.numel() == D - 6
+    keep = []
+
+    def o(t):
+        if t is None:
+            return None
+        keep.append(t.contiguous())
+        return _f32c(keep[-1])
+
+    per_env = torch.is_tensor(mu) and mu.numel() > 1
+    assert not per_env or mu.numel() == n
+    return n, F, D - 6, o, (o(mu.reshape(n)) if per_env else None, 0.0 if per_env or mu is None else float(mu))
+
+
 def foot_impedance(j_feet, dof_state, root_pose, foot_pos, target, kp3, kd3, bias=None, effort_limit=None):
     """LeggedRobot.foot_impedance_control in one launch (shf_foot_impedance): efforts (n, nd).  j_feet (n, F, 6, nd + 6): the
     foot rows of the floating-base Jacobian tensor (a view: rows packed inside a foot's block, any stride between feet and
     envs); dof_state as for osc; root_pose (n, >= 7) rows (pos, quat xyzw) and foot_pos (n, F, 3) world origins, unit stride
     in the last axis; target (n, F, 3) in the base frame; kp3 / kd3 (3); bias (n, nd + 6) or None; effort_limit (nd) or None."""
-    n, F, six, D = j_feet.shape
-    nd = D - 6
-    assert six == 6 and j_feet.stride(3) == 1 and j_feet.stride(2) == D
-    assert all(t.is_cuda and t.dtype == torch.float32 for t in (j_feet, dof_state, root_pose, foot_pos)), "float32 CUDA tensors expected"
+    n, F, nd, o, _ = _foot_args(j_feet, bias, effort_limit)
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in (dof_state, root_pose, foot_pos)), "float32 CUDA tensors expected"
     assert dof_state.shape[:2] == (n, nd) and dof_state.shape[2] >= 2 and dof_state.stride(2) == 1
     assert dof_state.stride(1) >= 2 and dof_state.stride(0) == nd * dof_state.stride(1)
     assert root_pose.shape[0] == n and root_pose.shape[1] >= 7 and root_pose.stride(1) == 1
     assert foot_pos.shape == (n, F, 3) and foot_pos.stride(2) == 1 and tuple(target.shape) == (n, F, 3)
     assert kp3.numel() == 3 and kd3.numel() == 3
-    assert bias is None or tuple(bias.shape) == (n, D)
-    assert effort_limit is None or effort_limit.numel() == nd
     out = torch.empty(n, nd, device=j_feet.device, dtype=torch.float32)
     with torch.cuda.device(j_feet.device):
         check(lib().shf_foot_impedance(_vp(j_feet.data_ptr()), j_feet.stride(0), j_feet.stride(1), _vp(dof_state.data_ptr()),
                                        dof_state.stride(1), _vp(root_pose.data_ptr()), root_pose.stride(0), _vp(foot_pos.data_ptr()),
-                                       foot_pos.stride(0), foot_pos.stride(1), _f32c(target.contiguous()), _f32c(kp3), _f32c(kd3),
-                                       None if bias is None else _f32c(bias), None if effort_limit is None else _f32c(effort_limit),
+                                       foot_pos.stride(0), foot_pos.stride(1), o(target), _f32c(kp3), _f32c(kd3), o(bias), o(effort_limit),
                                        n, F, nd, _f32c(out), _stream(j_feet.device)))
     return out
 
@@ -204,10 +223,9 @@ def foot_force_qp(j_feet, root_pose, foot_pos, stance, mu, weights6, wrench=None
     stance (n, F) uint8 / bool; mu a float or a (n) tensor; weights6 (6).  The wanted base wrench: `wrench` (n, 6), or
     mass_matrix (n, nd + 6, nd + 6), dyn_bias (n, nd + 6), base_target (n, 13) and gains12 (12) = (kp_lin, kd_lin, kp_ang,
     kd_ang).  f_prev (n, F, 3) or None; bias (n, nd + 6) or None: added to the efforts; effort_limit (nd) or None."""
-    n, F, six, D = j_feet.shape
-    nd = D - 6
-    assert six == 6 and j_feet.stride(3) == 1 and j_feet.stride(2) == D
-    assert all(t.is_cuda and t.dtype == torch.float32 for t in (j_feet, root_pose, foot_pos)), "float32 CUDA tensors expected"
+    n, F, nd, o, mu_args = _foot_args(j_feet, bias, effort_limit, mu)
+    D = nd + 6
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in (root_pose, foot_pos)), "float32 CUDA tensors expected"
     assert root_pose.shape[0] == n and root_pose.shape[1] >= (7 if wrench is not None else 13) and root_pose.stride(1) == 1
     assert foot_pos.shape == (n, F, 3) and foot_pos.stride(2) == 1
     assert tuple(stance.shape) == (n, F) and stance.dtype in (torch.uint8, torch.bool) and stance.is_cuda
@@ -220,48 +238,45 @@ def foot_force_qp(j_feet, root_pose, foot_pos, stance, mu, weights6, wrench=None
     else:
         assert tuple(wrench.shape) == (n, 6)
     assert f_prev is None or tuple(f_prev.shape) == (n, F, 3)
-    assert bias is None or tuple(bias.shape) == (n, D)
-    assert effort_limit is None or effort_limit.numel() == nd
-    per_env = torch.is_tensor(mu) and mu.numel() > 1
-    assert not per_env or mu.numel() == n
     st = stance.contiguous().view(torch.uint8)
-    keep = []                 # contiguous copies of optional inputs stay referenced until the launch is enqueued
-
-    def o(t):
-        if t is None:
-            return None
-        keep.append(t.contiguous())
-        return _f32c(keep[-1])
-
     forces = torch.empty(n, F, 3, device=j_feet.device, dtype=torch.float32)
     out = torch.empty(n, nd, device=j_feet.device, dtype=torch.float32)
     with torch.cuda.device(j_feet.device):
         check(lib().shf_foot_force_qp(_vp(j_feet.data_ptr()), j_feet.stride(0), j_feet.stride(1), _vp(root_pose.data_ptr()),
                                       root_pose.stride(0), _vp(foot_pos.data_ptr()), foot_pos.stride(0), foot_pos.stride(1),
                                       o(wrench), o(mass_matrix), o(dyn_bias), o(base_target), o(gains12), _vp(st.data_ptr()),
-                                      o(mu.reshape(n)) if per_env else None, 0.0 if per_env else float(mu), o(weights6),
+                                      *mu_args, o(weights6),
                                       float(alpha), float(beta), o(f_prev), float(fz_min), float(fz_max), int(iters), o(bias),
                                       o(effort_limit), n, F, nd, _f32c(forces), _f32c(out), _stream(j_feet.device)))
     return forces, out
 
 
-def gain3(g, device):
-    g = torch.as_tensor(g, dtype=torch.float32, device=device)
+def gain3(g, device, dtype=torch.float32):
+    g = torch.as_tensor(g, dtype=dtype, device=device)
     return (g.expand(3) if g.dim() == 0 else g.reshape(3)).contiguous()
+
+
+def _kernels():
+    """The default set of primitives of balance_control / locomotion_control: this module's kernel wrappers.  The other set,
+    utils.torch_utils.Primitives, presents the torch expressions under the same names and signatures."""
+    import sys
+    return sys.modules[__name__]
 
 
 def balance_control(j_feet, root_state, foot_pos, contact_z, shape_friction, ground_friction, mass_matrix, bias, target, effort_limit,
                     base_pos, base_quat, base_lin_vel=None, base_ang_vel=None, stance=None, kp_lin=100., kd_lin=None, kp_ang=400.,
                     kd_ang=None, mu=None, fz_min=5., fz_max=None, weights=(1, 1, 1, 10, 10, 10), alpha=1e-2, beta=0.,
-                    gravity_compensation=True, f_prev=None):
+                    gravity_compensation=True, f_prev=None, prims=None):
     """What LeggedRobot.balance_control and FusedA1Env.balance_control share: the gains (kd None = 2 sqrt(kp)), the base target
     written into the caller's (n, 13) buffer `target`, stance None = the feet whose contact force z (contact_z (n, F)) exceeds
     1 N, mu None = the friction the simulator applies, (shape_friction (n) + ground_friction) / 2 -- formed per call, so it
-    follows the friction tensor --, then foot_force_qp.  Returns (efforts, forces)."""
-    dev = j_feet.device
-    kpl, kpa = gain3(kp_lin, dev), gain3(kp_ang, dev)
-    gains = torch.cat([kpl, 2.0 * torch.sqrt(kpl) if kd_lin is None else gain3(kd_lin, dev),
-                       kpa, 2.0 * torch.sqrt(kpa) if kd_ang is None else gain3(kd_ang, dev)])
+    follows the friction tensor --, then foot_force_qp.  prims: the primitives it runs on (None = this module's kernels;
+    constants are made in j_feet's dtype, float32 for those).  Returns (efforts, forces)."""
+    prims = prims or _kernels()
+    dev, T = j_feet.device, j_feet.dtype
+    kpl, kpa = gain3(kp_lin, dev, T), gain3(kp_ang, dev, T)
+    gains = torch.cat([kpl, 2.0 * torch.sqrt(kpl) if kd_lin is None else gain3(kd_lin, dev, T),
+                       kpa, 2.0 * torch.sqrt(kpa) if kd_ang is None else gain3(kd_ang, dev, T)])
     target[:, :3], target[:, 3:7] = base_pos, base_quat
     target[:, 7:10] = 0.0 if base_lin_vel is None else base_lin_vel
     target[:, 10:13] = 0.0 if base_ang_vel is None else base_ang_vel
@@ -269,10 +284,10 @@ def balance_control(j_feet, root_state, foot_pos, contact_z, shape_friction, gro
         stance = (contact_z > 1.0).to(torch.uint8)
     if mu is None:
         mu = 0.5 * (shape_friction + float(ground_friction))
-    S = torch.as_tensor(weights, dtype=torch.float32, device=dev).reshape(6).contiguous()
-    forces, efforts = foot_force_qp(j_feet, root_state, foot_pos, stance, mu, S, None, mass_matrix, bias, target, gains, alpha, beta,
-                                    f_prev if beta > 0 else None, fz_min, float("inf") if fz_max is None else float(fz_max), QP_ITERS,
-                                    bias if gravity_compensation else None, effort_limit)
+    S = torch.as_tensor(weights, dtype=T, device=dev).reshape(6).contiguous()
+    forces, efforts = prims.foot_force_qp(j_feet, root_state, foot_pos, stance, mu, S, None, mass_matrix, bias, target, gains, alpha, beta,
+                                          f_prev if beta > 0 else None, fz_min, float("inf") if fz_max is None else float(fz_max),
+                                          QP_ITERS, bias if gravity_compensation else None, effort_limit)
     return efforts, forces
 
 
@@ -385,35 +400,21 @@ def foot_force_mpc(contact, xref, pos, root_state, mass_matrix, dyn_bias, j_feet
     foot_force_qp; mass_matrix (n, nd + 6, nd + 6), dyn_bias (n, nd + 6); mu a float or a (n) tensor; weights12 (12); step_dt:
     mpc_step_dt(S, dt); bias (n, nd + 6) or None: added to the efforts; effort_limit (nd) or None; u_io (n, H, F, 3)
     contiguous or None: the warm start, read shifted by warm_shift steps and overwritten with the solution."""
-    n, F, six, D = j_feet.shape
-    nd = D - 6
-    H = contact.shape[1]
-    assert six == 6 and j_feet.stride(3) == 1 and j_feet.stride(2) == D
-    assert all(t.is_cuda and t.dtype == torch.float32 for t in (j_feet, root_state, xref, pos)), "float32 CUDA tensors expected"
+    n, F, nd, o, mu_args = _foot_args(j_feet, bias, effort_limit, mu)
+    D, H = nd + 6, contact.shape[1]
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in (root_state, xref, pos)), "float32 CUDA tensors expected"
     assert root_state.shape[0] == n and root_state.shape[1] >= 13 and root_state.stride(1) == 1
     assert tuple(contact.shape) == (n, H, F) and contact.dtype == torch.uint8 and contact.is_cuda
     assert tuple(xref.shape) == (n, H + 1, 12) and tuple(pos.shape) == (n, H, F, 3)
     assert tuple(mass_matrix.shape) == (n, D, D) and tuple(dyn_bias.shape) == (n, D) and weights12.numel() == 12
-    assert bias is None or tuple(bias.shape) == (n, D)
-    assert effort_limit is None or effort_limit.numel() == nd
     assert u_io is None or (tuple(u_io.shape) == (n, H, F, 3) and u_io.is_contiguous() and u_io.is_cuda and u_io.dtype == torch.float32)
-    per_env = torch.is_tensor(mu) and mu.numel() > 1
-    assert not per_env or mu.numel() == n
-    keep = []                 # contiguous copies stay referenced until the launch is enqueued
-
-    def o(t):
-        if t is None:
-            return None
-        keep.append(t.contiguous())
-        return _f32c(keep[-1])
-
     ct = contact.contiguous()
     forces = torch.empty(n, F, 3, device=j_feet.device, dtype=torch.float32) if forces_out is None else forces_out
     out = torch.empty(n, nd, device=j_feet.device, dtype=torch.float32)
     with torch.cuda.device(j_feet.device):
         check(lib().shf_foot_force_mpc(_vp(ct.data_ptr()), o(xref), o(pos), _vp(root_state.data_ptr()), root_state.stride(0),
                                        o(mass_matrix), o(dyn_bias), _vp(j_feet.data_ptr()), j_feet.stride(0), j_feet.stride(1),
-                                       o(mu.reshape(n)) if per_env else None, 0.0 if per_env else float(mu), o(weights12),
+                                       *mu_args, o(weights12),
                                        float(alpha), float(fz_min), float(fz_max), int(iters), float(step_dt), o(bias),
                                        o(effort_limit), None if u_io is None else _f32c(u_io), int(warm_shift), n, H, F, nd,
                                        _f32c(forces), _f32c(out), _stream(j_feet.device)))
@@ -423,31 +424,24 @@ def foot_force_mpc(contact, xref, pos, root_state, mass_matrix, dyn_bias, j_feet
 def foot_force_efforts(forces, stance, j_feet, bias=None, effort_limit=None):
     """efforts (n, nd) = -sum over the feet with stance != 0 of Jl_f^T f_f, + bias[:, 6:], clamped to +-effort_limit, in one launch
     (shf_foot_force_efforts): the effort step of foot_force_qp / foot_force_mpc on its own, bit-equal to theirs."""
-    n, F, six, D = j_feet.shape
-    nd = D - 6
-    assert six == 6 and j_feet.stride(3) == 1 and j_feet.stride(2) == D and j_feet.is_cuda and j_feet.dtype == torch.float32
+    n, F, nd, o, _ = _foot_args(j_feet, bias, effort_limit)
     assert tuple(forces.shape) == (n, F, 3) and tuple(stance.shape) == (n, F) and stance.dtype in (torch.uint8, torch.bool)
-    assert bias is None or tuple(bias.shape) == (n, D)
-    assert effort_limit is None or effort_limit.numel() == nd
-    f, st = forces.contiguous(), stance.contiguous().view(torch.uint8)
-    b = None if bias is None else bias.contiguous()
-    lim = None if effort_limit is None else effort_limit.contiguous()
+    st = stance.contiguous().view(torch.uint8)
     out = torch.empty(n, nd, device=j_feet.device, dtype=torch.float32)
     with torch.cuda.device(j_feet.device):
-        check(lib().shf_foot_force_efforts(_f32c(f), _vp(st.data_ptr()), _vp(j_feet.data_ptr()), j_feet.stride(0), j_feet.stride(1),
-                                           None if b is None else _f32c(b), None if lim is None else _f32c(lim), n, F, nd,
-                                           _f32c(out), _stream(j_feet.device)))
+        check(lib().shf_foot_force_efforts(o(forces), _vp(st.data_ptr()), _vp(j_feet.data_ptr()), j_feet.stride(0), j_feet.stride(1),
+                                           o(bias), o(effort_limit), n, F, nd, _f32c(out), _stream(j_feet.device)))
     return out
 
 
 _CONSTANTS = {}
 
 
-def _constant(values, device):
-    """A small float32 device tensor of python numbers, made once per value and device."""
-    key = (str(device), tuple(float(v) for v in values))
+def _constant(values, device, dtype=torch.float32):
+    """A small device tensor of python numbers, made once per value, device and dtype."""
+    key = (str(device), dtype, tuple(float(v) for v in values))
     if key not in _CONSTANTS:
-        _CONSTANTS[key] = torch.tensor(key[1], dtype=torch.float32, device=device)
+        _CONSTANTS[key] = torch.tensor(key[2], dtype=dtype, device=device)
     return _CONSTANTS[key]
 
 
@@ -460,7 +454,8 @@ def locomotion_control(j_feet, dof_state, root_state, foot_pos, contact_z, shape
                        effort_limit, chain_mask, nominal, state, command, gait, dt, height=0.30, touchdown_z=0.01, swing_kp=400.,
                        swing_kd=10., reset=None, kp_lin=100., kd_lin=None, kp_ang=400., kd_ang=None, mu=None, fz_min=5., fz_max=None,
                        weights=(1, 1, 1, 10, 10, 10), alpha=1e-2, gravity_compensation=True, controller="qp", horizon=MPC_HORIZON,
-                       mpc_steps_per_tick=None, mpc_every=MPC_EVERY, mpc_weights=MPC_WEIGHTS, mpc_alpha=MPC_ALPHA, mpc_iters=MPC_ITERS):
+                       mpc_steps_per_tick=None, mpc_every=MPC_EVERY, mpc_weights=MPC_WEIGHTS, mpc_alpha=MPC_ALPHA, mpc_iters=MPC_ITERS,
+                       prims=None):
     """What LeggedRobot.locomotion_control and FusedA1Env.locomotion_control share, four launches: the gait plan (base target
     and stance from `gait`'s schedule gated by contact_z, swing targets), foot_force_qp on that target and stance (as
     balance_control: kd None = 2 sqrt(kp), mu None = (shape_friction + ground_friction) / 2), foot_impedance towards the swing
@@ -470,44 +465,44 @@ def locomotion_control(j_feet, dof_state, root_state, foot_pos, contact_z, shape
     after a reset), `horizon` steps of mpc_steps_per_tick gait ticks (None = ceil(period_ticks / horizon): the horizon covers
     one gait period), warm-started from the last solve; on the ticks in between foot_force_efforts holds the last solve's forces
     on the current Jacobian (a foot that has lifted since counts as zero; `forces` is then the held solve's).  The QP's gains
-    and weights are not read by the MPC.  Returns (efforts (n, nd), forces (n, F, 3), stance (n, F), swing_targets (n, F, 3))."""
+    and weights are not read by the MPC.  prims: the primitives it runs on, as balance_control's.  Returns (efforts (n, nd),
+    forces (n, F, 3), stance (n, F), swing_targets (n, F, 3))."""
     import math
-    dev = j_feet.device
+    prims = prims or _kernels()
+    dev, T = j_feet.device, j_feet.dtype
     if reset is None:
         reset = state.take_pending()
-    stance, swing_t, _ = gait_plan(state, root_state, foot_pos, contact_z, command, nominal, reset, gait.ticks(dt),
-                                   gait_params(dt, height, touchdown_z, gait))
-    kpl, kpa = _vec3(kp_lin), _vec3(kp_ang)
-    kdl = [2.0 * math.sqrt(k) for k in kpl] if kd_lin is None else _vec3(kd_lin)
-    kda = [2.0 * math.sqrt(k) for k in kpa] if kd_ang is None else _vec3(kd_ang)
-    gains = _constant(kpl + kdl + kpa + kda, dev)
+    ticks, params = gait.ticks(dt), prims.gait_params(dt, height, touchdown_z, gait)
+    stance, swing_t, _ = prims.gait_plan(state, root_state, foot_pos, contact_z, command, nominal, reset, ticks, params)
     if mu is None:
         mu = 0.5 * (shape_friction + float(ground_friction))
+    fz_max = float("inf") if fz_max is None else float(fz_max)
+    tau_bias = bias if gravity_compensation else None
     if controller == "mpc":
-        ticks = gait.ticks(dt)
         S = int(mpc_steps_per_tick) if mpc_steps_per_tick else -(-ticks[0] // int(horizon))
         u_io, held = state.mpc_buffers(horizon)
         if reset is not None:                        # a reset env starts cold, and everybody solves on this tick
-            keep = (1 - reset.view(torch.uint8).to(torch.float32))
+            keep = (1 - reset.view(torch.uint8).to(u_io.dtype))
             u_io.mul_(keep.view(-1, 1, 1, 1))
             state.mpc_count = 0
         if state.mpc_count % max(int(mpc_every), 1) == 0:
-            params = gait_params(dt, height, touchdown_z, gait)
-            contact, xref, pos = mpc_horizon(state, stance, foot_pos, command, nominal, ticks, params, horizon, S)
-            forces, tau_st = foot_force_mpc(contact, xref, pos, root_state, mass_matrix, bias, j_feet, mu, _constant(mpc_weights, dev),
-                                            mpc_alpha, fz_min, float("inf") if fz_max is None else float(fz_max), mpc_iters,
-                                            mpc_step_dt(S, dt), bias if gravity_compensation else None, effort_limit, u_io,
-                                            int(mpc_every) // S, forces_out=held)
+            contact, xref, pos = prims.mpc_horizon(state, stance, foot_pos, command, nominal, ticks, params, horizon, S)
+            forces, tau_st = prims.foot_force_mpc(contact, xref, pos, root_state, mass_matrix, bias, j_feet, mu,
+                                                  _constant(mpc_weights, dev, T), mpc_alpha, fz_min, fz_max, mpc_iters, mpc_step_dt(S, dt),
+                                                  tau_bias, effort_limit, u_io, int(mpc_every) // S, forces_out=held)
         else:
             forces = held
-            tau_st = foot_force_efforts(held, stance, j_feet, bias if gravity_compensation else None, effort_limit)
+            tau_st = prims.foot_force_efforts(held, stance, j_feet, tau_bias, effort_limit)
         state.mpc_count += 1
     elif controller == "qp":
-        forces, tau_st = foot_force_qp(j_feet, root_state, foot_pos, stance, mu, _constant(weights, dev), None, mass_matrix, bias,
-                                       state.target, gains, alpha, 0.0, None, fz_min, float("inf") if fz_max is None else float(fz_max),
-                                       QP_ITERS, bias if gravity_compensation else None, effort_limit)
+        kpl, kpa = _vec3(kp_lin), _vec3(kp_ang)
+        kdl = [2.0 * math.sqrt(k) for k in kpl] if kd_lin is None else _vec3(kd_lin)
+        kda = [2.0 * math.sqrt(k) for k in kpa] if kd_ang is None else _vec3(kd_ang)
+        forces, tau_st = prims.foot_force_qp(j_feet, root_state, foot_pos, stance, mu, _constant(weights, dev, T), None, mass_matrix, bias,
+                                             state.target, _constant(kpl + kdl + kpa + kda, dev, T), alpha, 0.0, None, fz_min, fz_max,
+                                             QP_ITERS, tau_bias, effort_limit)
     else:
         raise ValueError(f"locomotion_control: controller {controller!r} (\"qp\" or \"mpc\")")
-    tau_sw = foot_impedance(j_feet, dof_state, root_state, foot_pos, swing_t, _constant(_vec3(swing_kp), dev),
-                            _constant(_vec3(swing_kd), dev), None, effort_limit)
-    return leg_effort_mix(tau_st, tau_sw, stance, chain_mask, effort_limit), forces, stance, swing_t
+    tau_sw = prims.foot_impedance(j_feet, dof_state, root_state, foot_pos, swing_t, _constant(_vec3(swing_kp), dev, T),
+                                  _constant(_vec3(swing_kd), dev, T), None, effort_limit)
+    return prims.leg_effort_mix(tau_st, tau_sw, stance, chain_mask, effort_limit), forces, stance, swing_t

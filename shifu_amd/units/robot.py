@@ -349,6 +349,14 @@ class LeggedRobot(ArmRobot):
             self._bal_chain = mask.to(self.device)
         return self._bal_chain
 
+    @staticmethod
+    def _control_prims(*tensors):
+        """The primitives glue's control sequences run on: the kernels (None) for float32 CUDA tensors, else their torch expressions."""
+        if all(t.is_cuda and t.dtype == torch.float32 for t in tensors):
+            return None
+        from shifu_amd.utils.torch_utils import Primitives
+        return Primitives
+
     def stance_from_contacts(self, threshold=1.0):
         """(num_envs, num_ee) uint8: the end bodies whose net contact force along z, as last refreshed, exceeds `threshold`."""
         return (self._end_rows(self.contact_forces)[..., 2] > threshold).to(torch.uint8)
@@ -376,28 +384,13 @@ class LeggedRobot(ArmRobot):
         root = self.env.root_state.view(n, -1, 13)[:, 0]
         feet = self._end_rows(self.env.body_state.view(n, -1, 13))[..., :3]
         f_prev = getattr(self, "_bal_forces", None)
-        if jf.is_cuda and jf.dtype == torch.float32 and tg.is_cuda:
-            # the expressions of utils.torch_utils.balance_wrench / foot_force_qp as one launch (csrc/shf_qp.hip: shf_foot_force_qp)
-            from shifu_amd import _abi, glue
-            be = self.sim.backend
-            efforts, forces = glue.balance_control(
-                jf, root, feet, self._end_rows(self.contact_forces)[..., 2], be.tensors[_abi.T_FRICTION], be.terrain.friction, M, h, tg,
-                self.torque_limits.contiguous(), base_pos, base_quat, base_lin_vel, base_ang_vel, stance, kp_lin, kd_lin, kp_ang,
-                kd_ang, mu, fz_min, fz_max, weights, alpha, beta, gravity_compensation, f_prev)
-        else:
-            from shifu_amd.utils.torch_utils import balance_wrench, foot_force_qp
-            kpl, kpa = self._gain3(kp_lin), self._gain3(kp_ang)
-            gains = torch.cat([kpl, 2.0 * torch.sqrt(kpl) if kd_lin is None else self._gain3(kd_lin),
-                               kpa, 2.0 * torch.sqrt(kpa) if kd_ang is None else self._gain3(kd_ang)])
-            tg[:, :3], tg[:, 3:7] = base_pos, base_quat
-            tg[:, 7:10] = 0.0 if base_lin_vel is None else base_lin_vel
-            tg[:, 10:13] = 0.0 if base_ang_vel is None else base_ang_vel
-            S = torch.as_tensor(weights, dtype=torch.float32, device=self.device).reshape(6)
-            forces, efforts = foot_force_qp(jf, root[:, :3], feet, balance_wrench(M, h, root, tg, gains),
-                                            self.stance_from_contacts() if stance is None else stance,
-                                            self._contact_friction() if mu is None else mu, S, alpha, beta, f_prev if beta > 0 else None,
-                                            fz_min, float("inf") if fz_max is None else float(fz_max), 100,
-                                            h if gravity_compensation else None, self.torque_limits)
+        # one sequence (glue.balance_control) on the kernels (csrc/shf_qp.hip: shf_foot_force_qp), or on their torch expressions
+        from shifu_amd import _abi, glue
+        be = self.sim.backend
+        efforts, forces = glue.balance_control(
+            jf, root, feet, self._end_rows(self.contact_forces)[..., 2], be.tensors[_abi.T_FRICTION].to(self.device), be.terrain.friction,
+            M, h, tg, self.torque_limits.contiguous(), base_pos, base_quat, base_lin_vel, base_ang_vel, stance, kp_lin, kd_lin, kp_ang,
+            kd_ang, mu, fz_min, fz_max, weights, alpha, beta, gravity_compensation, f_prev, prims=self._control_prims(jf, tg))
         self._bal_forces = forces
         return efforts, forces
 
@@ -496,59 +489,12 @@ class LeggedRobot(ArmRobot):
         if getattr(self, "_gait_chain", None) is None:
             self._gait_chain = self._foot_dof_mask().to(torch.uint8)
         command = torch.as_tensor(command, dtype=torch.float32, device=self.device).expand(n, 3)
-        if jf.is_cuda and jf.dtype == torch.float32:
-            from shifu_amd import _abi, glue
-            be = self.sim.backend
-            efforts, forces, stance, swing = glue.locomotion_control(
-                jf, self.env.dof_state.view(n, self.num_dof, 2), root, feet, cz, be.tensors[_abi.T_FRICTION], be.terrain.friction, M, h,
-                self.torque_limits.contiguous(), self._gait_chain, self.nominal_foot_positions, st, command, gait, dt, height,
-                touchdown_z, swing_kp, swing_kd, **balance_kw)
-        else:
-            from shifu_amd.utils import torch_utils as TU
-            from shifu_amd import glue as G_
-            kw = dict(kp_lin=100., kd_lin=None, kp_ang=400., kd_ang=None, mu=None, fz_min=5., fz_max=None, weights=(1, 1, 1, 10, 10, 10),
-                      alpha=1e-2, gravity_compensation=True, controller="qp", horizon=G_.MPC_HORIZON, mpc_steps_per_tick=None,
-                      mpc_every=G_.MPC_EVERY, mpc_weights=G_.MPC_WEIGHTS, mpc_alpha=G_.MPC_ALPHA, mpc_iters=G_.MPC_ITERS)
-            kw.update(balance_kw)
-            pending = st.take_pending()
-            stance, swing, _, _ = TU.gait_plan(st, root, feet, cz, command, self.nominal_foot_positions, pending, gait.ticks(dt),
-                                               dt, height, gait.apex, touchdown_z, gait.late_depth, gait.k_fb, gait.max_step, gait.leash,
-                                               gait.contact_threshold)
-            kpl, kpa = self._gain3(kw["kp_lin"]), self._gain3(kw["kp_ang"])
-            gains = torch.cat([kpl, 2.0 * torch.sqrt(kpl) if kw["kd_lin"] is None else self._gain3(kw["kd_lin"]),
-                               kpa, 2.0 * torch.sqrt(kpa) if kw["kd_ang"] is None else self._gain3(kw["kd_ang"])])
-            S = torch.as_tensor(kw["weights"], dtype=torch.float32, device=self.device).reshape(6)
-            mu_, fz_max_ = self._contact_friction() if kw["mu"] is None else kw["mu"], float("inf") if kw["fz_max"] is None else float(kw["fz_max"])
-            if kw["controller"] == "mpc":
-                # the torch expressions of glue.locomotion_control's "mpc" branch (csrc/shf_mpc.hip)
-                tk, Hn, every = gait.ticks(dt), int(kw["horizon"]), max(int(kw["mpc_every"]), 1)
-                Sx = int(kw["mpc_steps_per_tick"]) if kw["mpc_steps_per_tick"] else -(-tk[0] // Hn)
-                u_io, held = st.mpc_buffers(Hn)
-                if pending is not None:
-                    u_io[pending.bool()] = 0.0
-                    st.mpc_count = 0
-                if st.mpc_count % every == 0:
-                    contact, xref, pos = TU.mpc_horizon(st, stance, feet, command, self.nominal_foot_positions, tk, dt, touchdown_z,
-                                                        gait.max_step, Hn, Sx)
-                    L12 = torch.as_tensor(kw["mpc_weights"], dtype=torch.float32, device=self.device).reshape(12)
-                    forces, tau_st = TU.foot_force_mpc(contact, xref, pos, root, M, h, jf, mu_, L12, kw["mpc_alpha"], kw["fz_min"], fz_max_,
-                                                       kw["mpc_iters"], G_.mpc_step_dt(Sx, dt), h if kw["gravity_compensation"] else None,
-                                                       self.torque_limits, u_io, every // Sx)
-                    held.copy_(forces)
-                else:
-                    forces = held
-                    tau_st = TU.foot_force_efforts(held, stance, jf, h if kw["gravity_compensation"] else None, self.torque_limits)
-                st.mpc_count += 1
-            elif kw["controller"] == "qp":
-                forces, tau_st = TU.foot_force_qp(jf, root[:, :3], feet, TU.balance_wrench(M, h, root, st.target, gains), stance, mu_, S,
-                                                  kw["alpha"], 0.0, None, kw["fz_min"], fz_max_, 100,
-                                                  h if kw["gravity_compensation"] else None, self.torque_limits)
-            else:
-                raise ValueError(f"locomotion_control: controller {kw['controller']!r} (\"qp\" or \"mpc\")")
-            tau_sw = TU.foot_impedance_control(jf, self.dof_vel, root[:, :3], root[:, 3:7], feet, swing, self._gain3(swing_kp),
-                                               self._gain3(swing_kd), None, self.torque_limits)
-            efforts = TU.leg_effort_mix(tau_st, tau_sw, stance, self._gait_chain, self.torque_limits)
-        return efforts, forces, stance, swing
+        from shifu_amd import _abi, glue
+        be = self.sim.backend
+        return glue.locomotion_control(
+            jf, self.env.dof_state.view(n, self.num_dof, 2), root, feet, cz, be.tensors[_abi.T_FRICTION].to(self.device), be.terrain.friction,
+            M, h, self.torque_limits.contiguous(), self._gait_chain, self.nominal_foot_positions, st, command, gait, dt, height,
+            touchdown_z, swing_kp, swing_kd, **balance_kw, prims=self._control_prims(jf))
 
     def apply_locomotion_control(self, command, **kw):
         """decimation x {refresh the state, Jacobian, mass-matrix and bias tensors, locomotion_control (one gait tick), set the

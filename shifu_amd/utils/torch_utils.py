@@ -27,6 +27,14 @@ def inverse_kinematics(dof_pos, ee_pos, ee_quat, tar_pos, tar_quat, j_ee, device
     return dof_pos + u
 
 
+def _effort_clamp(tau, effort_limit):
+    """tau clamped to +-effort_limit (entries <= 0: no limit; None: no clamp)."""
+    if effort_limit is None:
+        return tau
+    lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
+    return torch.maximum(torch.minimum(tau, lim), -lim)
+
+
 def wrap_to_pi(x):
     return x - 2.0 * torch.pi * torch.round(x / (2.0 * torch.pi))
 
@@ -50,10 +58,7 @@ def operational_space_control(j_ee, mass_matrix, dof_pos, dof_vel, ee_pos, ee_qu
         tau = tau + (mass_matrix @ u - jt @ torch.linalg.solve(A, j_ee @ u)).squeeze(-1)
     if bias is not None:
         tau = tau + bias
-    if effort_limit is not None:
-        lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
-        tau = torch.maximum(torch.minimum(tau, lim), -lim)
-    return tau
+    return _effort_clamp(tau, effort_limit)
 
 
 def quat_to_matrix(q):
@@ -79,10 +84,7 @@ def foot_impedance_control(j_feet, dof_vel, root_pos, root_quat, foot_pos, targe
     tau = (torch.transpose(jl, 2, 3) @ f).squeeze(-1).sum(1)
     if bias is not None:
         tau = tau + bias[:, 6:]
-    if effort_limit is not None:
-        lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
-        tau = torch.maximum(torch.minimum(tau, lim), -lim)
-    return tau
+    return _effort_clamp(tau, effort_limit)
 
 
 def balance_wrench(mass_matrix, bias, root_state, base_target, gains12):
@@ -117,14 +119,61 @@ def _ldlt_inverse(K):
     return X
 
 
+def _cone_ata(mu, feet):
+    """The diagonal of A^T A (n, 3 feet) of the friction-cone rows: (2, 2, 1 + 4 mu^2) per foot."""
+    d = torch.stack([torch.full_like(mu, 2.0), torch.full_like(mu, 2.0), 1.0 + 4.0 * (mu * mu)], -1)
+    return d.unsqueeze(1).expand(mu.shape[0], feet, 3).reshape(mu.shape[0], 3 * feet)
+
+
+def _cone_admm(Kinv, q, sigma, rho, mu, contact, fz_min, fz_max, iters, x0=None):
+    """The friction-cone ADMM sweeps and the exact clamp of csrc/shf_cone.h as batched torch expressions: forces (n, feet, 3).
+    Kinv (n, N, N) = (P + sigma I + rho A^T A)^-1 and q (n, N) over N = 3 feet variables (a foot of a horizon step counts as a
+    foot); sigma, rho (n, 1); mu (n) >= 0; contact (n, feet) bool: the feet that stand; x0 (n, feet, 3) or None: the warm start,
+    read where the foot stands."""
+    n, feet = contact.shape
+    N, T, dev = 3 * feet, q.dtype, q.device
+    mu_, rho3 = mu.view(n, 1), rho.unsqueeze(-1)
+
+    def rows(v):                                   # A v of every foot: (n, feet, 5)
+        v = v.reshape(n, feet, 3)
+        mz = mu_ * v[..., 2]
+        return torch.stack([v[..., 2], mz - v[..., 0], mz + v[..., 0], mz - v[..., 1], mz + v[..., 1]], -1)
+
+    x = torch.zeros(n, N, dtype=T, device=dev)
+    if x0 is not None:
+        x = torch.where(contact.unsqueeze(-1), x0, x.view(n, feet, 3)).reshape(n, N)
+    z, y = rows(x), torch.zeros(n, feet, 5, dtype=T, device=dev)
+    zero = torch.zeros(n, feet, dtype=T, device=dev)
+    lo, hi = torch.zeros(n, feet, 5, dtype=T, device=dev), torch.zeros(n, feet, 5, dtype=T, device=dev)
+    lo[..., 0] = torch.where(contact, torch.full_like(zero, fz_min), zero)
+    hi[..., 0] = torch.where(contact, torch.full_like(zero, fz_max), zero)
+    hi[..., 1:] = torch.where(contact, torch.full_like(zero, float("inf")), zero).unsqueeze(-1)
+    for _ in range(int(iters)):
+        v = rho3 * z - y
+        add = torch.stack([v[..., 2] - v[..., 1], v[..., 4] - v[..., 3],
+                           v[..., 0] + mu_ * (((v[..., 1] + v[..., 2]) + v[..., 3]) + v[..., 4])], -1).reshape(n, N)
+        xt = (Kinv @ ((sigma * x - q) + add).unsqueeze(-1)).squeeze(-1)
+        zt = rows(xt)
+        x = 1.6 * xt + (1.0 - 1.6) * x
+        zr = 1.6 * zt + (1.0 - 1.6) * z
+        zn = torch.minimum(torch.maximum(zr + y / rho3, lo), hi)
+        y = y + rho3 * (zr - zn)
+        z = zn
+    xv = x.reshape(n, feet, 3)
+    fz = xv[..., 2].clamp(fz_min, fz_max)
+    bnd = mu_ * fz
+    f = torch.stack([torch.minimum(torch.maximum(xv[..., 0], -bnd), bnd), torch.minimum(torch.maximum(xv[..., 1], -bnd), bnd), fz], -1)
+    return torch.where(contact.unsqueeze(-1), f, torch.zeros_like(f))
+
+
 def foot_force_qp(j_feet, root_pos, foot_pos, wrench, stance, mu, weights6, alpha=1e-2, beta=0.0, f_prev=None, fz_min=5.0,
                   fz_max=float("inf"), iters=100, bias=None, effort_limit=None):
     """Foot-force distribution of the balance controller: (forces (n, F, 3), efforts (n, nd)).  Per env, with r_f = p_foot_f -
     p_root and G = [[I .. I], [[r_1]x .. [r_F]x]], minimise 1/2 (G f - w)^T S (G f - w) + 1/2 alpha |f|^2 + 1/2 beta |f - f_prev|^2
     subject to fz_min <= f_z <= fz_max, |f_x|, |f_y| <= mu f_z on the stance feet and f = 0 on the others, by `iters` sweeps of
-    ADMM (rho = sqrt((alpha + beta) m), sigma = 1e-6 m, m the mean diagonal of the stance feet's Hessian block; relaxation
-    1.6) on K^-1 from one LDL^T, then the exact per-foot clamp; efforts = -sum_f Jl_f^T f_f (+ bias[:, 6:]), clamped to +-effort_limit last.  The
-    algorithm of csrc/shf_qp.hip's shf_foot_force_qp in torch (its CPU fallback); tests/qp_ref.py holds the NumPy twin."""
+    _cone_admm (rho = sqrt((alpha + beta) m), sigma = 1e-6 m, m the mean diagonal of the stance feet's Hessian block) on K^-1
+    from one LDL^T; the efforts are foot_force_efforts' of those forces.  The algorithm of csrc/shf_qp.hip's shf_foot_force_qp
+    in torch (its CPU fallback); tests/qp_ref.py holds the NumPy twin."""
     n, F = stance.shape
     N, dt, dev = 3 * F, j_feet.dtype, j_feet.device
     s = stance.to(dt)
@@ -151,49 +200,9 @@ def foot_force_qp(j_feet, root_pos, foot_pos, wrench, stance, mu, weights6, alph
     mean = (torch.diagonal(P, dim1=1, dim2=2) * sv).sum(1) / (3.0 * ns.clamp(min=1.0))
     mean = torch.where(ns > 0, mean, torch.ones_like(mean))
     rho, sigma = torch.sqrt(ab * mean).view(n, 1), (1e-6 * mean).view(n, 1)
-    # the rows of one foot: f_z, mu f_z - f_x, mu f_z + f_x, mu f_z - f_y, mu f_z + f_y
-    Af = torch.zeros(n, 5, 3, dtype=dt, device=dev)
-    Af[:, :, 2] = mu.view(n, 1)
-    Af[:, 0, 2] = 1.0
-    Af[:, 1, 0], Af[:, 2, 0], Af[:, 3, 1], Af[:, 4, 1] = -1.0, 1.0, -1.0, 1.0
-    A = torch.zeros(n, F, 5, F, 3, dtype=dt, device=dev)
-    for f in range(F):
-        A[:, f, :, f, :] = Af
-    A = A.reshape(n, 5 * F, N)
-    At = torch.transpose(A, 1, 2)
-    K = P + sigma.unsqueeze(-1) * eye + rho.unsqueeze(-1) * (At @ A)
-    Kinv = _ldlt_inverse(K)
-    inf = float("inf")
-    lo = torch.zeros(n, F, 5, dtype=dt, device=dev)
-    hi = torch.zeros(n, F, 5, dtype=dt, device=dev)
-    lo[:, :, 0] = fz_min
-    hi[:, :, 0], hi[:, :, 1:] = fz_max, inf
-    lo = torch.where(st.unsqueeze(-1), lo, torch.zeros_like(lo)).reshape(n, 5 * F)
-    hi = torch.where(st.unsqueeze(-1), hi, torch.zeros_like(hi)).reshape(n, 5 * F)
-    x = torch.zeros(n, N, dtype=dt, device=dev)
-    z = torch.zeros(n, 5 * F, dtype=dt, device=dev)
-    y = torch.zeros(n, 5 * F, dtype=dt, device=dev)
-    for _ in range(int(iters)):
-        b = sigma * x - q + (At @ (rho * z - y).unsqueeze(-1)).squeeze(-1)
-        xt = Kinv @ b.unsqueeze(-1)
-        zt = (A @ xt).squeeze(-1)
-        x = 1.6 * xt.squeeze(-1) + (1.0 - 1.6) * x
-        zr = 1.6 * zt + (1.0 - 1.6) * z
-        zn = torch.minimum(torch.maximum(zr + y / rho, lo), hi)
-        y = y + rho * (zr - zn)
-        z = zn
-    x = x.view(n, F, 3)
-    fz = x[..., 2].clamp(fz_min, fz_max)
-    bnd = mu.view(n, 1) * fz
-    forces = torch.stack([torch.minimum(torch.maximum(x[..., 0], -bnd), bnd), torch.minimum(torch.maximum(x[..., 1], -bnd), bnd), fz], -1)
-    forces = torch.where(st.unsqueeze(-1), forces, torch.zeros_like(forces))
-    tau = -(torch.transpose(j_feet[:, :, :3, 6:], 2, 3) @ forces.unsqueeze(-1)).squeeze(-1).sum(1)
-    if bias is not None:
-        tau = tau + bias[:, 6:]
-    if effort_limit is not None:
-        lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
-        tau = torch.maximum(torch.minimum(tau, lim), -lim)
-    return forces, tau
+    K = P + torch.diag_embed(sigma + rho * _cone_ata(mu, F))
+    forces = _cone_admm(_ldlt_inverse(K), q, sigma, rho, mu, st, fz_min, fz_max, iters)
+    return forces, foot_force_efforts(forces, stance, j_feet, bias, effort_limit)
 
 
 def gait_plan(state, root_state, foot_pos, contact_z, command, nominal, reset, ticks, dt, height, apex, touchdown_z, late_depth, k_fb,
@@ -288,10 +297,7 @@ def leg_effort_mix(stance_efforts, swing_efforts, stance, chain_mask, effort_lim
     shf_leg_effort_mix."""
     m = ((stance == 0).unsqueeze(-1) & (chain_mask != 0).unsqueeze(0)).any(1).to(stance_efforts.dtype)
     tau = stance_efforts + m * swing_efforts
-    if effort_limit is not None:
-        lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
-        tau = torch.maximum(torch.minimum(tau, lim), -lim)
-    return tau
+    return _effort_clamp(tau, effort_limit)
 
 
 # -- the horizon MPC (csrc/shf_mpc.hip, whose header states the three algorithms step by step; tests/mpc_ref.py holds the NumPy twins)
@@ -441,43 +447,9 @@ def foot_force_mpc(contact, xref, pos, root_state, mass_matrix, dyn_bias, j_feet
     mean = (dgl * cf).sum(1) / nc.clamp(min=1.0)
     mean = torch.where(nc > 0, mean, torch.ones_like(mean))
     rho, sigma = torch.sqrt(float(alpha) * mean).view(n, 1), (1e-6 * mean).view(n, 1)
-    ata = torch.where((ci == 2).unsqueeze(0), (1.0 + 4.0 * (mu * mu)).view(n, 1), torch.full((n, N), 2.0, dtype=T, device=dev))
-    Kinv = _gauss_jordan_inverse(P + torch.diag_embed(sigma + rho * ata))
-    con = cf != 0
-    x = torch.zeros(n, N, dtype=T, device=dev)
-    if u_io is not None:
-        kk = (torch.arange(H, device=dev) + int(warm_shift)).clamp(max=H - 1)
-        x = torch.where(con, u_io[:, kk].reshape(n, N).to(T), x)
-    mu_ = mu.view(n, 1)
-
-    def rows(v):
-        v = v.reshape(n, H * F, 3)
-        mz = mu_ * v[..., 2]
-        return torch.stack([v[..., 2], mz - v[..., 0], mz + v[..., 0], mz - v[..., 1], mz + v[..., 1]], -1)
-
-    z, y = rows(x), torch.zeros(n, H * F, 5, dtype=T, device=dev)
-    cfoot = con.reshape(n, H * F, 3)[..., 0]
-    lo, hi = torch.zeros(n, H * F, 5, dtype=T, device=dev), torch.zeros(n, H * F, 5, dtype=T, device=dev)
-    lo[..., 0] = torch.where(cfoot, torch.full_like(lo[..., 0], fz_min), lo[..., 0])
-    hi[..., 0] = torch.where(cfoot, torch.full_like(hi[..., 0], fz_max), hi[..., 0])
-    hi[..., 1:] = torch.where(cfoot, torch.full_like(hi[..., 0], float("inf")), hi[..., 0]).unsqueeze(-1)
-    rho3 = rho.unsqueeze(-1)
-    for _ in range(int(iters)):
-        v = rho3 * z - y
-        add = torch.stack([v[..., 2] - v[..., 1], v[..., 4] - v[..., 3],
-                           v[..., 0] + mu_ * (((v[..., 1] + v[..., 2]) + v[..., 3]) + v[..., 4])], -1).reshape(n, N)
-        xt = (Kinv @ ((sigma * x - q) + add).unsqueeze(-1)).squeeze(-1)
-        zt = rows(xt)
-        x = 1.6 * xt + (1.0 - 1.6) * x
-        zr = 1.6 * zt + (1.0 - 1.6) * z
-        zn = torch.minimum(torch.maximum(zr + y / rho3, lo), hi)
-        y = y + rho3 * (zr - zn)
-        z = zn
-    xv = x.reshape(n, H * F, 3)
-    fz = xv[..., 2].clamp(fz_min, fz_max)
-    bnd = mu_ * fz
-    u = torch.stack([torch.minimum(torch.maximum(xv[..., 0], -bnd), bnd), torch.minimum(torch.maximum(xv[..., 1], -bnd), bnd), fz], -1)
-    u = torch.where(cfoot.unsqueeze(-1), u, torch.zeros_like(u)).reshape(n, H, F, 3)
+    Kinv = _gauss_jordan_inverse(P + torch.diag_embed(sigma + rho * _cone_ata(mu, H * F)))
+    x0 = None if u_io is None else u_io[:, (torch.arange(H, device=dev) + int(warm_shift)).clamp(max=H - 1)].reshape(n, H * F, 3).to(T)
+    u = _cone_admm(Kinv, q, sigma, rho, mu, (cf != 0).reshape(n, H * F, 3)[..., 0], fz_min, fz_max, iters, x0).reshape(n, H, F, 3)
     if u_io is not None:
         u_io.copy_(u)
     forces = u[:, 0]
@@ -491,7 +463,48 @@ def foot_force_efforts(forces, stance, j_feet, bias=None, effort_limit=None):
     tau = -(torch.transpose(j_feet[:, :, :3, 6:], 2, 3) @ f.unsqueeze(-1)).squeeze(-1).sum(1)
     if bias is not None:
         tau = tau + bias[:, 6:]
-    if effort_limit is not None:
-        lim = torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
-        tau = torch.maximum(torch.minimum(tau, lim), -lim)
-    return tau
+    return _effort_clamp(tau, effort_limit)
+
+
+class Primitives:
+    """The functions above under the signatures of shifu_amd.glue's kernel wrappers: the set of primitives
+    glue.balance_control / glue.locomotion_control run on when the tensors are not float32 CUDA tensors."""
+
+    @staticmethod
+    def gait_params(dt, height, touchdown_z, gait):
+        from types import SimpleNamespace
+        return SimpleNamespace(dt=float(dt), height=float(height), apex=gait.apex, touchdown_z=float(touchdown_z), late_depth=gait.late_depth,
+                               k_fb=gait.k_fb, max_step=gait.max_step, leash=gait.leash, contact_threshold=gait.contact_threshold)
+
+    @staticmethod
+    def gait_plan(state, root_state, foot_pos, contact_z, command, nominal, reset, ticks, p):
+        return gait_plan(state, root_state, foot_pos, contact_z, command, nominal, reset, ticks, p.dt, p.height, p.apex, p.touchdown_z,
+                         p.late_depth, p.k_fb, p.max_step, p.leash, p.contact_threshold)[:3]
+
+    @staticmethod
+    def foot_force_qp(j_feet, root_pose, foot_pos, stance, mu, weights6, wrench=None, mass_matrix=None, dyn_bias=None, base_target=None,
+                      gains12=None, alpha=1e-2, beta=0.0, f_prev=None, fz_min=5.0, fz_max=float("inf"), iters=100, bias=None,
+                      effort_limit=None):
+        if wrench is None:
+            wrench = balance_wrench(mass_matrix, dyn_bias, root_pose, base_target, gains12)
+        return foot_force_qp(j_feet, root_pose[:, :3], foot_pos, wrench, stance, mu, weights6, alpha, beta, f_prev, fz_min, fz_max, iters,
+                             bias, effort_limit)
+
+    @staticmethod
+    def mpc_horizon(state, stance, foot_pos, command, nominal, ticks, p, horizon, steps_per_tick):
+        return mpc_horizon(state, stance, foot_pos, command, nominal, ticks, p.dt, p.touchdown_z, p.max_step, horizon, steps_per_tick)
+
+    @staticmethod
+    def foot_force_mpc(*args, forces_out=None):
+        forces, efforts = foot_force_mpc(*args)
+        if forces_out is not None:
+            forces = forces_out.copy_(forces)
+        return forces, efforts
+
+    foot_force_efforts = staticmethod(foot_force_efforts)
+    leg_effort_mix = staticmethod(leg_effort_mix)
+
+    @staticmethod
+    def foot_impedance(j_feet, dof_state, root_pose, foot_pos, target, kp3, kd3, bias=None, effort_limit=None):
+        return foot_impedance_control(j_feet, dof_state[..., 1], root_pose[:, :3], root_pose[:, 3:7], foot_pos, target, kp3, kd3, bias,
+                                      effort_limit)

@@ -12,9 +12,10 @@
 """
 import numpy as np
 
+from tests import cone_ref as CR
 from tests import qp_ref as Q
+from tests.cone_ref import RELAX, SIGMA_C              # the sweep's constants live with the sweep (re-exported)
 
-SIGMA_C, RELAX = 1e-6, 1.6                             # the kernel's constants (csrc/shf_mpc.hip)
 # glue's defaults (DESIGN.md 8h "Horizon MPC" says where each comes from)
 HORIZON, ITERS, ALPHA, EVERY = 10, 100, 1e-5, 1
 WEIGHTS12 = (25.0, 25.0, 10.0, 2.0, 2.0, 50.0, 0.0, 0.0, 0.3, 0.2, 0.2, 0.2)
@@ -264,8 +265,7 @@ def twin(prob, mu, weights, alpha, fz_min, fz_max, iters=ITERS, dtype=np.float64
 
     def rows(v):                                   # A v of every (k, f): (n, H F, 5)
         v = v.reshape(n, H * F, 3)
-        mz = mu_ * v[..., 2]
-        return np.stack([v[..., 2], mz - v[..., 0], mz + v[..., 0], mz - v[..., 1], mz + v[..., 1]], -1)
+        return np.stack(CR.rows(mu_, v[..., 0], v[..., 1], v[..., 2]), -1)
 
     z, y = rows(x), np.zeros((n, H * F, 5), T)
     cfoot = con.reshape(n, H * F, 3)[..., 0]
@@ -275,13 +275,10 @@ def twin(prob, mu, weights, alpha, fz_min, fz_max, iters=ITERS, dtype=np.float64
     lo[..., 0] = np.where(cfoot, T(fz_min), T(0))
     hi[..., 0] = np.where(cfoot, T(fz_max), T(0))
     hi[..., 1:] = np.where(cfoot, inf, T(0))[..., None]
-    ar, a1 = T(RELAX), T(1) - T(RELAX)
     irho = (T(1) / rho)[:, None, None]
     rho3, rho2 = rho[:, None, None], rho[:, None]
     for _ in range(int(iters)):
-        v = rho3 * z - y
-        add = np.stack([v[..., 2] - v[..., 1], v[..., 4] - v[..., 3],
-                        v[..., 0] + mu_ * (((v[..., 1] + v[..., 2]) + v[..., 3]) + v[..., 4])], -1).reshape(n, N)
+        add = np.stack(CR.at(mu_, np.moveaxis(rho3 * z - y, -1, 0)), -1).reshape(n, N)
         b = np.zeros((n, N4), T)
         b[:, :N] = (sigma[:, None] * x - q) + add
         s = [np.zeros((n, N), T) for _ in range(4)]
@@ -290,16 +287,10 @@ def twin(prob, mu, weights, alpha, fz_min, fz_max, iters=ITERS, dtype=np.float64
                 s[l] = s[l] + Kinv[:, :, 4 * j4 + l] * b[:, 4 * j4 + l, None]
         xt = (s[0] + s[1]) + (s[2] + s[3])
         zt = rows(xt)
-        x = ar * xt + a1 * x
-        zr = ar * zt + a1 * z
-        zn = np.minimum(np.maximum(zr + y * irho, lo), hi)
-        y = y + rho3 * (zr - zn)
-        z = zn
+        x = CR.relax(xt, x, T)
+        z, y = CR.project(zt, z, y, rho3, irho, lo, hi, T)
     xv = x.reshape(n, H * F, 3)
-    fz = np.minimum(np.maximum(xv[..., 2], T(fz_min)), T(fz_max))
-    bnd = mu_ * fz
-    u = np.stack([np.minimum(np.maximum(xv[..., 0], -bnd), bnd), np.minimum(np.maximum(xv[..., 1], -bnd), bnd), fz], -1)
-    u = np.where(cfoot[..., None], u, T(0)).astype(T).reshape(n, H, F, 3)
+    u = np.stack(CR.feasible(cfoot, mu_, xv[..., 0], xv[..., 1], xv[..., 2], fz_min, fz_max, T), -1).astype(T).reshape(n, H, F, 3)
     if return_state:
         return u, {"x": x.reshape(n, H, F, 3), "rho": rho2, "sigma": sigma, "P": P, "q": q}
     return u

@@ -36,15 +36,19 @@ def steps_per_tick(tk, horizon=R.HORIZON):
     return -(-tk[0] // horizon)
 
 
-def control(m, state, mpc, q, qd, root, feet_pos, contact_z, command, tk, P, every, reset=None, horizon=R.HORIZON, iters=R.ITERS):
-    """One control tick in float64 on float32 state, as trot_cpu.control: (efforts float32, forces, stance, swing targets).
-    mpc: the dict {"u", "forces", "count"} kept between ticks (empty at the start)."""
+def control(m, state, mpc, q, qd, root, feet_pos, contact_z, command, tk, P, every, reset=None, horizon=R.HORIZON, iters=R.ITERS,
+            out=np.float32):
+    """One control tick in float64 on float32 state, as trot_cpu.control: (efforts float32 or `out`, forces, stance, swing
+    targets).  mpc: the dict {"u", "forces", "count"} kept between ticks (empty at the start).  As glue.locomotion_control, a
+    reset makes everybody solve on this tick and the reset envs start cold (a zero warm start is a cold start)."""
     plan = G.plan(state, root, feet_pos, contact_z, command, B.swing_targets(m), reset, *tk, P)
     J, M, h = B.dynamics64(m, q, qd, root)
     limit = np.array([m.effort[d] for d in range(m.nd)])
     S = steps_per_tick(tk, horizon)
-    if reset is not None or "u" not in mpc or mpc.get("tk") != tk:
+    if "u" not in mpc or mpc.get("tk") != tk:
         mpc.update(u=None, count=0, tk=tk)
+    if reset is not None:
+        mpc.update(u=None if mpc["u"] is None else mpc["u"] * (np.asarray(reset) == 0)[:, None, None, None], count=0)
     if mpc["count"] % every == 0:
         contact, xref, pos = R.horizon(state["tick"], state["target"], state["yaw"], *tk, plan["stance"], feet_pos, command,
                                        B.swing_targets(m), P, horizon, S)
@@ -57,7 +61,7 @@ def control(m, state, mpc, q, qd, root, feet_pos, contact_z, command, tk, P, eve
     _, tau_sw = FR.foot_impedance(J, qd, root[:, :3], root[:, 3:7], feet_pos, plan["swing_target"], np.full(3, T.SWING_KP),
                                   np.full(3, T.SWING_KD), None, limit)
     tau = G.mix(tau_st, tau_sw, plan["stance"], T.chain_mask(m), limit)
-    return tau.astype(np.float32), f, plan["stance"], plan["swing_target"]
+    return tau.astype(out), f, plan["stance"], plan["swing_target"]
 
 
 def run(every=R.EVERY, controller="mpc", settle=T.SETTLE, trot=T.TROT, vx=T.VX, trot_ticks=T.TROT_TICKS, n=T.N_ENVS, verbose=False):

@@ -15,7 +15,10 @@ import itertools
 
 import numpy as np
 
-RHO_C, SIGMA_C, RELAX, ITERS = 1.0, 1e-6, 1.6, 100     # the kernel's constants (csrc/shf_qp.hip) and glue's default sweeps
+from tests import cone_ref as CR
+from tests.cone_ref import RELAX, SIGMA_C              # the sweep's constants live with the sweep (re-exported)
+
+RHO_C, ITERS = 1.0, 100                                # the kernel's constant (csrc/shf_qp.hip) and glue's default sweeps
 
 
 # ------------------------------------------------------------------------------------------------------ the problem --
@@ -142,15 +145,13 @@ def twin(r, w, S, alpha, beta, f_prev, stance, mu, fz_min, fz_max, iters=ITERS, 
     x = [zero] * N
     z = [[zero] * 5 for _ in range(F)]
     y = [[zero] * 5 for _ in range(F)]
-    a, a1 = T(RELAX), T(1) - T(RELAX)
     irho = one / rho
     for _ in range(int(iters)):
         b = [None] * N
         for f in range(F):
-            v = [rho * z[f][m] - y[f][m] for m in range(5)]
-            b[3 * f + 0] = (sigma * x[3 * f + 0] - q[3 * f + 0]) + (v[2] - v[1])
-            b[3 * f + 1] = (sigma * x[3 * f + 1] - q[3 * f + 1]) + (v[4] - v[3])
-            b[3 * f + 2] = (sigma * x[3 * f + 2] - q[3 * f + 2]) + (v[0] + mu * (((v[1] + v[2]) + v[3]) + v[4]))
+            add = CR.at(mu, [rho * z[f][m] - y[f][m] for m in range(5)])
+            for k in range(3):
+                b[3 * f + k] = (sigma * x[3 * f + k] - q[3 * f + k]) + add[k]
         for i in range(N):
             for k in range(i):
                 b[i] = b[i] - L[i][k] * b[k]
@@ -160,23 +161,14 @@ def twin(r, w, S, alpha, beta, f_prev, stance, mu, fz_min, fz_max, iters=ITERS, 
             for k in range(i + 1, N):
                 b[i] = b[i] - L[k][i] * b[k]
         for f in range(F):
-            tx, ty, tz = b[3 * f], b[3 * f + 1], b[3 * f + 2]
-            mz = mu * tz
-            zt = [tz, mz - tx, mz + tx, mz - ty, mz + ty]
+            zt = CR.rows(mu, b[3 * f], b[3 * f + 1], b[3 * f + 2])
             for k in range(3):
-                x[3 * f + k] = a * b[3 * f + k] + a1 * x[3 * f + k]
+                x[3 * f + k] = CR.relax(b[3 * f + k], x[3 * f + k], T)
             for m in range(5):
-                zr = a * zt[m] + a1 * z[f][m]
-                zn = np.minimum(np.maximum(zr + y[f][m] * irho, lo[f][m]), hi[f][m])
-                y[f][m] = y[f][m] + rho * (zr - zn)
-                z[f][m] = zn
+                z[f][m], y[f][m] = CR.project(zt[m], z[f][m], y[f][m], rho, irho, lo[f][m], hi[f][m], T)
     out = np.zeros((n, F, 3), T)
     for f in range(F):
-        fz = np.minimum(np.maximum(x[3 * f + 2], T(fz_min)), T(fz_max))
-        bnd = mu * fz
-        out[:, f, 0] = np.where(st[:, f], np.minimum(np.maximum(x[3 * f + 0], -bnd), bnd), T(0))
-        out[:, f, 1] = np.where(st[:, f], np.minimum(np.maximum(x[3 * f + 1], -bnd), bnd), T(0))
-        out[:, f, 2] = np.where(st[:, f], fz, T(0))
+        out[:, f, 0], out[:, f, 1], out[:, f, 2] = CR.feasible(st[:, f], mu, x[3 * f], x[3 * f + 1], x[3 * f + 2], fz_min, fz_max, T)
     if return_state:
         return out, {"x": np.stack(x, 1).reshape(n, F, 3), "y": np.stack([np.stack(v, 1) for v in y], 1), "rho": rho, "sigma": sigma}
     return out

@@ -140,6 +140,25 @@ def test_kernel_matches_the_float64_twin(n, case):
         assert (st[1:] != st[:-1]).any(1).mean() > 0.5, "neighbouring lanes take different branches"
 
 
+def test_the_effort_step_alone_is_bit_equal_to_the_solver_s():
+    """glue.foot_force_efforts on the forces foot_force_qp returned gives foot_force_qp's efforts bit for bit (one effort step in
+    csrc/shf_cone.h behind both), and clearing a foot's stance is the same as zeroing its force.  The 'dynamics' case (bias and
+    limits) at 65 envs: more than one block."""
+    _need_gpu()
+    from shifu_amd import glue
+    S = _setup()
+    sl = slice(0, 65)
+    forces, efforts = _launch(S, sl, "dynamics")
+    jf, stance, h = S["jf"][sl], S["stance"][sl], S["h"][sl]
+    assert torch.equal(glue.foot_force_efforts(forces, stance, jf, h, S["limit"]), efforts)
+    assert (forces[:, 1].abs().amax(1) > 0).sum() > 30, "the foot that is cleared below carries force in many envs"
+    cleared, zeroed = stance.clone(), forces.clone()
+    cleared[:, 1], zeroed[:, 1] = 0, 0.0
+    a = glue.foot_force_efforts(forces, cleared, jf, h, S["limit"])
+    b = glue.foot_force_efforts(zeroed, stance, jf, h, S["limit"])
+    assert torch.equal(a, b) and not torch.equal(a, efforts)
+
+
 def test_torch_fallback_on_the_gpu_matches_the_kernel_at_4096_envs():
     """utils.torch_utils.balance_wrench + foot_force_qp on CUDA float32 tensors (what LeggedRobot.balance_control runs when the
     kernel's input conditions are not met) against the kernel, on the seeded launch tiled to 4112 envs -- a batch size at which

@@ -60,8 +60,9 @@ def chain_mask(m):
     return mask
 
 
-def control(m, state, q, qd, root, feet_pos, contact_z, command, tk, P, swing_kp=SWING_KP, swing_kd=SWING_KD, reset=None):
-    """One control tick in float64 on float32 state: (efforts (n, nd) float32, forces, stance, swing targets)."""
+def control(m, state, q, qd, root, feet_pos, contact_z, command, tk, P, swing_kp=SWING_KP, swing_kd=SWING_KD, reset=None, out=np.float32):
+    """One control tick in float64 on float32 state: (efforts (n, nd) float32 -- what the simulator takes; `out` float64 keeps
+    them as computed --, forces, stance, swing targets)."""
     n = q.shape[0]
     plan = G.plan(state, root, feet_pos, contact_z, command, B.swing_targets(m), reset, *tk, P)
     J, M, h = B.dynamics64(m, q, qd, root)
@@ -73,7 +74,7 @@ def control(m, state, q, qd, root, feet_pos, contact_z, command, tk, P, swing_kp
     _, tau_sw = FR.foot_impedance(J, qd, root[:, :3], root[:, 3:7], feet_pos, plan["swing_target"], np.full(3, swing_kp),
                                   np.full(3, swing_kd), None, limit)
     tau = G.mix(tau_st, tau_sw, plan["stance"], chain_mask(m), limit)
-    return tau.astype(np.float32), f, plan["stance"], plan["swing_target"]
+    return tau.astype(out), f, plan["stance"], plan["swing_target"]
 
 
 def run(settle=SETTLE, trot=TROT, vx=VX, trot_ticks=TROT_TICKS, swing_kp=SWING_KP, swing_kd=SWING_KD, n=N_ENVS, verbose=False, **over):

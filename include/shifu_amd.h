@@ -1067,6 +1067,58 @@ int shf_foot_force_mpc(const uint8_t* contact, const float* xref, const float* p
 int shf_foot_force_efforts(const float* forces, const uint8_t* stance, const float* j_feet, int64_t j_env_stride,
                            int64_t j_foot_stride, const float* bias_or_null, const float* effort_limit_or_null, int32_t n,
                            int32_t num_feet, int32_t num_dof, float* efforts_out, void* stream);
+/* ---- actuator models: command delay, PD or actuator network, motor strength, DC-motor clip (csrc/shf_actuator.hip, whose
+ * header states the algorithm step by step).  One launch is one simulation sub-step; the work item is one (env, dof) pair
+ * and reads no other pair's state.  Per pair, with t = target[e, d] and (q, qd) the dof's state: the command history shifts
+ * and takes t at slot 0; a = the slot `delay` calls back; err = a - q; tau = (kp err) - (kd qd) (SHF_ACTUATOR_PD) or
+ * out_scale net(err_scale err_hist[taps], vel_scale vel_hist[taps]) (SHF_ACTUATOR_NET, after the two histories have taken err
+ * and qd at slot 0); tau = tau strength[e, d]; then the DC motor's clip when saturation and velocity_limit are given,
+ *   r = qd / vlim,  hi = min(max(sat (1 - r), 0), lim),  lo = max(min(sat (-1 - r), 0), -lim),  tau = max(min(tau, hi), lo),
+ * else the clamp to +-effort_limit[d]; an effort_limit entry <= 0 or a NULL effort_limit: no limit.
+ * Views: target (n, num_dof) contiguous; dof (e, d) has its position at dof_state[(e * num_dof + d) * dof_elem_stride] and
+ * its velocity one float later (as for shf_osc); kp / kd at [e * gain_env_stride + d], gain_env_stride 0 (shared (num_dof)
+ * gains) or num_dof (per-env gains), unused and NULL-able in network mode; delay (n) int32, clamped to 0..cmd_slots-1, or
+ * NULL for delay_scalar; strength (n, num_dof) or NULL; saturation / velocity_limit / effort_limit (num_dof) or NULL; reset
+ * (n) uint8 or NULL: an env with reset != 0 starts from cmd_hist = t and zero err / vel histories.  State, caller-owned,
+ * updated in place: cmd_hist (n, cmd_slots, num_dof), and in network mode err_hist / vel_hist (n, hist_slots, num_dof);
+ * slot 0 is this call's value, slot k the value from k calls ago.  Outputs: applied_target_out (n, num_dof) or NULL (the
+ * delayed command a), efforts_out (n, num_dof).
+ * The network (HOST struct): num_layers linear layers of widths[0] = 2 num_taps inputs .. widths[num_layers] = 1 output,
+ * the activation on every layer but the last, taps = the history lags read.  weights: ONE device buffer, 16-byte aligned,
+ * zero-padded -- the inputs to 8, every hidden width to P = 32 (no hidden width above 32) or 64 -- holding, per layer, W
+ * row-major (out, in) and then b: the first layer (P, 8) + (P), the num_layers - 2 middle layers (P, P) + (P), the last layer
+ * (1, P) + (1); a one-layer net is its last layer alone over the inputs padded to P = 32; the whole rounded up to a multiple of
+ * 4 floats = weights_count.
+ * Refused with a message: num_dof outside 1..SHF_MAX_DOFS, n < 1, dof_elem_stride < 2, cmd_slots or hist_slots outside 1..8,
+ * delay_scalar outside 0..cmd_slots-1 (when delay is NULL), a tap outside 0..hist_slots-1, num_taps outside 1..4, num_layers
+ * outside 1..4, a width outside 1..64, widths[0] != 2 num_taps, a last width != 1, an unknown mode or activation,
+ * gain_env_stride not 0 or num_dof, saturation without velocity_limit or the other way round, network mode without weights or
+ * histories, a weights_count other than the layout's, a null required tensor.  Additive: no new SHF_ABI_VERSION. */
+#define SHF_ACTUATOR_PD 0
+#define SHF_ACTUATOR_NET 1
+#define SHF_ACTUATOR_SOFTSIGN 0         /* x / (1 + |x|) */
+#define SHF_ACTUATOR_RELU 1
+#define SHF_ACTUATOR_TANH 2
+#define SHF_ACTUATOR_ELU 3              /* x > 0 ? x : expm1(x) */
+#define SHF_ACTUATOR_MAX_SLOTS 8
+#define SHF_ACTUATOR_MAX_TAPS 4
+#define SHF_ACTUATOR_MAX_LAYERS 4
+#define SHF_ACTUATOR_MAX_WIDTH 64
+typedef struct ShfActuatorNet {
+  int32_t activation;                              /* SHF_ACTUATOR_SOFTSIGN .. SHF_ACTUATOR_ELU */
+  int32_t num_layers;                              /* linear layers, 1..SHF_ACTUATOR_MAX_LAYERS */
+  int32_t widths[SHF_ACTUATOR_MAX_LAYERS + 1];     /* unpadded: inputs, hidden widths, 1 */
+  int32_t num_taps;
+  int32_t taps[SHF_ACTUATOR_MAX_TAPS];             /* history lags, each in 0..hist_slots-1 */
+  float err_scale, vel_scale, out_scale;
+} ShfActuatorNet;
+int shf_actuator_step(const float* target, const float* dof_state, int32_t dof_elem_stride, const float* kp_or_null,
+                      const float* kd_or_null, int32_t gain_env_stride, const int32_t* delay_or_null, int32_t delay_scalar,
+                      const float* strength_or_null, const float* saturation_or_null, const float* velocity_limit_or_null,
+                      const float* effort_limit_or_null, const uint8_t* reset_or_null, int32_t mode,
+                      const ShfActuatorNet* net_or_null, const float* weights_or_null, int64_t weights_count, float* cmd_hist,
+                      int32_t cmd_slots, float* err_hist_or_null, float* vel_hist_or_null, int32_t hist_slots, int32_t n,
+                      int32_t num_dof, float* applied_target_out_or_null, float* efforts_out, void* stream);
 /* ShifuVecEnv.compute_reward's accumulation (env.py:180-185): rew = terms[0] + terms[1] + ... in that order,
  * sums[k] += terms[k]; HOST arrays of num_keys <= 16 device pointers to (num_envs) fp32 tensors. */
 int shf_reward_accumulate(const float* const* terms, float* const* sums, int32_t num_keys, int64_t num_envs, float* rew,

@@ -127,6 +127,17 @@ class ShfGaitParams(C.Structure):      # shf_gait_plan's scalars, passed by valu
                 ("max_step", f32), ("leash", f32), ("contact_threshold", f32)]
 
 
+# shf_actuator_step (csrc/shf_actuator.hip): modes, activations, limits and the host-side description of the network
+ACTUATOR_PD, ACTUATOR_NET = 0, 1
+ACTUATOR_ACTIVATIONS = {"softsign": 0, "relu": 1, "tanh": 2, "elu": 3}
+ACTUATOR_MAX_SLOTS, ACTUATOR_MAX_TAPS, ACTUATOR_MAX_LAYERS, ACTUATOR_MAX_WIDTH = 8, 4, 4, 64
+
+
+class ShfActuatorNet(C.Structure):
+    _fields_ = [("activation", i32), ("num_layers", i32), ("widths", i32 * (ACTUATOR_MAX_LAYERS + 1)), ("num_taps", i32),
+                ("taps", i32 * ACTUATOR_MAX_TAPS), ("err_scale", f32), ("vel_scale", f32), ("out_scale", f32)]
+
+
 MPC_MAX_HORIZON = 10                   # SHF_MPC_MAX_HORIZON: steps of shf_mpc_horizon / shf_foot_force_mpc (csrc/shf_mpc.hip)
 
 

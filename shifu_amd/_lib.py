@@ -117,6 +117,11 @@ _SIGS = {
                             C.c_float, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp], i32),
     # forces, stance, j_feet, j_env_stride, j_foot_stride, bias, effort_limit, n, num_feet, num_dof, efforts_out, stream
     "shf_foot_force_efforts": ([vp, vp, vp, i64, i64, vp, vp, i32, i32, i32, vp, vp], i32),
+    # actuator models (csrc/shf_actuator.hip).  target, dof_state, dof_elem_stride, kp, kd, gain_env_stride, delay, delay_scalar,
+    # strength, saturation, velocity_limit, effort_limit, reset, mode, net (host struct), weights, weights_count, cmd_hist,
+    # cmd_slots, err_hist, vel_hist, hist_slots, n, num_dof, applied_target_out, efforts_out, stream
+    "shf_actuator_step": ([vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, C.POINTER(_abi.ShfActuatorNet), vp, i64, vp,
+                           i32, vp, vp, i32, i32, i32, vp, vp, vp], i32),
     "shf_reward_accumulate": ([C.POINTER(vp), C.POINTER(vp), i32, i64, vp, vp], i32),
     "shf_gae": ([vp, vp, vp, vp, i32, i64, C.c_float, C.c_float, vp, vp], i32),
     "shf_ppo_loss_workspace": ([i64, i32, C.POINTER(i64)], i32),

@@ -353,6 +353,50 @@ def leg_effort_mix(stance_efforts, swing_efforts, stance, chain_mask, effort_lim
     return out
 
 
+# -- actuator models: delay, PD or actuator net, strength, DC-motor clip in one launch (csrc/shf_actuator.hip) --------------------
+def actuator_step(target, dof_state, cmd_hist, kp=None, kd=None, delay=0, strength=None, saturation=None, velocity_limit=None,
+                  effort_limit=None, reset=None, net=None, err_hist=None, vel_hist=None, applied_out=None, efforts_out=None):
+    """One simulation sub-step of the actuator model in one launch (shf_actuator_step): efforts (n, nd).  target (n, nd)
+    contiguous; dof_state (n, nd, >= 2) as for osc (the dof-state tensor itself, read in place); cmd_hist (n, L, nd) and, with a
+    net, err_hist / vel_hist (n, H, nd): the caller's state, contiguous, updated in place (slot 0 = this call).  kp / kd (nd)
+    or (n, nd) (PD mode: net None); delay an int in 0..L-1 or a (n) int32 tensor (clamped to 0..L-1); strength (n, nd);
+    saturation / velocity_limit / effort_limit (nd); reset (n) uint8 / bool; net: a units.actuators.ActuatorNet on the device
+    (its padded weight buffer and host-side description).  applied_out / efforts_out (n, nd) contiguous: written when given
+    (efforts_out None: a new tensor).  utils.torch_utils.actuator_step is the same algorithm as torch expressions."""
+    from . import _abi
+    n, nd = target.shape
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in (target, dof_state, cmd_hist)), "float32 CUDA tensors expected"
+    assert target.is_contiguous() and cmd_hist.is_contiguous() and cmd_hist.dim() == 3 and cmd_hist.shape[0] == n and cmd_hist.shape[2] == nd
+    assert dof_state.shape[:2] == (n, nd) and dof_state.shape[2] >= 2 and dof_state.stride(2) == 1
+    assert dof_state.stride(1) >= 2 and dof_state.stride(0) == nd * dof_state.stride(1)
+    L = cmd_hist.shape[1]
+
+    def o(t, shape, dtype=torch.float32):
+        if t is None:
+            return None
+        assert tuple(t.shape) == shape and t.dtype == dtype and t.is_cuda and t.is_contiguous(), (tuple(t.shape), shape, t.dtype)
+        return _vp(t.data_ptr())
+
+    stride = 0
+    if net is None:
+        assert kp is not None and kd is not None and kp.shape == kd.shape and tuple(kp.shape) in ((nd,), (n, nd)), "kp / kd: (nd) or (n, nd)"
+        stride = nd if kp.dim() == 2 else 0
+    per_env = torch.is_tensor(delay)
+    rs = None if reset is None else reset.contiguous().view(torch.uint8)
+    H = 1 if err_hist is None else err_hist.shape[1]
+    out = torch.empty(n, nd, device=target.device, dtype=torch.float32) if efforts_out is None else efforts_out
+    with torch.cuda.device(target.device):
+        check(lib().shf_actuator_step(
+            _f32c(target), _vp(dof_state.data_ptr()), dof_state.stride(1), None if net is not None else o(kp, tuple(kp.shape)),
+            None if net is not None else o(kd, tuple(kd.shape)), stride, o(delay, (n,), torch.int32) if per_env else None,
+            0 if per_env else int(delay), o(strength, (n, nd)), o(saturation, (nd,)), o(velocity_limit, (nd,)), o(effort_limit, (nd,)),
+            o(rs, (n,), torch.uint8), _abi.ACTUATOR_PD if net is None else _abi.ACTUATOR_NET,
+            None if net is None else C.byref(net.struct), None if net is None else _f32c(net.packed),
+            0 if net is None else net.packed.numel(), _f32c(cmd_hist), L, o(err_hist, (n, H, nd)), o(vel_hist, (n, H, nd)), H, n, nd,
+            o(applied_out, (n, nd)), o(out, (n, nd)), _stream(target.device)))
+    return out
+
+
 # -- the horizon MPC: tables over the gait schedule -> condensed QP -> efforts (csrc/shf_mpc.hip) ---------------------------------
 # The defaults (DESIGN.md 8h "Horizon MPC" says where each comes from): horizon steps, sweeps, force weight, ticks between two
 # solves, and the weights of (roll, pitch, yaw, x, y, z, omega, v)

@@ -16,9 +16,41 @@ class Robot(Actor):
     def reset_idx(self, env_ids):
         self._reset_dof_state(env_ids)
         self._reset_root_state(env_ids)
+        if getattr(self, "actuator", None) is not None:
+            self.actuator.reset(env_ids)
 
     def step(self, actions):
         self._internal_motor_step(actions)
+
+    # -- actuator models (not in the reference; units/actuators.py, csrc/shf_actuator.hip) ------------------------------------
+    def set_actuator(self, actuator):
+        """Puts an Actuator (units.actuators: PD with delay, DC motor, actuator net) between apply_actuator_targets' joint angles
+        and the joint efforts; None takes it away.  The asset must be in DOF_MODE_EFFORT.  Call it once the buffers exist
+        (after create_envs); the actuator is bound to this robot's envs, dofs and device."""
+        if actuator is None:
+            self.actuator = None
+            return
+        if self.asset_options.default_dof_drive_mode != gymapi.DOF_MODE_EFFORT:
+            raise RuntimeError("set_actuator: the asset's default_dof_drive_mode must be DOF_MODE_EFFORT")
+        actuator.bind(self.env.num_envs, self.num_dof, self.device)
+        self.actuator = actuator
+
+    def apply_actuator_targets(self, dof_targets):
+        """decimation x {actuator.efforts (one launch), set the efforts, simulate, refresh the dof state}: apply_dof_targets
+        through the robot's actuator model.  dof_targets (num_envs, num_dof): the desired joint angles."""
+        act = getattr(self, "actuator", None)
+        if act is None:
+            raise RuntimeError("apply_actuator_targets: no actuator (set_actuator first)")
+        n = self.env.num_envs
+        ds = self.env.dof_state.view(n, self.num_dof, 2)
+        for _ in range(int(self.env.decimation)):
+            efforts = act.efforts(dof_targets, ds)
+            self.gym.set_dof_actuation_force_tensor(self.sim, gymtorch.unwrap_tensor(efforts))
+            self.gym.simulate(self.sim)
+            if self.device == 'cpu':
+                self.gym.fetch_results(self.sim, True)
+            self.gym.refresh_dof_state_tensor(self.sim)
+        return efforts
 
     def _init_props(self):
         super()._init_props()

@@ -300,6 +300,82 @@ def leg_effort_mix(stance_efforts, swing_efforts, stance, chain_mask, effort_lim
     return _effort_clamp(tau, effort_limit)
 
 
+# -- actuator models (csrc/shf_actuator.hip, whose header states the algorithm step by step; tests/actuator_ref.py holds the NumPy twin)
+def _actuator_shift(hist, reset, fill, value):
+    """Steps 1 and 2 on a history (n, S, nd), in place: reset rows take `fill`, the slots move back by one, `value` enters."""
+    if reset is not None:
+        r = (reset.reshape(-1) != 0).view(-1, 1, 1)
+        hist.copy_(torch.where(r, fill.unsqueeze(1) if torch.is_tensor(fill) else torch.full_like(hist, fill), hist))
+    if hist.shape[1] > 1:
+        hist[:, 1:] = hist[:, :-1].clone()
+    hist[:, 0] = value
+
+
+def actuator_activation(h, name):
+    if name == "softsign":
+        return h / (1.0 + h.abs())
+    if name == "relu":
+        return torch.where(h > 0, h, torch.zeros_like(h))
+    if name == "tanh":
+        return torch.tanh(h)
+    if name == "elu":
+        return torch.nn.functional.elu(h)
+    raise ValueError(f"unknown activation {name!r}")
+
+
+def actuator_step(target, dof_state, cmd_hist, kp=None, kd=None, delay=0, strength=None, saturation=None, velocity_limit=None,
+                  effort_limit=None, reset=None, net=None, err_hist=None, vel_hist=None, applied_out=None, efforts_out=None):
+    """One sub-step of the actuator model: efforts (n, nd).  The algorithm of csrc/shf_actuator.hip's shf_actuator_step as
+    batched torch expressions in the same operation order (its CPU fallback, and the timing baseline on the GPU); a network's
+    layers go through torch.nn.functional.linear, which sums in an order of its own.  target (n, nd); dof_state (n, nd, >= 2):
+    position and velocity in the last axis; cmd_hist (n, L, nd) and, with a net, err_hist / vel_hist (n, H, nd): the caller's
+    state, updated in place; kp / kd (nd) or (n, nd); delay an int or a (n) integer tensor; strength (n, nd); saturation /
+    velocity_limit / effort_limit (nd); reset (n) uint8 / bool; net: a units.actuators.ActuatorNet on target's device.
+    applied_out / efforts_out (n, nd): written when given."""
+    n, nd = target.shape
+    L = cmd_hist.shape[1]
+    q, qd = dof_state[..., 0], dof_state[..., 1]
+    _actuator_shift(cmd_hist, reset, target, target)
+    if torch.is_tensor(delay):
+        D = delay.reshape(n).to(torch.int64).clamp(0, L - 1)
+        a = torch.gather(cmd_hist, 1, D.view(n, 1, 1).expand(n, 1, nd)).squeeze(1)
+    else:
+        assert 0 <= int(delay) < L, "delay outside 0..L-1"
+        a = cmd_hist[:, int(delay)].clone()
+    if applied_out is not None:
+        applied_out.copy_(a)
+    err = a - q
+    if net is None:
+        tau = (kp * err) - (kd * qd)
+    else:
+        _actuator_shift(err_hist, reset, 0.0, err)
+        _actuator_shift(vel_hist, reset, 0.0, qd)
+        taps = list(net.taps)
+        x = torch.cat([net.err_scale * err_hist[:, taps], net.vel_scale * vel_hist[:, taps]], 1)       # (n, 2T, nd)
+        h = x.transpose(1, 2).reshape(n * nd, 2 * len(taps))
+        layers = net.layers
+        for l, (W, b) in enumerate(layers):
+            h = torch.nn.functional.linear(h, W, b)
+            if l < len(layers) - 1:
+                h = actuator_activation(h, net.activation)
+        tau = (net.out_scale * h[:, 0]).reshape(n, nd)
+    if strength is not None:
+        tau = tau * strength
+    if saturation is not None and velocity_limit is not None:
+        cap = torch.full_like(saturation, float("inf")) if effort_limit is None else \
+            torch.where(effort_limit > 0, effort_limit, torch.full_like(effort_limit, float("inf")))
+        r = qd / velocity_limit
+        hi = torch.minimum(torch.clamp_min(saturation * (1.0 - r), 0.0), cap)
+        lo = torch.maximum(torch.clamp_max(saturation * (-1.0 - r), 0.0), -cap)
+        tau = torch.maximum(torch.minimum(tau, hi), lo)
+    else:
+        tau = _effort_clamp(tau, effort_limit)
+    if efforts_out is not None:
+        efforts_out.copy_(tau)
+        return efforts_out
+    return tau
+
+
 # -- the horizon MPC (csrc/shf_mpc.hip, whose header states the three algorithms step by step; tests/mpc_ref.py holds the NumPy twins)
 def mpc_horizon(state, stance, foot_pos, command, nominal, ticks, dt, touchdown_z, max_step, horizon, steps_per_tick):
     """The MPC's tables: (contact (n, H, F) uint8, xref (n, H + 1, 12), pos (n, H, F, 3)).  The algorithm of shf_mpc_horizon as

@@ -1119,6 +1119,51 @@ int shf_actuator_step(const float* target, const float* dof_state, int32_t dof_e
                       const ShfActuatorNet* net_or_null, const float* weights_or_null, int64_t weights_count, float* cmd_hist,
                       int32_t cmd_slots, float* err_hist_or_null, float* vel_hist_or_null, int32_t hist_slots, int32_t n,
                       int32_t num_dof, float* applied_target_out_or_null, float* efforts_out, void* stream);
+/* ---- proprioceptive sensors: IMUs, joint encoders and foot contact switches behind a per-env latency (csrc/shf_proprio.hip,
+ * whose header states the algorithm, the noise streams and every layout step by step).  One launch is one sensor read of all
+ * envs; the work item is one (env, unit) pair -- a unit is one IMU, one dof or one foot -- and reads no other pair's state.
+ * Inputs, read in place: body_state (n, num_bodies, 13), dof_state (n, num_dof, 2), contact (n, num_bodies, 3), each with its
+ * element strides between envs and between rows (a row is contiguous; strided views are read as they are); reset (n) uint8
+ * or NULL; global_ids (n) int64 or NULL: the ids that key the noise (NULL: env_id_offset + e); delay (n, 3) int32: the
+ * latency in reads of the env's IMUs, encoders, feet, clamped to 0..max_delay; params (SHF_PROPRIO_NUM_PARAMS) float32 ON THE DEVICE: sigma_gyro, sigma_accel, walk_gyro sqrt(dt), walk_accel sqrt(dt), bias0_gyro,
+ * bias0_accel, sigma_q, sigma_qd, offset range, resolution r, 1 / r (0 when r = 0), f_on^2, f_off^2, then zeros.
+ * State, caller-owned, zero before the first read, updated in place: counter (n, U, 2) int32, U = num_imus + num_dof +
+ * num_feet; imu_state (n, num_imus, 9 + 6 slots); enc_state (n, num_dof, 2 + 2 slots); foot_state (n, num_feet, 5 + 6 slots).
+ * Outputs: out (n, D) float32, D = 6 num_imus + 2 num_dof + 6 num_feet: gyro | accel | dof_pos | dof_vel | contact |
+ * first_contact | air_time | contact_time | last_air_time | last_contact_time; switch_out (n, 2 num_feet) uint8 or NULL:
+ * contact | first_contact as bytes.  The config is a HOST struct: inv_dt is the float32 reciprocal of dt, formed by the caller.
+ * Refused with a message: more than 4 IMUs, more than 8 feet, slots outside 1..8, max_delay outside 0..slots-1 (a delay of
+ * slots or more), dt <= 0, a body index outside 0..num_bodies-1, n < 1, num_dof outside 1..SHF_MAX_DOFS, an unknown mode, a
+ * row stride shorter than the row, a null required tensor (body_state / imu_state with IMUs, contact / foot_state with feet,
+ * the others always).  Additive: no new SHF_ABI_VERSION, no struct layout changed. */
+#define SHF_PROPRIO_MAX_IMUS 4
+#define SHF_PROPRIO_MAX_FEET 8
+#define SHF_PROPRIO_MAX_SLOTS 8
+#define SHF_PROPRIO_NUM_PARAMS 16
+#define SHF_PROPRIO_CONTACT_NORM 0      /* s = |f|^2 */
+#define SHF_PROPRIO_CONTACT_Z 1         /* s = f_z |f_z| */
+#define SHF_PROPRIO_VEL_DIRECT 0        /* qd + noise */
+#define SHF_PROPRIO_VEL_DIFFERENCE 1    /* (q_meas - q_meas_prev) / dt */
+typedef struct ShfProprioConfig {
+  int64_t env_id_offset;                           /* global id of env 0: the noise is keyed by global ids */
+  uint32_t seed_lo, seed_hi;                       /* the Philox key */
+  int32_t num_imus;
+  int32_t imu_body[SHF_PROPRIO_MAX_IMUS];
+  float imu_pos[SHF_PROPRIO_MAX_IMUS][3];          /* the mounting in the body frame */
+  float imu_quat[SHF_PROPRIO_MAX_IMUS][4];         /* xyzw, unit */
+  int32_t num_feet;
+  int32_t foot_body[SHF_PROPRIO_MAX_FEET];
+  int32_t contact_mode, velocity_mode;
+  int32_t slots, max_delay;                        /* ring slots L in 1..8; the largest delay, below L */
+  float gravity[3];
+  float dt, inv_dt;                                /* the time between two reads and its float32 reciprocal */
+} ShfProprioConfig;
+int shf_proprioception_step(const float* body_state, int64_t body_env_stride, int64_t body_row_stride, const float* dof_state,
+                            int64_t dof_env_stride, int64_t dof_row_stride, const float* contact, int64_t contact_env_stride,
+                            int64_t contact_row_stride, const uint8_t* reset_or_null, const ShfProprioConfig* config,
+                            const float* params, const int32_t* delay, const int64_t* global_ids_or_null, int32_t* counter,
+                            float* imu_state, float* enc_state, float* foot_state, int32_t n, int32_t num_bodies, int32_t num_dof, float* out,
+                            uint8_t* switch_out_or_null, void* stream);
 /* ShifuVecEnv.compute_reward's accumulation (env.py:180-185): rew = terms[0] + terms[1] + ... in that order,
  * sums[k] += terms[k]; HOST arrays of num_keys <= 16 device pointers to (num_envs) fp32 tensors. */
 int shf_reward_accumulate(const float* const* terms, float* const* sums, int32_t num_keys, int64_t num_envs, float* rew,

@@ -138,6 +138,21 @@ class ShfActuatorNet(C.Structure):
                 ("taps", i32 * ACTUATOR_MAX_TAPS), ("err_scale", f32), ("vel_scale", f32), ("out_scale", f32)]
 
 
+# shf_proprioception_step (csrc/shf_proprio.hip): limits, modes, the device parameter vector's entries and the host-side config
+PROPRIO_MAX_IMUS, PROPRIO_MAX_FEET, PROPRIO_MAX_SLOTS, PROPRIO_NUM_PARAMS = 4, 8, 8, 16
+PROPRIO_CONTACT_MODES = {"norm": 0, "z": 1}
+PROPRIO_VELOCITY_MODES = {"direct": 0, "difference": 1}
+PROPRIO_PARAMS = ("gyro_noise", "accel_noise", "gyro_walk_sqrt_dt", "accel_walk_sqrt_dt", "gyro_bias", "accel_bias", "dof_pos_noise",
+                  "dof_vel_noise", "dof_offset", "resolution", "inv_resolution", "f_on_sq", "f_off_sq")
+
+
+class ShfProprioConfig(C.Structure):
+    _fields_ = [("env_id_offset", C.c_int64), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("num_imus", i32),
+                ("imu_body", i32 * PROPRIO_MAX_IMUS), ("imu_pos", (f32 * 3) * PROPRIO_MAX_IMUS), ("imu_quat", (f32 * 4) * PROPRIO_MAX_IMUS),
+                ("num_feet", i32), ("foot_body", i32 * PROPRIO_MAX_FEET), ("contact_mode", i32), ("velocity_mode", i32),
+                ("slots", i32), ("max_delay", i32), ("gravity", f32 * 3), ("dt", f32), ("inv_dt", f32)]
+
+
 MPC_MAX_HORIZON = 10                   # SHF_MPC_MAX_HORIZON: steps of shf_mpc_horizon / shf_foot_force_mpc (csrc/shf_mpc.hip)
 
 

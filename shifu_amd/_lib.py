@@ -122,6 +122,11 @@ _SIGS = {
     # cmd_slots, err_hist, vel_hist, hist_slots, n, num_dof, applied_target_out, efforts_out, stream
     "shf_actuator_step": ([vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, C.POINTER(_abi.ShfActuatorNet), vp, i64, vp,
                            i32, vp, vp, i32, i32, i32, vp, vp, vp], i32),
+    # proprioceptive sensors (csrc/shf_proprio.hip).  body_state, its env and row strides, dof_state, its strides, contact, its
+    # strides, reset, config (host struct), params, delay, global_ids, counter, imu_state, enc_state, foot_state, n, num_bodies, num_dof, out,
+    # switch_out, stream
+    "shf_proprioception_step": ([vp, i64, i64, vp, i64, i64, vp, i64, i64, vp, C.POINTER(_abi.ShfProprioConfig), vp, vp, vp, vp, vp, vp, vp,
+                                 i32, i32, i32, vp, vp, vp], i32),
     "shf_reward_accumulate": ([C.POINTER(vp), C.POINTER(vp), i32, i64, vp, vp], i32),
     "shf_gae": ([vp, vp, vp, vp, i32, i64, C.c_float, C.c_float, vp, vp], i32),
     "shf_ppo_loss_workspace": ([i64, i32, C.POINTER(i64)], i32),

@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "libshifu_amd.so")
 # (csrc/shf_kernel_list.h) so that they compile side by side -- as one unit the library took 4.5 minutes to build.
 KERNEL_UNITS = ["shf_k_sim.hip", "shf_k_sim_link.hip", "shf_k_sim_hard.hip", "shf_k_sim_hard_wide.hip", "shf_k_a1.hip", "shf_k_abb.hip",
                 "shf_k_abb_link.hip", "shf_k_abb_hard.hip", "shf_k_abb_ws.hip", "shf_k_abb_ws_hard.hip", "shf_k_sim_ext.hip", "shf_k_abb_ext.hip", "shf_k_hull_test.hip", "shf_k_cap_select_test.hip"]
-UNITY_SOURCES = ["shf_api.hip", "shf_a1_chain.hip", "shf_glue.hip", "shf_mlp.hip", "shf_k_hull_test.hip", "shf_k_cap_select_test.hip", "shf_render.hip", "shf_conv.hip", "shf_lstm.hip", "shf_gru.hip", "shf_dyn.hip", "shf_dyn_fb.hip", "shf_qp.hip", "shf_gait.hip", "shf_mpc.hip", "shf_actuator.hip"]      # with -DSHF_UNITY: shf_api.hip instantiates every kernel
+UNITY_SOURCES = ["shf_api.hip", "shf_a1_chain.hip", "shf_glue.hip", "shf_mlp.hip", "shf_k_hull_test.hip", "shf_k_cap_select_test.hip", "shf_render.hip", "shf_conv.hip", "shf_lstm.hip", "shf_gru.hip", "shf_dyn.hip", "shf_dyn_fb.hip", "shf_qp.hip", "shf_gait.hip", "shf_mpc.hip", "shf_actuator.hip", "shf_proprio.hip"]      # with -DSHF_UNITY: shf_api.hip instantiates every kernel
 SOURCES = UNITY_SOURCES + [u for u in KERNEL_UNITS if u not in UNITY_SOURCES]
 HEADERS = ["shf_device.h", "shf_boxes.h", "shf_task.h", "shf_chain.h", "shf_chain_hard.h", "shf_hard.h", "shf_link.h", "shf_arm.h", "shf_kernels.h",
            "shf_kernel_list.h", "shf_hull.h", "shf_dyn.h", "shf_rnn_cell.h", "shf_cone.h", "shf_quat.h", os.path.join("..", "..", "include", "shifu_amd.h")]
@@ -140,7 +140,11 @@ BUDGETS = [("_Z16k_a1_step_a1_g32", 256, 0),          # default: A1, two envs pe
            # vectors of 32 or 64 floats each, eight accumulators, the weights in flight from LDS) plus a margin of 10; nothing on
            # the stack (the columns are named fields and a layer's output vector shifts in place so that it stays that way)
            ("_ZN12_GLOBAL__N_113k_actuator_pd", 30, 0), ("_ZN12_GLOBAL__N_114k_actuator_netILi32E", 116, 0),
-           ("_ZN12_GLOBAL__N_114k_actuator_netILi64E", 212, 0)]
+           ("_ZN12_GLOBAL__N_114k_actuator_netILi64E", 212, 0),
+           # the proprioceptive sensors (csrc/shf_proprio.hip: k_proprioception): 94 registers in the first clean build
+           # (the IMU branch: two rotation matrices, the measurement and its ring slot, a Philox block in flight) plus a margin
+           # of 10; nothing on the stack (the ring slot is loaded unconditionally so that the measurement stays in registers)
+           ("_ZN12_GLOBAL__N_116k_proprioception", 104, 0)]
 
 
 def parse_resources(remarks: str) -> dict:

@@ -54,3 +54,38 @@ class RayCasterSensorConfig(BaseSensorConfig):
     min_range = 0.0
     max_range = 10.0
     ignore_robot = True
+
+
+class ProprioceptionSensorConfig(BaseSensorConfig):
+    """units.ProprioceptionSensor (no counterpart in the reference): IMUs, joint encoders and foot contact switches with the
+    imperfections a robot's own sensors have.  imu: up to 4 dicts(body=<rigid body name or index>, position=(x, y, z),
+    quat=(x, y, z, w)), the mounting in the body frame; feet: "auto" (the robot's end_effector_names), or up to 8 body names /
+    indices, or [].  A foot switch closes above f_on newtons and opens below f_off (None: f_on) of |f| (contact_mode "norm") or
+    of f_z ("z").  velocity: "direct" (the joint velocity plus noise) or "difference" (of two measured positions).  The noise
+    terms are standard deviations per read (gyro rad/s, accel m/s^2, dof_pos rad, dof_vel rad/s), *_walk the bias random
+    walks' densities (per sqrt(s)), *_bias / dof_offset the half-widths of the uniform draws at a reset, resolution the
+    encoder's step (0: none).  delay: reads of latency, one int or (IMUs, encoders, feet), at most max_delay <= 7; randomize()
+    draws them per env.  dt: seconds between two reads (None: the env's dt); gravity None: the sim's."""
+    name = "DummyProprioceptionSensor"
+    imu = []
+    feet = "auto"
+    contact_mode = "norm"
+    f_on = 1.0
+    f_off = None
+    velocity = "direct"
+    gyro_noise = 0.0
+    accel_noise = 0.0
+    gyro_walk = 0.0
+    accel_walk = 0.0
+    gyro_bias = 0.0
+    accel_bias = 0.0
+    dof_pos_noise = 0.0
+    dof_vel_noise = 0.0
+    dof_offset = 0.0
+    resolution = 0.0
+    delay = 0
+    max_delay = 0
+    dt = None
+    gravity = None
+    seed = 0
+    backend = "auto"

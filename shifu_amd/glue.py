@@ -397,6 +397,52 @@ def actuator_step(target, dof_state, cmd_hist, kp=None, kd=None, delay=0, streng
     return out
 
 
+# -- proprioceptive sensors: IMUs, encoders and foot contact switches in one launch (csrc/shf_proprio.hip) -------------------------
+def proprioception_step(body_state, dof_state, contact, config, params, delay, state, out, switches=None, reset=None, global_ids=None):
+    """One sensor read of every env in one launch (shf_proprioception_step): fills and returns out (n, D).  body_state
+    (n, nb, 13), dof_state (n, nd, >= 2), contact (n, nb, 3): float32 CUDA tensors or strided views of them with a contiguous
+    last axis, read in place (body_state / contact may be None without IMUs / feet); config: the _abi.ShfProprioConfig
+    (proprio.make_config); params (PROPRIO_NUM_PARAMS) float32 on the device (proprio.make_params); delay (n, 3) int32;
+    state: proprio.make_state's tensors on the device, updated in place; out (n, D) float32 and switches (n, 2 F) uint8 or None,
+    contiguous; reset (n) uint8 / bool or None (read, not cleared); global_ids (n) int64 or None: the ids that key the noise
+    (None: config.env_id_offset + e).  utils.torch_utils.proprioception_step is the same algorithm as torch expressions."""
+    from . import _abi, proprio
+    n, nd = dof_state.shape[:2]
+    I, F, L = config.num_imus, config.num_feet, config.slots
+
+    def strided(t, width, name):
+        if t is None:
+            return None, 0, 0, 0
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.shape[0] == n and t.shape[2] >= width, f"{name}: (n, rows, >= {width}) float32 CUDA"
+        assert t.stride(2) == 1 or t.shape[2] == 1, f"{name}: the last axis must be contiguous"
+        return _vp(t.data_ptr()), t.stride(0), t.stride(1), t.shape[1]
+
+    def own(t, shape, dtype, name):
+        if t is None:
+            return None
+        assert tuple(t.shape) == tuple(shape) and t.dtype == dtype and t.is_cuda and t.is_contiguous(), (name, tuple(t.shape), tuple(shape), t.dtype)
+        return _vp(t.data_ptr())
+
+    bp, be, br, nb = strided(body_state, 13, "body_state")
+    dp, de, dr, _ = strided(dof_state, 2, "dof_state")
+    cp, ce, cr, nbc = strided(contact, 3, "contact")
+    assert body_state is None or contact is None or nb == nbc, "body_state and contact disagree about the bodies"
+    shapes = proprio.state_shapes(n, I, nd, F, L)
+    rs = None if reset is None else reset.contiguous().view(torch.uint8)
+    with torch.cuda.device(dof_state.device):
+        check(lib().shf_proprioception_step(
+            bp, be, br, dp, de, dr, cp, ce, cr, own(rs, (n,), torch.uint8, "reset"), C.byref(config),
+            own(params, (_abi.PROPRIO_NUM_PARAMS,), torch.float32, "params"), own(delay, (n, 3), torch.int32, "delay"),
+            own(global_ids, (n,), torch.int64, "global_ids"),
+            own(state["counter"], shapes["counter"], torch.int32, "counter"),
+            own(state["imu"], shapes["imu"], torch.float32, "imu") if I else None,
+            own(state["enc"], shapes["enc"], torch.float32, "enc"),
+            own(state["foot"], shapes["foot"], torch.float32, "foot") if F else None,
+            n, max(nb, nbc, 1), nd, own(out, (n, proprio.out_width(I, nd, F)), torch.float32, "out"),
+            own(switches, (n, 2 * F), torch.uint8, "switches") if F else None, _stream(dof_state.device)))
+    return out
+
+
 # -- the horizon MPC: tables over the gait schedule -> condensed QP -> efforts (csrc/shf_mpc.hip) ---------------------------------
 # The defaults (DESIGN.md 8h "Horizon MPC" says where each comes from): horizon steps, sweeps, force weight, ticks between two
 # solves, and the weights of (roll, pitch, yaw, x, y, z, omega, v)

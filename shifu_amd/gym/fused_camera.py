@@ -9,7 +9,11 @@ Optical flow (add_camera(..., flow=True)): the camera keeps the bo
 (render.FlowHistory) and renders with shf_render_cameras_flow.  The fused step kernels reset envs inside the launch, so
 whether an env's previous frame is usable is worked out on the device: an env is valid iff its reset counter
 (A1_RESET_COUNT / ABB_RESET_COUNT) still equals the value snapshotted at the previous flow render; env.reset()
-invalidates every env."""
+invalidates every env.
+
+Proprioceptive sensors (add_proprioception; DESIGN.md 8e "Proprioception") stand beside them: IMUs, joint encoders and foot
+contact switches on the body, dof and contact tensors the step writes, one launch per read, with the same reset-counter rule for
+the envs the fused step teleported since the last read."""
 from __future__ import annotations
 
 from typing import Optional, Sequence
@@ -170,8 +174,53 @@ class FusedRayCaster:
         return o
 
 
+class FusedProprioception:
+    """Proprioceptive sensors in every env (shifu_amd/proprio.py; shf_proprioception_step): IMUs, joint encoders and foot
+    contact switches on the tensors the fused step writes, one launch per read().  The fused step resets envs inside the
+    launch, so which envs were teleported since the last read is worked out on the device, the way flow cameras do it: an
+    env's reset counter no longer equals the value snapshotted at the previous read.  reset(env_ids) raises flags by hand;
+    env.reset() raises them all."""
+
+    def __init__(self, env, core, reset_count):
+        n, nd = env.num_envs, core.num_dof
+        self.env, self.core = env, core
+        self.flat = core.flat
+        self._body = env.body_state.view(n, -1, 13)
+        self._dof = env.dof_state.view(n, -1, 2)[:, :nd]
+        self._contact = env.contact_state.view(n, -1, 3)
+        self._count = reset_count
+        self._count_seen = None if reset_count is None else reset_count.clone()
+        self._moved = torch.zeros(n, dtype=torch.bool, device=env.device)
+
+    def read(self) -> dict:
+        """One launch for all envs on the states of the last step / reset, into this sensor's own tensors; no host sync.
+        {"gyro", "accel": (N, I, 3); "dof_pos", "dof_vel": (N, nd); "contact", "first_contact": (N, F) uint8; "air_time",
+        "contact_time", "last_air_time", "last_contact_time": (N, F)}: views of `flat` (N, D) and of the switch bytes."""
+        extra = None
+        if self._count is not None:
+            torch.ne(self._count, self._count_seen, out=self._moved)
+            self._count_seen.copy_(self._count)
+            extra = self._moved.view(torch.uint8)
+        return self.core.read(self._body, self._dof, self._contact, extra_reset=extra)
+
+    def reset(self, env_ids=None):
+        self.core.reset(env_ids)
+
+    def randomize(self, env_ids=None, delay=None, generator=None):
+        self.core.randomize(env_ids, delay=delay, generator=generator)
+
+    def set_noise(self, **noise):
+        self.core.set_noise(**noise)
+
+    @property
+    def last_reset(self):
+        """(N) uint8: the reset flags the last read used."""
+        return self.core.last_reset
+
+
 class FusedCameraHost:
-    """What FusedA1Env and FusedAbbEnv share: the per-env segmentation / color tables, add_camera and add_ray_caster."""
+    """What FusedA1Env and FusedAbbEnv share: the per-env segmentation / color tables, add_camera, add_ray_caster and
+    add_proprioception."""
 
     def _init_cameras(self, box_dims: Sequence = (), reset_count=None):
         """box_dims: full extents of the env's box actors, in body-state row order after the articulation's bodies;
@@ -184,6 +233,7 @@ class FusedCameraHost:
         self.cam_color = torch.tensor(DEFAULT_BODY_COLOR, dtype=torch.float32, device=self.device).repeat(self.num_envs, B, 1)
         self.cameras = []
         self.ray_casters = []
+        self.proprioception = []
         self.viewers = []
         self._renderer = None
         self._cam_reset_count = reset_count
@@ -191,6 +241,8 @@ class FusedCameraHost:
     def _invalidate_camera_flow(self, env_ids=None):
         for cam in self.cameras:
             cam.invalidate_flow(env_ids)
+        for s in self.proprioception:             # the same moment for the proprioceptive sensors: a reset is a teleport
+            s.reset(env_ids)
 
     def add_camera(self, width: int, height: int, horizontal_fov: float, near_plane: float, far_plane: float,
                    position=(0.0, 0.0, 0.0), target=None, quat=None, attach_body: Optional[int] = None,
@@ -235,6 +287,31 @@ class FusedCameraHost:
                             shape_mask_for(r.scene, ignore_bodies), tuple(outputs))
         self.ray_casters.append(rc)
         return rc
+
+    def add_proprioception(self, imu=(), feet="auto", contact_mode="norm", velocity="direct", max_delay=0, delay=0, dt=None,
+                           seed=0, backend="auto", **noise) -> FusedProprioception:
+        """Proprioceptive sensors in every env (DESIGN.md 8e "Proprioception"): s = env.add_proprioception(imu=[dict(body=0,
+        position=..., quat=...)], feet="auto", gyro_noise=..., ...); s.read() after a step.  imu: up to 4 mountings on rows
+        of the env's body states; feet: "auto" (the articulation's bodies named *_foot), or up to 8 body rows, or ();
+        contact_mode "norm" | "z" with f_on / f_off newtons; velocity "direct" | "difference"; max_delay <= 7 reads of latency
+        and `delay` (an int, three ints for IMUs / encoders / feet, or an (N, 3) tensor; randomize() draws them per env); dt:
+        seconds between two reads (default: the env's dt, one read per step); seed: the noise key (the draws are keyed by global
+        env ids, so a sharded run draws what the unsharded one draws); the noise terms are shifu_amd.proprio.NOISE_NAMES.
+        Derived data, like the cameras: the simulation and state_dict are unchanged."""
+        from ..proprio import Proprioception
+        names = list(self.cm.body_names)
+        if isinstance(feet, str):
+            if feet != "auto":
+                raise ValueError(f"add_proprioception: feet must be 'auto' or body rows, got {feet!r}")
+            feet = [b for b, name in enumerate(names) if name.endswith("_foot")]
+        B = self.cam_seg.shape[1]
+        core = Proprioception(self.num_envs, B, int(self.cm.blob.nd), self.device, imus=list(imu), feet=list(feet), contact_mode=contact_mode,
+                              velocity=velocity, max_delay=max_delay, delay=delay, gravity=tuple(float(v) for v in self.sim_params.gravity),
+                              dt=float(self.dt) if dt is None else float(dt), seed=seed, env_id_offset=int(getattr(self, "env_id_offset", 0)),
+                              backend=backend, **noise)
+        s = FusedProprioception(self, core, self._cam_reset_count)
+        self.proprioception.append(s)
+        return s
 
     def _ensure_renderer(self):
         from ..render import Renderer, build_scene

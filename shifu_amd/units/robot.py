@@ -18,6 +18,8 @@ class Robot(Actor):
         self._reset_root_state(env_ids)
         if getattr(self, "actuator", None) is not None:
             self.actuator.reset(env_ids)
+        for sensor in getattr(self, "proprioception_sensors", ()):       # units.ProprioceptionSensor: a reset is a teleport
+            sensor.reset(env_ids)
 
     def step(self, actions):
         self._internal_motor_step(actions)

@@ -217,3 +217,81 @@ class RayCasterSensor(Sensor):
 
     def refresh(self):
         self.gym.cast_ray_caster_group(self.sim, self._handle)
+
+
+class ProprioceptionSensor(Sensor):
+    """What the robot measures about itself (configs.ProprioceptionSensorConfig; shifu_amd/proprio.py; DESIGN.md 8e
+    "Proprioception"): IMUs with bias, noise and a bias walk, joint encoders with offset, noise and quantisation, foot contact
+    switches with hysteresis and the air / contact times, each behind a per-env latency.  read() is one launch on the GPU
+    (csrc/shf_proprio.hip) and the same algorithm in torch on the CPU or with cfg.backend = "torch"; it returns a dict of
+    views of `flat` (N, D) -- gyro / accel (N, I, 3), dof_pos / dof_vel (N, nd), contact / first_contact (N, F) uint8, air_time
+    / contact_time / last_air_time / last_contact_time (N, F) -- on the state tensors as the last refresh left them.
+    refresh() is read().  Robot.reset_idx raises the reset flags of the envs it resets; reset(env_ids) does it by hand."""
+
+    def __init__(self, cfg):
+        super().__init__(cfg)
+        self.core = None
+
+    def _init_props(self):
+        pass
+
+    def load_to(self, env_id, env_handle, seg_id):
+        pass                                                 # nothing to create per env: the sensor reads the state tensors
+
+    def reset_idx(self, env_ids):
+        self.reset(env_ids)
+
+    def _body(self, b, bodies):
+        if isinstance(b, str):
+            if b not in bodies:
+                raise ValueError(f"ProprioceptionSensor: the robot has no rigid body {b!r} (it has {sorted(bodies)})")
+            return int(bodies[b])
+        return int(b)
+
+    def init_buffers(self):
+        from shifu_amd.proprio import NOISE_NAMES, Proprioception
+        cfg, env, robot = self.cfg, self.env, self.env.robot
+        bodies = robot.rigid_body_dict
+        n = env.num_envs
+        imus = [dict(m, body=self._body(m["body"], bodies)) for m in cfg.imu]
+        feet = cfg.feet
+        if isinstance(feet, str):
+            if feet != "auto":
+                raise ValueError(f"ProprioceptionSensor: feet must be 'auto' or a list of bodies, got {feet!r}")
+            feet = list(getattr(robot.cfg, "end_effector_names", ()) or ())
+        feet = [self._body(b, bodies) for b in feet]
+        self._body_view = env.body_state.view(n, -1, 13)
+        self._contact_view = env.contact_state.view(n, -1, 3)
+        self._dof_view = env.dof_state.view(n, -1, 2)[:, :robot.num_dof]
+        gravity = cfg.gravity if cfg.gravity is not None else _sim_gravity(self.sim)
+        dt = float(cfg.dt) if cfg.dt is not None else float(env.dt)
+        noise = {k: getattr(cfg, k) for k in NOISE_NAMES if getattr(cfg, k, None) is not None}
+        self.core = Proprioception(n, self._body_view.shape[1], robot.num_dof, self.device, imus=imus, feet=feet,
+                                   contact_mode=cfg.contact_mode, velocity=cfg.velocity, max_delay=cfg.max_delay, delay=cfg.delay,
+                                   gravity=gravity, dt=dt, seed=cfg.seed, backend=cfg.backend, **noise)
+        self.flat = self.core.flat
+        if not hasattr(robot, "proprioception_sensors"):
+            robot.proprioception_sensors = []
+        robot.proprioception_sensors.append(self)
+
+    def read(self):
+        return self.core.read(self._body_view, self._dof_view, self._contact_view)
+
+    def refresh(self):
+        self.read()
+
+    def reset(self, env_ids=None):
+        if self.core is not None:
+            self.core.reset(env_ids)
+
+    def randomize(self, env_ids=None, delay=None, generator=None):
+        self.core.randomize(env_ids, delay=delay, generator=generator)
+
+
+def _sim_gravity(sim):
+    """The simulation's gravity vector as three floats."""
+    for holder in (getattr(sim, "params", None), getattr(sim, "sim_params", None), getattr(getattr(sim, "backend", None), "params", None)):
+        g = getattr(holder, "gravity", None)
+        if g is not None:
+            return (float(g.x), float(g.y), float(g.z)) if hasattr(g, "x") else tuple(float(v) for v in g)
+    raise RuntimeError("ProprioceptionSensor: the sim's gravity is not known here; set cfg.gravity")

@@ -376,6 +376,158 @@ def actuator_step(target, dof_state, cmd_hist, kp=None, kd=None, delay=0, streng
     return tau
 
 
+# -- proprioceptive sensors (csrc/shf_proprio.hip, whose header states the algorithm step by step; tests/proprio_ref.py holds the NumPy twin)
+def _philox_mulhilo(a: int, b):
+    """(high, low) 32-bit words of a * b for a 32-bit constant a and int64 tensors b of 32-bit words, without leaving int64:
+    b = bh 2^16 + bl, so that both partial products stay below 2^48."""
+    pl, ph = a * (b & 0xFFFF), a * (b >> 16)
+    return ((ph + (pl >> 16)) >> 16) & 0xFFFFFFFF, (pl + ((ph & 0xFFFF) << 16)) & 0xFFFFFFFF
+
+
+def philox4x32(c0, c1, c2, c3, k0: int, k1: int):
+    """Philox4x32-10 (csrc/shf_task.h: philox4x32) on int64 tensors of 32-bit words."""
+    c0, c1, c2, c3 = torch.broadcast_tensors(c0, c1, c2, c3)
+    for _ in range(10):
+        h0, l0 = _philox_mulhilo(0xD2511F53, c0)
+        h1, l1 = _philox_mulhilo(0xCD9E8D57, c2)
+        c0, c1, c2, c3 = h1 ^ c1 ^ k0, l1, h0 ^ c3 ^ k1, l0
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
+
+def _proprio_latency(ring, h, D, rs, m):
+    """ring (n, L, C), a view of the state: the delayed (n, C) output, and the ring updated in place."""
+    n, L, C = ring.shape
+    slot = h - D
+    slot = torch.where(slot < 0, slot + L, slot)
+    old = torch.gather(ring, 1, slot.view(n, 1, 1).expand(n, 1, C)).squeeze(1)
+    out = torch.where((rs | (D == 0)).view(n, 1), m, old)
+    here = rs.view(n, 1) | (torch.arange(L, device=ring.device).view(1, L) == h.view(n, 1))       # (n, L): the slots that take m
+    ring.copy_(torch.where(here.unsqueeze(2), m.unsqueeze(1), ring))
+    return out
+
+
+def proprioception_step(body_state, dof_state, contact, config, params, delay, state, out, switches=None, reset=None, global_ids=None):
+    """One sensor read of every env: fills and returns out (n, D).  The algorithm of csrc/shf_proprio.hip's
+    shf_proprioception_step as batched torch expressions in the same operation order (its CPU path, and the timing baseline on
+    the GPU); the arguments are glue.proprioception_step's, on any device."""
+    f32 = torch.float32
+    n, nd = dof_state.shape[:2]
+    dev = dof_state.device
+    I, F, L = int(config.num_imus), int(config.num_feet), int(config.slots)
+    P = params.to(f32)
+    sg, sa, wg, wa, b0g, b0a, sq, sv, o_rng, res, inv_res, on2, off2 = (P[k] for k in range(13))
+    dt, inv_dt = torch.tensor(config.dt, dtype=f32, device=dev), torch.tensor(config.inv_dt, dtype=f32, device=dev)
+    cnt = state["counter"]
+    c = cnt[:, 0, 0].to(torch.int64) & 0xFFFFFFFF
+    h = cnt[:, 0, 1].to(torch.int64)
+    rs = c == 0
+    if reset is not None:
+        rs = rs | (reset.reshape(n) != 0)
+    Dl = delay.reshape(n, 3).to(torch.int64).clamp(0, int(config.max_delay))
+    gid = int(config.env_id_offset) + torch.arange(n, device=dev, dtype=torch.int64) if global_ids is None else global_ids.reshape(n).to(torch.int64)
+    lo, hi = gid & 0xFFFFFFFF, (gid >> 32) & 0xFFFFFFFF
+    k0, k1 = int(config.seed_lo), int(config.seed_hi)
+
+    def block(stream):
+        s = torch.as_tensor(stream, dtype=torch.int64, device=dev)
+        sh = (n,) + (1,) * s.dim()
+        w = philox4x32(lo.view(sh), c.view(sh), s, hi.view(sh), k0, k1)
+        return [(x >> 8).to(f32) * 5.9604644775390625e-08 for x in w]
+
+    def gauss(stream):
+        u = block(stream)
+        return (((u[0] + u[1]) + (u[2] + u[3])) - 2.0) * 1.7320508
+
+    usym = lambda u, b: ((b - (-b)) * u) + (-b)
+
+    def matrix(q):
+        x, y, z, w = q
+        return [[1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)],
+                [2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x)],
+                [2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)]]
+
+    for i in range(I):
+        S = 0x50000000 + 16 * i
+        b = int(config.imu_body[i])
+        ps = [torch.tensor(float(v), dtype=f32, device=dev) for v in config.imu_pos[i]]
+        bx, by, bz, bw = [torch.tensor(float(v), dtype=f32, device=dev) for v in config.imu_quat[i]]
+        bs = body_state[:, b]
+        ax, ay, az, aw = (bs[:, 3 + k] for k in range(4))
+        wb = [bs[:, 10 + k] for k in range(3)]
+        q = (((aw * bx + ax * bw) + ay * bz) - az * by, ((aw * by - ax * bz) + ay * bw) + az * bx,
+             ((aw * bz + ax * by) - ay * bx) + az * bw, ((aw * bw - ax * bx) - ay * by) - az * bz)
+        R, Rb = matrix(q), matrix((ax, ay, az, aw))
+        arm = [(Rb[a][0] * ps[0] + Rb[a][1] * ps[1]) + Rb[a][2] * ps[2] for a in range(3)]
+        vs = [bs[:, 7] + (wb[1] * arm[2] - wb[2] * arm[1]), bs[:, 8] + (wb[2] * arm[0] - wb[0] * arm[2]),
+              bs[:, 9] + (wb[0] * arm[1] - wb[1] * arm[0])]
+        st = state["imu"][:, i]
+        ug, ua = block(S + 12), block(S + 13)
+        vp = [torch.where(rs, vs[a], st[:, a]) for a in range(3)]
+        bg = [torch.where(rs, usym(ug[a], b0g), st[:, 3 + a]) for a in range(3)]
+        ba = [torch.where(rs, usym(ua[a], b0a), st[:, 6 + a]) for a in range(3)]
+        accw = [((vs[a] - vp[a]) * inv_dt) - float(config.gravity[a]) for a in range(3)]
+        m = []
+        for a in range(3):
+            gw = (R[0][a] * wb[0] + R[1][a] * wb[1]) + R[2][a] * wb[2]
+            m.append((gw + bg[a]) + (sg * gauss(S + a)))
+        for a in range(3):
+            aw_ = (R[0][a] * accw[0] + R[1][a] * accw[1]) + R[2][a] * accw[2]
+            m.append((aw_ + ba[a]) + (sa * gauss(S + 3 + a)))
+        o = _proprio_latency(st[:, 9:].view(n, L, 6), h, Dl[:, 0], rs, torch.stack(m, 1))
+        for a in range(3):
+            st[:, 3 + a] = bg[a] + (wg * gauss(S + 6 + a))
+            st[:, 6 + a] = ba[a] + (wa * gauss(S + 9 + a))
+            st[:, a] = vs[a]
+        out[:, 3 * i:3 * i + 3] = o[:, :3]
+        out[:, 3 * I + 3 * i:3 * I + 3 * i + 3] = o[:, 3:]
+
+    S = 0x50001000 + 4 * torch.arange(nd, device=dev, dtype=torch.int64)
+    st = state["enc"]
+    q, qd = dof_state[:, :, 0], dof_state[:, :, 1]
+    off = torch.where(rs.view(n, 1), usym(block(S + 2)[0], o_rng), st[:, :, 0])
+    st[:, :, 0] = off
+    x = (q + off) + (sq * gauss(S))
+    x = torch.where(res > 0, res * torch.round(x * inv_res), x)
+    if int(config.velocity_mode) == 1:
+        v = (x - torch.where(rs.view(n, 1), x, st[:, :, 1])) * inv_dt
+    else:
+        v = qd + (sv * gauss(S + 1))
+    rep = lambda a: a.repeat_interleave(nd)
+    o = _proprio_latency(st[:, :, 2:].view(n * nd, L, 2), rep(h), rep(Dl[:, 1]), rep(rs), torch.stack([x, v], -1).view(n * nd, 2)).view(n, nd, 2)
+    st[:, :, 1] = x
+    out[:, 6 * I:6 * I + nd] = o[:, :, 0]
+    out[:, 6 * I + nd:6 * I + 2 * nd] = o[:, :, 1]
+
+    base = 6 * I + 2 * nd
+    zero = torch.zeros((), dtype=f32, device=dev)
+    for k in range(F):
+        cf = contact[:, int(config.foot_body[k])]
+        fx, fy, fz = cf[:, 0], cf[:, 1], cf[:, 2]
+        s = fz * fz.abs() if int(config.contact_mode) == 1 else (fx * fx + fy * fy) + fz * fz
+        st = state["foot"][:, k]
+        p = (st[:, 0] != 0) & ~rs
+        air, con, lair, lcon = (torch.where(rs, zero, st[:, j]) for j in (1, 2, 3, 4))
+        on = torch.where(s > on2, torch.ones_like(p), torch.where(s < off2, torch.zeros_like(p), p))
+        first, left = on & ~p & ~rs, p & ~on
+        lair = torch.where(first, air + dt, lair)
+        lcon = torch.where(left, con + dt, lcon)
+        air = torch.where(on, zero, air + dt)
+        con = torch.where(on, con + dt, zero)
+        m = torch.stack([on.to(f32), first.to(f32), air, con, lair, lcon], -1)
+        o = _proprio_latency(st[:, 5:].view(n, L, 6), h, Dl[:, 2], rs, m)
+        st[:, :5] = torch.stack([m[:, 0], air, con, lair, lcon], -1)
+        for j in range(6):
+            out[:, base + j * F + k] = o[:, j]
+        if switches is not None:
+            switches[:, k] = o[:, 0] != 0
+            switches[:, F + k] = o[:, 1] != 0
+    c1 = (c + 1) & 0xFFFFFFFF
+    cnt[:, :, 0] = torch.where(c1 >= 2 ** 31, c1 - 2 ** 32, c1).to(torch.int32).view(n, 1)
+    cnt[:, :, 1] = torch.where(h + 1 == L, torch.zeros_like(h), h + 1).to(torch.int32).view(n, 1)
+    return out
+
+
 # -- the horizon MPC (csrc/shf_mpc.hip, whose header states the three algorithms step by step; tests/mpc_ref.py holds the NumPy twins)
 def mpc_horizon(state, stance, foot_pos, command, nominal, ticks, dt, touchdown_z, max_step, horizon, steps_per_tick):
     """The MPC's tables: (contact (n, H, F) uint8, xref (n, H + 1, 12), pos (n, H, F, 3)).  The algorithm of shf_mpc_horizon as
